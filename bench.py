@@ -6,21 +6,29 @@ Headline workload (BASELINE.json configs[1]): example-1-style scene S1 on the 12
 a path-sample = one pixel x one pass.  All inputs are resident in HBM
 before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-secondary] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-secondary] [--no-cpu-baseline]]
 
 N > 1 is launched by the driver through torch.distributed.run, one rank per GPU: the frame is
 split into N contiguous row tiles (strong scaling: the frame is fixed), every rank renders its
 tile with no data-path communication, and every step's HDR tiles are gathered to rank 0 over RCCL
 (inside the timed region).
 
-Rank 0 prints ONE JSON line: the headline throughput, the roofline of its dominant kernel
-(k_render_pool), the CPU-oracle baseline timed on this box's host cores, a `secondary` list and, as the
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up, warm-up, the K timed steps,
+the outputs (--dump-outputs) and the line (`metric`, `value`, `unit`, `ms_per_step`, ...).
+
+--dump-outputs DIR: after the timed steps, what they computed -- the HDR frame a caller of accumulate() receives
+(rank 0's frame assembled from the gathered tiles on N GPUs) -- as DIR/hdr.npy (float32, H x W x 3).  The inputs are
+fixed and seeded, so two builds run with the same arguments can be compared output for output.
+
+--full adds what takes runs of its own: the roofline of the dominant kernel (k_render_pool, from instrumented
+launches), the CPU-oracle baseline timed on this box's host cores, a `secondary` list and, as the
 LAST key, a compact `summary` of every workload's value (a record that keeps only the end of the line keeps these):
 on one GPU the other BASELINE configs in their one-GPU form (config 3: sky + clouds + ReSTIR at
 1080p; config 4: dense 128^3 at 3840x2160; config 5: dense 256^3 at 3840x2160), each with its own
 dominant kernel, duration, algorithmic bytes and roofline fraction, plus the reference's own loop
 shape (one sample per call, `scene_api_default`); on N GPUs configs 4 and 5 as BASELINE.json
-defines them -- rows split N ways, the gather inside the timed region.
+defines them -- rows split N ways, the gather inside the timed region.  --no-secondary / --no-cpu-baseline leave
+those parts out of a --full run.
 """
 import argparse
 import ctypes as C
@@ -370,11 +378,18 @@ class ShardedRun:
             elapsed = float(t.item())
         return elapsed, self.sess.stats()
 
-    def check_against_unsharded(self, label):
-        """Rehearsal only (rank 0): the frame assembled from the LAST gathered tiles equals an unsharded render of the same steps."""
+    def frame(self):
+        """Rank 0: the HDR frame of the last step -- the session's own on one GPU, else assembled from the LAST gathered tiles."""
+        if self.world == 1:
+            return self.sess.fetch_hdr()
         full = np.zeros((self.H, self.W, 3), np.float32)
         for r in range(self.world):
             full[self.rank_rows[r]] = self.gathered[r][: len(self.rank_rows[r])].cpu().numpy()
+        return full
+
+    def check_against_unsharded(self, label):
+        """Rehearsal only (rank 0): the frame assembled from the LAST gathered tiles equals an unsharded render of the same steps."""
+        full = self.frame()
         one = self.make_full_session()
         for _ in range(self.steps_done):
             one.accumulate(self.spp)
@@ -433,9 +448,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)   # at least 50 timed frames
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (the last step's HDR frame) as DIR/hdr.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the other configs (`secondary`) and the CPU baseline, each from runs of its own")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the other configs")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py --steps must be at least 1")
 
     from voxel_rt2_amd import scenes, _lib, parallel
     lib = _lib.load()   # before torch touches the device: the library picks the HIP runtime torch ships (and the queue count)
@@ -472,29 +493,22 @@ def main():
     stripes = int(os.environ.get("VRT_BENCH_STRIPES", "0"))
     run = ShardedRun(lib, dist, torch, scene=scene, W=WIDTH, H=HEIGHT, depth=MAX_DEPTH, spp=SPP_PER_STEP, balance=True, stripes=stripes, **common)
     elapsed, st = run.timed(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hdr=run.frame())
     if rehearse and world > 1 and rank == 0:
         run.check_against_unsharded("config 2")
-    bounds = run.bounds
-    # what a path-sample of this rank's tile does: untimed instrumented launches
-    work = count_work(lib, run.sess, SPP_PER_STEP)
-    run.sess.sync()
+    if args.full:
+        # what a path-sample of this rank's tile does: untimed instrumented launches
+        work = count_work(lib, run.sess, SPP_PER_STEP)
+        run.sess.sync()
 
+    out = None   # rank 0's result line
     if rank == 0:
         total_samples = WIDTH * HEIGHT * SPP_PER_STEP * args.steps
         value = total_samples / elapsed / 1e6
         launches = max(st["render_launches"], 1)
         avg_ms = st["render_ms"] / launches
-        samples_per_launch = st["path_samples"] / launches  # a launch renders this rank's pixels x the fused samples
-        counters, counters_note = measured_counters(lib) if world == 1 else ({}, None)
-        render_kernel = "k_render" if os.environ.get("VRT_RENDER") == "fused" else "k_render_pool"
         flags = st.get("pipeline_flags", 0)
-        note = ("HBM is the bound the tier names; the 128^3 working set (8.3 MB) is cache resident and the kernel is bound by vector-instruction "
-                "issue under divergence at 2 waves per SIMD (DESIGN.md 7); `achieved` counts the bytes of the schedule that is timed (fused "
-                "samples share their camera rays: queries counted once), `reference_algorithm` the bytes the reference would move for the same "
-                "paths. Launches overlap: `achieved` / `frac` use a launch's span (what the kernel trace shows), `all_launches_in_flight` "
-                "the period between launches (the chip's rate)")
-        if counters_note:
-            note += "; " + counters_note
         out = {
             "metric": "Mpath-samples/sec at 1920x1080, 8 bounces", "value": round(value, 3), "unit": "Mpath-samples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
@@ -509,14 +523,49 @@ def main():
                                     f"of {ShardedRun.N_TILES} device tiles, RCCL gather of every step's tile (issued when its pass is queued, all inside the "
                                     f"timed region), {parallel.reserved_cus(world)} CUs' worth of workgroup slots left free for the collective; "
                                     f"tile rows {[len(r) for r in run.rank_rows]}") if world > 1 else "none"},
-            "roofline": roofline_block(render_kernel, avg_ms, samples_per_launch, render_bytes(work["reference"]), render_bytes(work["timed"]),
-                                       counters.get("config2_s1_1080p", {}), note, elapsed / launches * 1e3),
-            "work_per_path_sample": {k: {a: round(b, 3) for a, b in v.items()} for k, v in work.items()},
-            "rays_per_s": rays_block(value, work),
             "kernel_ms_per_launch": {"render": round(avg_ms, 4), "temporal": round(st["temporal_ms"] / max(st["temporal_launches"], 1), 4)},
         }
+        if args.dump_outputs:
+            out["outputs"] = {"dir": args.dump_outputs, "files": ["hdr.npy"]}
+        if args.full:
+            samples_per_launch = st["path_samples"] / launches  # a launch renders this rank's pixels x the fused samples
+            counters, counters_note = measured_counters(lib) if world == 1 else ({}, None)
+            render_kernel = "k_render" if os.environ.get("VRT_RENDER") == "fused" else "k_render_pool"
+            note = ("HBM is the bound the tier names; the 128^3 working set (8.3 MB) is cache resident and the kernel is bound by vector-instruction "
+                    "issue under divergence at 2 waves per SIMD (DESIGN.md 7); `achieved` counts the bytes of the schedule that is timed (fused "
+                    "samples share their camera rays: queries counted once), `reference_algorithm` the bytes the reference would move for the same "
+                    "paths. Launches overlap: `achieved` / `frac` use a launch's span (what the kernel trace shows), `all_launches_in_flight` "
+                    "the period between launches (the chip's rate)")
+            if counters_note:
+                note += "; " + counters_note
+            out["roofline"] = roofline_block(render_kernel, avg_ms, samples_per_launch, render_bytes(work["reference"]), render_bytes(work["timed"]),
+                                             counters.get("config2_s1_1080p", {}), note, elapsed / launches * 1e3)
+            out["work_per_path_sample"] = {k: {a: round(b, 3) for a, b in v.items()} for k, v in work.items()}
+            out["rays_per_s"] = rays_block(value, work)
     run.close()
 
+    if args.full:
+        full_extras(args, lib, dist, torch, scenes, out, scene, stripes, common)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(d, **arrays):
+    """DIR/<name>.npy for every array, float32 (the frame is 1920 x 1080 x 3 floats: 24.9 MB)."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def full_extras(args, lib, dist, torch, scenes, out, scene, stripes, common):
+    """--full: the other workloads (`secondary`), the CPU baseline and the `summary`, after the headline's session is closed.
+    `out` is rank 0's result line (None on the other ranks), completed in place."""
+    rank, world, rehearse = common["rank"], common["world"], common["rehearse"]
+    mat, rgb, params = scene
+    counters = measured_counters(lib)[0] if world == 1 else {}
     sec = None
     if not args.no_secondary:
         sec = []
@@ -563,10 +612,6 @@ def main():
                           "roofline_frac": rl["frac"], "roofline_frac_all_launches_in_flight": (rl.get("all_launches_in_flight") or {}).get("frac"),
                           "config3_roofline_frac": ((by_name.get("config3_s6_sky_clouds_restir_1080p") or {}).get("roofline") or {}).get("frac"),
                           "cpu_baseline": (out["cpu_baseline"] or {}).get("value")}
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

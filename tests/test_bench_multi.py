@@ -26,7 +26,7 @@ def test_bench_two_ranks_rehearsal(stripes):
     port = sock.getsockname()[1]
     sock.close()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     for label in ("config 2", "config4_dense_4k", "config5_dense256_4k"):   # the 1080p headline and the two 4K frames defined on N GPUs

@@ -199,23 +199,39 @@ def _session(cfg, mat, rgb, params, cam=None):
     return s
 
 
-def test_pipeline_depth_follows_the_launch_size(monkeypatch):
-    """A caller that changes the sample count of its calls: the depth of the pipeline follows the size of each launch (the
-    pipeline is drained once per change), whatever the first call was.  Development build with the size limits moved so that
-    this small frame has launches of all three kinds: one sample -> eight launches of a quarter of the slots, two -> four of a
-    half, three or four -> two of every slot."""
+def _pipeline_depth_follows_the_launch_size():
+    """The body of test_pipeline_depth_follows_the_launch_size, run in a process of its own."""
     calls = (1, 4, 4, 2, 1, 1, 3, 4, 2, 2, 1) * 2
-    monkeypatch.setenv("VRT_OVERLAP", "0")
+    os.environ["VRT_OVERLAP"] = "0"
     ref, st = render(calls)
+    assert os.environ.get("GPU_MAX_HW_QUEUES") == "16", "the eight-deep pipeline needs sixteen hardware queues"
     assert st["pipeline_flags"] & 1 == 0
-    monkeypatch.delenv("VRT_OVERLAP")
-    monkeypatch.setenv("VRT_DEEPER_ITEMS", str(W * H + 1))
-    monkeypatch.setenv("VRT_DEEP_ITEMS", str(2 * W * H + 1))
+    del os.environ["VRT_OVERLAP"]
+    os.environ["VRT_DEEPER_ITEMS"] = str(W * H + 1)
+    os.environ["VRT_DEEP_ITEMS"] = str(2 * W * H + 1)
     hdr, st = render(calls, dev=True)
     switches = st["pipeline_flags"] >> 24
     assert st["pipeline_flags"] & 1 == 1 and switches >= 12, st
     assert (st["pipeline_flags"] >> 2) & 7 == 4 and (st["pipeline_flags"] >> 5) & 7 == 4, "the last call was one sample: eight launches of a quarter"
     assert np.array_equal(hdr.view(np.uint32), ref.view(np.uint32))
+
+
+def test_pipeline_depth_follows_the_launch_size():
+    """A caller that changes the sample count of its calls: the depth of the pipeline follows the size of each launch (the
+    pipeline is drained once per change), whatever the first call was.  Development build with the size limits moved so that
+    this small frame has launches of all three kinds: one sample -> eight launches of a quarter of the slots, two -> four of a
+    half, three or four -> two of every slot.  The eight-deep pipeline needs sixteen hardware queues, which the runtime reads
+    when it starts: so the test runs in a child process started without GPU_MAX_HW_QUEUES, where _lib.load asks for them."""
+    code = textwrap.dedent("""
+        import os, sys
+        sys.path[:0] = [%r, os.path.join(%r, "tests")]
+        import test_gpu_pipeline
+        test_gpu_pipeline._pipeline_depth_follows_the_launch_size()
+        print("depth follows the launch size: ok")
+    """) % (ROOT, ROOT)
+    env = {k: v for k, v in os.environ.items() if k not in ("GPU_MAX_HW_QUEUES", "VRT_OVERLAP", "VRT_DEEP_ITEMS", "VRT_DEEPER_ITEMS")}
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0 and "depth follows the launch size: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
 def test_pipeline_depth_of_the_shipped_library_at_900p(monkeypatch):

@@ -5,7 +5,7 @@
 # (no further GPU step is started after one that was killed).  Steps:
 #   smoke           __graft_entry__.smoke()
 #   tests           the whole GPU suite;           tests:EXPR  -> pytest -k EXPR
-#   bench           the judged line (bench.py) + a short digest
+#   bench           the judged line with everything else it measures (bench.py --full) + a short digest
 #   scenes[:names]  tools/bench_scenes.py [names, comma separated]
 #   refidx          tools/ref_indexing_diff.py on configs 4 and 5 (GPU)
 #   trace:CASE      rocprofv3 --kernel-trace --stats of bench_scenes.py CASE (CASE = bench: the bench command, config 2)
@@ -31,7 +31,7 @@ for step in "$@"; do
       else timeout -k 10 1000 python -m pytest tests/ -x -q -m gpu > $O/pytest_gpu.log 2>&1 || { rc=$?; tail -30 $O/pytest_gpu.log; fail tests $rc; }; fi
       tail -1 $O/pytest_gpu.log ;;
     bench)
-      timeout -k 10 600 python bench.py $arg > $O/bench.json 2> $O/bench.err || { rc=$?; tail -5 $O/bench.err; fail bench $rc; }
+      timeout -k 10 600 python bench.py --full $arg > $O/bench.json 2> $O/bench.err || { rc=$?; tail -5 $O/bench.err; fail bench $rc; }
       python tools/bench_digest.py $O/bench.json ;;
     scenes)
       timeout -k 10 900 python tools/bench_scenes.py ${arg//,/ } > $O/scenes${arg:+_}${arg//,/_}.jsonl 2> $O/scenes.err || { rc=$?; tail -5 $O/scenes.err; fail scenes $rc; }
