@@ -69,6 +69,40 @@ def test_traversal_counters_match_oracle_256(render_schedule):
     assert_same(g, o, bufs=())
 
 
+def reference_indexing_pair():
+    """dense256 at 480x272, 8 bounces: a frame where the reference's reading of cells outside the grid (vrt_set_reference_indexing:
+    ref_bit<256>, descend_outside<256>, the l3 word of cell_occupied) changes dozens of pixels.  Returns the GPU and oracle
+    sessions in that mode and an oracle in the default mode."""
+    cfg = config("dense256", 480, 272, 8, seed=3)
+    g, o = pair("dense256", cfg, threads=16)
+    default = orc.Oracle(cfg, threads=16)
+    orc.setup(default, *scene("dense256"))
+    for s in (g, o):
+        s.set_reference_indexing(True)
+    return g, o, default
+
+
+def test_hdr_matches_oracle_256_reference_indexing(render_schedule):
+    g, o, default = reference_indexing_pair()
+    for s in (g, o, default):
+        s.accumulate(2)
+    assert (default.fetch_hdr() != o.fetch_hdr()).any(-1).sum() >= 20, "the modes must differ on this frame"
+    assert_same(g, o)
+    assert np.array_equal(g.fetch_ldr().view(np.uint32), o.fetch_ldr().view(np.uint32))
+
+
+def test_traversal_counters_match_oracle_256_reference_indexing(render_schedule):
+    g, o, default = reference_indexing_pair()
+    assert _lib.load().vrt_set_instrumented(g._ctx, 1) == 0
+    for s in (g, o, default):
+        s.accumulate(2)
+    sg, so, sd = g.stats(), o.stats(), default.stats()
+    assert so["occupancy_queries"] != sd["occupancy_queries"], "the modes must walk differently on this frame"
+    for k in ("rays", "dda_iters", "occupancy_queries", "closest_hits"):
+        assert sg[k] == so[k], (k, sg[k], so[k])
+    assert_same(g, o, bufs=())
+
+
 def test_restir_256():
     g, o = pair("sponge256", config("sponge256", 128, 80, 5, seed=7, use_restir=True))
     for s in (g, o):

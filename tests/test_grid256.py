@@ -148,6 +148,23 @@ def test_emulated_device_code_matches_oracle_256(render_schedule, name, W, H, de
     assert e.stats()["occupancy_queries"] > 0
 
 
+def test_emulated_device_code_with_reference_indexing_256(render_schedule):
+    """vrt_set_reference_indexing at 256^3: cells outside the grid read the bit the reference's index arithmetic addresses
+    (ref_bit<256>, descend_outside<256>, and the l3 word of cell_occupied for LODs 6 and 7: vrt_trace.h).  A frame large enough
+    for the two modes to differ on many pixels, so that the comparison cannot pass on code that ignores the mode."""
+    mat, rgb, params = scene("dense256")
+    cfg = host.make_config(480, 272, voxel_edges=params["voxel_edges"], exposure=params["exposure"], max_depth=8, seed=3, grid_res=256)
+    default, o, e = orc.Oracle(cfg, threads=8), orc.Oracle(cfg, threads=8), emu.Emulated(cfg)
+    for s in (default, o, e):
+        orc.setup(s, mat, rgb, params)
+    for s in (o, e):
+        s.set_reference_indexing(True)
+    for s in (default, o, e):
+        s.accumulate(2)
+    assert (default.fetch_hdr() != o.fetch_hdr()).any(-1).sum() >= 20
+    assert_same(o, e, stats=True)   # (with the reference's indexing no ray is culled: every ray is walked and counted)
+
+
 def test_emulated_restir_256():
     mat, rgb, params = scene("sponge256")
     cfg = host.make_config(80, 56, voxel_edges=params["voxel_edges"], exposure=params["exposure"], max_depth=4, seed=7, use_restir=True,
