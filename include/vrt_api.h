@@ -193,6 +193,25 @@ int vrt_hdr_targets_written(vrt_ctx* ctx, uint64_t* count);
  * vrt_fetch_hdr_device / the tiles of vrt_set_hdr_targets hold the context's rows stripe after stripe.  Static camera, ReSTIR off.
  * Call before the first vrt_accumulate; stripe_rows = 0 turns it off.  No counterpart in the reference (one GPU). */
 int vrt_set_row_stripes(vrt_ctx* ctx, int stripe_rows, int n_parts, int part);
+/* The MOVING camera on contiguous row tiles (set_camera_is_moving, scene.py:206-262).  The moving-camera accumulation pass resamples
+ * the previous frame's histories, depth and normals at each pixel's reprojected position (pathtracer.py:993-1000, 1092-1183), which
+ * can be any row of the frame, while a tile's buffers hold its own rows and a halo.  A row tile that opts in keeps a whole-frame copy
+ * of that previous state; each vrt_accumulate call stores the tile's own rows in it (behind the call's last pass, on the context's
+ * stream), and the caller imports every other row from the other tiles between calls (voxel_rt2_amd/parallel.py, exchange_history).
+ * Per step: vrt_accumulate(1) -> export own rows / all-gather / import the others -> vrt_set_camera / vrt_reset -> vrt_accumulate.
+ *   vrt_set_history_exchange: before the first vrt_accumulate (else VRT_E_STATE).  On a row tile it allocates the planes (40 B a
+ *     pixel of the whole frame), zeroed like a fresh context's state; on a whole-frame context it is accepted and changes nothing;
+ *     with row stripes (either order) VRT_E_INVALID: stripes stay static-camera only.  vrt_set_camera accepts camera_is_moving on a
+ *     row tile only with it on.  A moving vrt_accumulate on such a tile takes n_samples = 1 (else VRT_E_INVALID) and needs every row
+ *     outside the tile's own imported since the previous call (else VRT_E_STATE; not before the first call).  vrt_reset also
+ *     zeroes the whole frame's histories (every rank resets in the same step); imported g-buffer rows stay.
+ *   vrt_history_rows_io: rows [row0, row1) between the library and caller-owned DEVICE memory, queued on the context's stream.
+ *     Record: four planes back to back, each [row1-row0][W]: diffuse history f32x4, specular history f32x4, g-buffer depth f32,
+ *     g-buffer normal u32 (the oct encoding of VRT_BUF_GBUF_NORMAL) -- 40 bytes a pixel.  to_library = 0 exports rows inside the
+ *     context's own rows, as the most recent vrt_accumulate left them; 1 imports rows outside them (row tile with the exchange on,
+ *     else VRT_E_STATE).  Other ranges: VRT_E_INVALID.  No counterpart in the reference (one GPU). */
+int vrt_set_history_exchange(vrt_ctx* ctx, int on);
+int vrt_history_rows_io(vrt_ctx* ctx, int row0, int row1, void* device_ptr, int to_library);
 int vrt_fetch_buffer(vrt_ctx* ctx, int which, void* out);
 int vrt_sync(vrt_ctx* ctx);
 int vrt_get_stats(vrt_ctx* ctx, vrt_stats* out);

@@ -94,3 +94,5 @@ def declare(lib, prefix):
     sig("is_instrumented", C.c_int)
     sig("set_reference_indexing", C.c_int, P, C.c_int)
     sig("set_row_stripes", C.c_int, P, C.c_int, C.c_int, C.c_int)
+    sig("set_history_exchange", C.c_int, P, C.c_int)
+    sig("history_rows_io", C.c_int, P, C.c_int, C.c_int, P, C.c_int)

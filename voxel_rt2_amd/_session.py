@@ -100,6 +100,21 @@ class NativeSession:
         self._call("set_row_stripes", int(stripe_rows), int(n_parts), int(part))
         self.stripes = (int(stripe_rows), int(n_parts), int(part)) if stripe_rows else None
 
+    @property
+    def io_on_device(self):
+        """Whether the *_io entry points take device memory (the HIP library) or host memory (the oracle)."""
+        return self._p == "vrt_"
+
+    def set_history_exchange(self, on=True):
+        """Row tile: keep the previous frame's temporal state of the whole frame, so that the moving camera can run on it
+        (include/vrt_api.h, vrt_set_history_exchange; parallel.exchange_history moves the rows between ranks)."""
+        self._call("set_history_exchange", int(bool(on)))
+
+    def history_rows_io(self, row0, row1, ptr, to_library):
+        """Rows [row0, row1) of the temporal state <-> device memory at `ptr`: four planes back to back, 40 bytes a pixel
+        (include/vrt_api.h, vrt_history_rows_io).  to_library False exports own rows, True imports other rows."""
+        self._call("history_rows_io", int(row0), int(row1), C.c_void_p(int(ptr)), int(bool(to_library)))
+
     def owned_rows(self):
         """Row indices this session produces, in the order its device tiles hold them."""
         st = getattr(self, "stripes", None)

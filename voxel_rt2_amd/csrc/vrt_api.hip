@@ -219,6 +219,15 @@ struct vrt_ctx {
     bool fetch_valid[VRT_FETCH_SLOTS] = {}, cbuf_read_pending[2] = {};
     unsigned last_full_seq = 0;          // launch_seq + 1 of the most recent launch that took every workgroup slot (0: none)
     int hist_in = 0;  // history ping-pong
+    // History exchange (vrt_set_history_exchange): a row tile's whole-frame copy of the previous frame's temporal state, which the
+    // moving-camera pass resamples from.  Own rows are stored by every vrt_accumulate call, the other rows imported by the caller
+    // (vrt_history_rows_io); hx_row_epoch[r] = hx_epoch when row r was imported after the most recent call.
+    bool hx_on = false;               // opted in (also on a whole-frame context, where it changes nothing)
+    f4 *d_hx_hist_d = nullptr, *d_hx_hist_s = nullptr;   // [H][W], allocated on a row tile only
+    float* d_hx_depth = nullptr;
+    uint32_t* d_hx_normal = nullptr;
+    std::vector<unsigned> hx_row_epoch;
+    unsigned hx_epoch = 0;            // vrt_accumulate calls since the opt-in
     mat4 prev_view{}, prev_proj{};
     uint32_t frame = 0;
     unsigned launch_seq = 0;  // render launches so far (selects which of the two work counters a launch uses)
@@ -535,7 +544,8 @@ void vrt_destroy(vrt_ctx* c) {
                     c->d_sky_trans, c->d_cloud_ambient, c->d_trans_lut, c->d_cloud_tex, c->d_cbuf[0], c->d_cbuf[1], c->d_spec_planes, c->d_color_d2,
                     c->d_color_s2, c->d_gb_pos, c->d_gb_normal[0], c->d_gb_normal[1], c->d_gb_depth[0], c->d_gb_depth[1],
                     c->d_gb_mat, c->d_refl_planes, c->d_gb_refl_f, c->d_hist_d[0], c->d_hist_d[1], c->d_hist_s[0], c->d_hist_s[1],
-                    c->d_ldr, c->d_ldr8, c->d_res[1], c->d_res_planes, c->d_multi_d, c->d_pool_scratch, c->d_gris_geo, c->d_gris_src, c->d_gris_tst, c->d_mats_x};
+                    c->d_ldr, c->d_ldr8, c->d_res[1], c->d_res_planes, c->d_multi_d, c->d_pool_scratch, c->d_gris_geo, c->d_gris_src, c->d_gris_tst, c->d_mats_x,
+                    c->d_hx_hist_d, c->d_hx_hist_s, c->d_hx_depth, c->d_hx_normal};
     for (void* p : ptrs)
         if (p) hipFree(p);
     if (c->stream && c->owns_stream) hipStreamDestroy(c->stream);
@@ -581,7 +591,7 @@ int vrt_set_scene(vrt_ctx* c, const vrt_scene_params* s) {
 int vrt_set_camera(vrt_ctx* c, const vrt_camera* cam) {
     if (!c || !cam) return fail(VRT_E_INVALID, "null argument");
     if (!(cam->render_scale > 0.0f) || cam->render_scale > 1.0f) return fail(VRT_E_INVALID, "render_scale must be in (0, 1]");
-    if (cam->camera_is_moving && (c->own0 != 0 || c->own1 != c->cfg.height || c->stripe_rows))
+    if (cam->camera_is_moving && (c->own0 != 0 || c->own1 != c->cfg.height || c->stripe_rows) && !c->d_hx_hist_d)
         return fail(VRT_E_INVALID, "row-sharded contexts support the static camera only (history resampling crosses tiles)");
     c->cam = *cam;
     c->have_cam = true;
@@ -602,10 +612,84 @@ int vrt_set_row_stripes(vrt_ctx* c, int stripe_rows, int n_parts, int part) {
     if (c->own0 != 0 || c->own1 != c->cfg.height) return fail(VRT_E_INVALID, "row stripes are a property of a whole-frame context (row_begin = row_end = 0)");
     if (c->cfg.use_restir) return fail(VRT_E_INVALID, "row stripes with ReSTIR would render a 24-row halo around every stripe: use contiguous row tiles");
     if (c->have_cam && c->cam.camera_is_moving) return fail(VRT_E_INVALID, "row stripes support the static camera only");
+    if (c->hx_on) return fail(VRT_E_INVALID, "row stripes support the static camera only: no history exchange");
     if (c->frame != 0) return fail(VRT_E_STATE, "set the stripes before the first vrt_accumulate");
     c->stripe_rows = stripe_rows; c->stripe_parts = n_parts; c->stripe_part = part;
     return VRT_OK;
 }
+// ---- history exchange: the moving camera on row tiles ------------------------------------------------------------------------
+// The moving-camera pass resamples the previous frame's histories, depth and normals at each pixel's reprojected position, which
+// can be any row of the frame (pathtracer.py:993-1000, 1092-1183).  A row tile that opts in keeps all four as frame-sized planes:
+// every vrt_accumulate call stores the tile's own rows there, the caller imports the other tiles' rows between calls.
+static bool is_row_tile(const vrt_ctx* c) { return c->own0 != 0 || c->own1 != c->cfg.height; }
+static void free_history_planes(vrt_ctx* c) {
+    void* p[] = {c->d_hx_hist_d, c->d_hx_hist_s, c->d_hx_depth, c->d_hx_normal};
+    for (void* q : p)
+        if (q) hipFree(q);
+    c->d_hx_hist_d = c->d_hx_hist_s = nullptr; c->d_hx_depth = nullptr; c->d_hx_normal = nullptr;
+    c->hx_row_epoch.clear();
+}
+int vrt_set_history_exchange(vrt_ctx* c, int on) {
+    if (!c) return fail(VRT_E_INVALID, "null context");
+    if (c->stripe_rows) return fail(VRT_E_INVALID, "row stripes support the static camera only: no history exchange");
+    if (c->frame != 0) return fail(VRT_E_STATE, "set the history exchange before the first vrt_accumulate");
+    if (!on && c->have_cam && c->cam.camera_is_moving && is_row_tile(c))
+        return fail(VRT_E_INVALID, "the moving camera on a row tile needs the history exchange: set a static camera first");
+    HIP_TRY(hipSetDevice(c->device));
+    c->hx_on = on != 0;
+    if (!c->hx_on || !is_row_tile(c)) { free_history_planes(c); return VRT_OK; }   // a whole-frame context has nothing to import
+    if (c->d_hx_hist_d) return VRT_OK;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (dalloc(&c->d_hx_hist_d, n) != hipSuccess || dalloc(&c->d_hx_hist_s, n) != hipSuccess || dalloc(&c->d_hx_depth, n) != hipSuccess ||
+        dalloc(&c->d_hx_normal, n) != hipSuccess) {
+        (void)hipGetLastError();
+        free_history_planes(c);
+        c->hx_on = false;
+        return fail(VRT_E_DEVICE, "no device memory for the whole-frame history planes");
+    }
+    c->hx_row_epoch.assign((size_t)c->cfg.height, 0u);
+    c->hx_epoch = 0;
+    return VRT_OK;
+}
+// Rows [row0, row1) of the temporal state <-> caller-owned device memory: four planes back to back, each [row1 - row0][W]
+// (diffuse history f32x4, specular history f32x4, g-buffer depth f32, g-buffer normal u32): 40 bytes a pixel.  Export
+// (to_library = 0): rows of the context's own, as the most recent vrt_accumulate left them.  Import (1): rows outside them,
+// into the whole-frame planes of a row tile with history exchange.  Queued on the context's stream.
+int vrt_history_rows_io(vrt_ctx* c, int row0, int row1, void* device_ptr, int to_library) {
+    if (!c || !device_ptr) return fail(VRT_E_INVALID, "null argument");
+    if (c->stripe_rows) return fail(VRT_E_INVALID, "row stripes support the static camera only: no history exchange");
+    if (row0 < 0 || row1 > c->cfg.height || row1 <= row0) return fail(VRT_E_INVALID, "row range outside the image");
+    if (!to_library && (row0 < c->own0 || row1 > c->own1)) return fail(VRT_E_INVALID, "export: rows must lie inside the context's own rows");
+    if (to_library && row0 < c->own1 && row1 > c->own0) return fail(VRT_E_INVALID, "import: rows must lie outside the context's own rows");
+    if (to_library && !c->d_hx_hist_d) return fail(VRT_E_STATE, "import needs vrt_set_history_exchange on a row tile");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t W = c->cfg.width, rows = (size_t)(row1 - row0);
+    char* rec = (char*)device_ptr;
+    char* const planes[4] = {rec, rec + rows * W * 16, rec + rows * W * 32, rec + rows * W * 36};
+    const size_t elem[4] = {16, 16, 4, 4};
+    c->main_dirty = true;
+    if (to_library) {
+        void* const dst[4] = {c->d_hx_hist_d, c->d_hx_hist_s, c->d_hx_depth, c->d_hx_normal};
+        for (int k = 0; k < 4; k++)
+            HIP_TRY(hipMemcpyAsync((char*)dst[k] + (size_t)row0 * W * elem[k], planes[k], rows * W * elem[k], hipMemcpyDeviceToDevice, c->stream));
+        for (int r = row0; r < row1; r++) c->hx_row_epoch[(size_t)r] = c->hx_epoch;
+    } else {
+        const void* const src[4] = {c->d_hist_d[c->hist_in], c->d_hist_s[c->hist_in], c->last_gb_depth, c->last_gb_normal};
+        for (int k = 0; k < 4; k++)
+            HIP_TRY(hipMemcpyAsync(planes[k], (const char*)src[k] + (size_t)(row0 - c->buf0) * W * elem[k], rows * W * elem[k], hipMemcpyDeviceToDevice, c->stream));
+    }
+    return VRT_OK;
+}
+// after a vrt_accumulate call: the tile's own rows of the new state into the whole-frame planes (behind the call's last pass)
+static int store_history_rows(vrt_ctx* c) {
+    const size_t W = c->cfg.width, rows = (size_t)(c->own1 - c->own0), off = (size_t)(c->own0 - c->buf0) * W, at = (size_t)c->own0 * W;
+    HIP_TRY(hipMemcpyAsync(c->d_hx_hist_d + at, c->d_hist_d[c->hist_in] + off, rows * W * sizeof(f4), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_hx_hist_s + at, c->d_hist_s[c->hist_in] + off, rows * W * sizeof(f4), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_hx_depth + at, c->last_gb_depth + off, rows * W * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_hx_normal + at, c->last_gb_normal + off, rows * W * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    return VRT_OK;
+}
+
 int vrt_set_instrumented(vrt_ctx* c, int on) {
     if (!c) return fail(VRT_E_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
@@ -852,6 +936,14 @@ int vrt_accumulate(vrt_ctx* c, int n_samples) {
     if (!c || n_samples < 0) return fail(VRT_E_INVALID, "bad argument");
     if (!c->prepared) return fail(VRT_E_STATE, "vrt_prepare has not run since the last voxel upload");
     if (!c->have_cam) return fail(VRT_E_STATE, "vrt_set_camera has not been called");
+    const bool hx = c->d_hx_hist_d != nullptr && n_samples > 0;
+    if (hx && c->cam.camera_is_moving) {
+        if (n_samples != 1)
+            return fail(VRT_E_INVALID, "moving camera on a row tile: one sample per call (each sample resamples the other tiles' state from the sample before)");
+        for (int r = 0; r < c->cfg.height && c->hx_epoch > 0; r++)
+            if ((r < c->own0 || r >= c->own1) && c->hx_row_epoch[(size_t)r] != c->hx_epoch)
+                return fail(VRT_E_STATE, "history row " + std::to_string(r) + " has not been imported since the last vrt_accumulate (vrt_history_rows_io)");
+    }
     HIP_TRY(hipSetDevice(c->device));
 #if defined(VRT_HOST_PROFILE)
     const double t_acc = prof_now();
@@ -862,6 +954,10 @@ int vrt_accumulate(vrt_ctx* c, int n_samples) {
 #endif
     if (rc != VRT_OK) abort_pipeline(c);
     else c->hdr_targets_committed = c->hdr_targets_written;
+    if (rc == VRT_OK && hx) {
+        if (store_history_rows(c) != VRT_OK) { abort_pipeline(c); return VRT_E_DEVICE; }
+        c->hx_epoch++;
+    }
     return rc;
 }
 
@@ -1074,6 +1170,12 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
             // (the "previous" g-buffer of a launch's later samples is the launch's own: a launch per sample would have written it again)
             tb.prev_normal = s == 0 ? c->last_gb_normal : c->d_gb_normal[c->cur];
             tb.prev_depth = s == 0 ? c->last_gb_depth : c->d_gb_depth[c->cur];
+            // a row tile's moving camera: the previous state of the whole frame (history exchange; one sample per call)
+            const bool frame_prev = c->d_hx_hist_d && fps.camera_is_moving;
+            if (frame_prev) {
+                tb.hist_d_in = c->d_hx_hist_d; tb.hist_s_in = c->d_hx_hist_s;
+                tb.prev_normal = c->d_hx_normal; tb.prev_depth = c->d_hx_depth;
+            }
             tb.hdr = c->d_cbuf[ci ^ 1];
             tb.sample_stride = restir ? 0 : out.sample_stride;
             tb.prev_view = c->prev_view; tb.prev_proj = c->prev_proj;
@@ -1089,7 +1191,7 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
                 const int n_own = (int)owned_ranges(c).size() * c->stripe_rows;   // (a last stripe cut short by the frame's edge is cut there)
                 HIP_TRY(launch_temporal(c->stream, fps, tb, 0, n_own, g));
             } else {
-                HIP_TRY(launch_temporal(c->stream, fps, tb, c->own0, c->own1, restir ? 1 : g));
+                HIP_TRY(launch_temporal(c->stream, fps, tb, c->own0, c->own1, restir ? 1 : g, frame_prev));
             }
             if (timed) HIP_TRY(hipEventRecord(b, c->stream));
             c->passes_n[1]++;
@@ -1121,6 +1223,11 @@ int vrt_reset(vrt_ctx* c) {
     for (int s = 0; s < 2; s++) {
         HIP_TRY(hipMemsetAsync(c->d_hist_d[s], 0, c->npix * sizeof(f4), c->stream));
         HIP_TRY(hipMemsetAsync(c->d_hist_s[s], 0, c->npix * sizeof(f4), c->stream));
+    }
+    if (c->d_hx_hist_d) {   // the whole frame's histories, as every rank's reset_framebuffer in the same step (imported g-buffer rows stay)
+        const size_t n = (size_t)c->cfg.width * c->cfg.height;
+        HIP_TRY(hipMemsetAsync(c->d_hx_hist_d, 0, n * sizeof(f4), c->stream));
+        HIP_TRY(hipMemsetAsync(c->d_hx_hist_s, 0, n * sizeof(f4), c->stream));
     }
     return VRT_OK;
 }

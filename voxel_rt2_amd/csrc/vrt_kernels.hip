@@ -11,6 +11,7 @@
 //   k_mat_derived                                         per-material-id part of a shading point (after material uploads)
 //   k_temporal                                            fused temporal accumulation -> HDR (sized to run beside
 //                                                         the next render launch, see vrt_api.hip)
+//   k_temporal_frame_prev                                 the same, moving camera on a row tile with history exchange
 //   k_tonemap                                             LDR presentation
 //
 // k_render is a persistent-thread kernel: the grid is sized to the device's residency, each wave
@@ -884,6 +885,13 @@ __global__ __launch_bounds__(64 * VRT_TEMPORAL_ROWS) __attribute__((amdgpu_num_v
     const int v = (k / fp.stripe_rows) * fp.stripe_period + fp.stripe_first + k % fp.stripe_rows;
     if (u < fp.W && v < fp.H) temporal_pixel<true>(fp, tb, u, v, n_samples);
 }
+// the moving-camera pass of a row tile with history exchange (vrt_set_history_exchange): the previous frame's histories and
+// g-buffer come from whole-frame planes (the reprojected taps land on any row), the rest from the tile's own + halo rows
+__global__ __launch_bounds__(64 * VRT_TEMPORAL_ROWS) __attribute__((amdgpu_num_vgpr(VRT_TEMPORAL_HALF_VGPRS))) void k_temporal_frame_prev(FrameParams fp, TemporalBuffers tb, int r0, int r1, int n_samples) {
+    const int u = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int v = r0 + blockIdx.y * VRT_TEMPORAL_ROWS + (threadIdx.x >> 6);
+    if (u < fp.W && v < r1) temporal_pixel<false, true>(fp, tb, u, v, n_samples);
+}
 __global__ __launch_bounds__(256) void k_tonemap(FrameParams fp, const f3* hdr, f4* ldr, int r0, int r1) {
     const int u = blockIdx.x * 64 + (threadIdx.x & 63);
     const int v = r0 + blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -1065,9 +1073,10 @@ hipError_t launch_gris(hipStream_t st, int grid_res, bool instr, const FramePara
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }
-hipError_t launch_temporal(hipStream_t st, const FrameParams& fp, const TemporalBuffers& tb, int r0, int r1, int n_samples) {
+hipError_t launch_temporal(hipStream_t st, const FrameParams& fp, const TemporalBuffers& tb, int r0, int r1, int n_samples, bool frame_prev) {
     dim3 g((fp.W + 63) / 64, (r1 - r0 + VRT_TEMPORAL_ROWS - 1) / VRT_TEMPORAL_ROWS), b(64 * VRT_TEMPORAL_ROWS);
-    if (fp.stripe_period) hipLaunchKernelGGL(k_temporal_stripes, g, b, 0, st, fp, tb, r1 - r0, n_samples);   // (r0 = 0, r1 = the context's own rows)
+    if (frame_prev) hipLaunchKernelGGL(k_temporal_frame_prev, g, b, 0, st, fp, tb, r0, r1, n_samples);
+    else if (fp.stripe_period) hipLaunchKernelGGL(k_temporal_stripes, g, b, 0, st, fp, tb, r1 - r0, n_samples);   // (r0 = 0, r1 = the context's own rows)
     else hipLaunchKernelGGL(k_temporal, g, b, 0, st, fp, tb, r0, r1, n_samples);
     VRT_LAUNCH_CHECK();
     return hipSuccess;

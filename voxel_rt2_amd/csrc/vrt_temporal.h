@@ -33,7 +33,8 @@ struct TemporalBuffers {
     const f4* hist_s_in;
     f4* hist_s_out;
     const uint32_t* prev_normal;  // gbuff_prev_normals / gbuff_prev_depth
-    const float* prev_depth;
+    const float* prev_depth;      // (FRAME_PREV: hist_*_in, prev_normal and prev_depth are the whole-frame planes of a row tile
+                                  //  with history exchange, rows from 0 -- vrt_set_history_exchange, vrt_api.hip)
     f3* hdr;                      // color_buffer after accumulate(); becomes the next pass's render target
     int sample_stride;            // elements between the planes of consecutive fused samples (colours, raw reflection depth)
     mat4 prev_view, prev_proj;    // prev_view_mat / prev_proj_mat (pathtracer.py:103-104, 283-287)
@@ -109,8 +110,9 @@ VRT_DEV float catmullrom(float x) {  // pathtracer.py:1002-1014
     else if (x < 2.0f) fx = -0.5f * x3 + 2.5f * x2 - 4.0f * x + 2.0f;
     return fx;
 }
-// pathtracer.py:1092-1130 (DEPTH_TEST) and 1132-1183 (without): 4x4 Catmull-Rom history resample
-template <bool DEPTH_TEST>
+// pathtracer.py:1092-1130 (DEPTH_TEST) and 1132-1183 (without): 4x4 Catmull-Rom history resample.  FRAME_PREV: the previous
+// frame's history, depth and normal are read from frame-sized planes (absolute rows), not from the shard's own + halo rows
+template <bool DEPTH_TEST, bool FRAME_PREV = false>
 VRT_DEV float history_resample(const FrameParams& fp, const TemporalBuffers& tb, const f4* hist, f2 uv, float center_depth,
                                f3 center_normal, f4& out) {
     int rx, ry;
@@ -124,7 +126,7 @@ VRT_DEV float history_resample(const FrameParams& fp, const TemporalBuffers& tb,
         for (int y = -1; y < 3; y++) {
             int tx = icx + x, ty = icy + y;
             if (tx < 0 || ty < 0 || tx > rx - 1 || ty > ry - 1) continue;
-            int t = (ty - fp.row0) * fp.W + tx;
+            int t = (FRAME_PREV ? ty : ty - fp.row0) * fp.W + tx;
             float w = catmullrom(dm_abs((float)x - fx)) * catmullrom(dm_abs((float)y - fy));
             f3 tn = oct_decode(tb.prev_normal[t]);
             if (fp.camera_is_moving == 1) {
@@ -164,15 +166,17 @@ VRT_DEV void blend_history(const FrameParams& fp, float wsum, f4& h, f3 cur) {  
 // One pixel (u, v) of this shard's rows.  n_samples > 1: the samples of one accumulate(n) call, rendered by one
 // fused k_render launch into consecutive planes (static camera only): the running means are advanced n times in
 // registers, in sample order, exactly as n separate passes would, and the histories / HDR are written once.
-template <bool STRIPED = false>
+// FRAME_PREV: the incoming histories and the previous g-buffer are whole-frame planes (see TemporalBuffers).
+template <bool STRIPED = false, bool FRAME_PREV = false>
 VRT_DEV void temporal_pixel(const FrameParams& fp, const TemporalBuffers& tb, int u, int v, int n_samples) {
     const int idx = (v - fp.row0) * fp.W + u;
+    const int hidx = FRAME_PREV ? v * fp.W + u : idx;   // this pixel in the incoming histories
     if (outside_render_area(fp, (float)u, (float)v)) {
         // not rendered at this render_scale: the reference leaves color_buffer (= the last HDR value) untouched.
         // The render target and the HDR target swap roles every pass, so carry the value across.
         store_hdr<STRIPED>(fp, tb, idx, u, v, tb.color_d[idx]);
-        tb.hist_d_out[idx] = tb.hist_d_in[idx];
-        tb.hist_s_out[idx] = tb.hist_s_in[idx];
+        tb.hist_d_out[idx] = tb.hist_d_in[hidx];
+        tb.hist_s_out[idx] = tb.hist_s_in[hidx];
         return;
     }
     int rx, ry;
@@ -205,14 +209,14 @@ VRT_DEV void temporal_pixel(const FrameParams& fp, const TemporalBuffers& tb, in
     const f3 x1 = xform(fp.view_inv, screen_to_view(tc, nl_depth, fp.proj_inv), 1.0f);
     if (near_zero3(x1)) {  // both filters `continue`: colour stays the scrubbed diffuse sample, histories persist
         store_hdr<STRIPED>(fp, tb, idx, u, v, scrub(tb.color_d[last + idx]));
-        tb.hist_d_out[idx] = tb.hist_d_in[idx];
-        tb.hist_s_out[idx] = tb.hist_s_in[idx];
+        tb.hist_d_out[idx] = tb.hist_d_in[hidx];
+        tb.hist_s_out[idx] = tb.hist_s_in[hidx];
         return;
     }
     f4 hd, hs;
     if (fp.camera_is_moving == 0) {
-        hd = tb.hist_d_in[idx];
-        hs = tb.hist_s_in[idx];
+        hd = tb.hist_d_in[hidx];
+        hs = tb.hist_s_in[hidx];
         for (int k = 0; k < n_samples; k++) {
             f3 cur_d, cur_s;
             bilinear_color2(fp, tb.color_d + k * tb.sample_stride, tb.color_s + k * tb.sample_stride, tc, cur_d, cur_s);
@@ -224,11 +228,11 @@ VRT_DEV void temporal_pixel(const FrameParams& fp, const TemporalBuffers& tb, in
         const f3 cur_s = bilinear_color(fp, tb.color_s, tc);
         const f3 n1 = oct_decode(tb.gb_normal[idx]);
         f3 rp = reproject(fp, tb, x1);
-        float wd = history_resample<true>(fp, tb, tb.hist_d_in, mk2(rp.x, rp.y), linearize_depth(rp.z, fp.proj_inv), n1, hd);
+        float wd = history_resample<true, FRAME_PREV>(fp, tb, tb.hist_d_in, mk2(rp.x, rp.y), linearize_depth(rp.z, fp.proj_inv), n1, hd);
         float nl = delinearize_depth(refl_depth, fp.proj);
         f3 refl_pos = xform(fp.view_inv, screen_to_view(tc, nl, fp.proj_inv), 1.0f);
         f3 rps = reproject(fp, tb, (refl_depth != 0.0f) ? refl_pos : x1);
-        float ws = history_resample<false>(fp, tb, tb.hist_s_in, mk2(rps.x, rps.y), linearize_depth(rps.z, fp.proj_inv), n1, hs);
+        float ws = history_resample<false, FRAME_PREV>(fp, tb, tb.hist_s_in, mk2(rps.x, rps.y), linearize_depth(rps.z, fp.proj_inv), n1, hs);
         blend_history(fp, wd, hd, cur_d);
         blend_history(fp, ws, hs, cur_s);
     }

@@ -55,6 +55,51 @@ def gather_frame(tile, height, width, rank, world_size, dst=0, out_list=None):
     return frame
 
 
+# ---- the moving camera on row tiles: history exchange ----------------------------------------------------------------------------
+# The moving-camera accumulation pass resamples the previous frame's histories and g-buffer at reprojected positions that can
+# fall on any row (reference renderer/pathtracer.py:993-1000, 1092-1183).  A rank's context keeps a whole-frame copy of that
+# state (include/vrt_api.h, vrt_set_history_exchange); after every accumulate(1) the ranks all-gather their own rows of it:
+# 40 B x (H - tile rows) x W into each rank per step.  Per step: accumulate(1) -> exchange_history -> set_camera / reset.
+
+HISTORY_BYTES_PER_PIXEL = 40   # diffuse + specular history f32x4, g-buffer depth f32, g-buffer normal u32
+
+
+def enable_moving_camera(sess):
+    """Opt a rank's context into the history exchange; call after configure_session, before the first accumulate."""
+    sess.set_history_exchange(True)
+
+
+def exchange_history(sess, rank, world_size, device, bounds=None):
+    """All-gather every rank's own rows of the temporal state and import the other ranks' rows into this rank's context.
+    `bounds`: the ranks' row ranges (default split_rows); `device`: where the collective's buffers live ("cuda" for nccl,
+    "cpu" for gloo -- the library then exchanges through a device buffer on the context's GPU)."""
+    import torch
+    import torch.distributed as dist
+    bounds = [tuple(b) for b in bounds] if bounds is not None else split_rows(sess.H, world_size)
+    a, b = bounds[rank]
+    row_bytes = HISTORY_BYTES_PER_PIXEL * sess.W
+    rows = max(hi - lo for lo, hi in bounds)
+    coll = torch.device(device)
+    on_device = getattr(sess, "io_on_device", True)   # the HIP library reads and writes device memory only
+    io = torch.device("cuda", int(sess.cfg.device)) if on_device and coll.type == "cpu" else coll
+    # (empty: nothing on torch's stream writes a buffer before the library, whose stream is another, has filled it)
+    full = torch.empty((world_size, rows * row_bytes), dtype=torch.uint8, device=coll)
+    mine = full[rank] if io == coll else torch.empty(rows * row_bytes, dtype=torch.uint8, device=io)
+    sess.history_rows_io(a, b, mine.data_ptr(), False)
+    sess.sync()
+    if io != coll:
+        full[rank].copy_(mine)
+    if world_size > 1:
+        dist.all_gather(list(full.unbind(0)), full[rank].clone())
+    staged = full if io == coll else full.to(io)
+    if staged.is_cuda:
+        torch.cuda.current_stream(staged.device).synchronize()   # the gather / staging copy before the library reads
+    for r, (lo, hi) in enumerate(bounds):
+        if r != rank and hi > lo:
+            sess.history_rows_io(lo, hi, staged[r].data_ptr(), True)
+    sess.sync()   # (the caller's buffers are released on return)
+
+
 def rebalance_rows(bounds, costs, height, min_rows=8):
     """New contiguous row ranges with (approximately) equal cost, given the cost each rank measured on its current
     range (piecewise-constant cost density per row).  Rows are the unit; every rank keeps at least `min_rows`."""
