@@ -141,7 +141,19 @@ int vrt_sky_compute_slice(vrt_ctx* ctx, int slice_idx, int max_slices);
 int vrt_sky_accumulate_clouds_slice(vrt_ctx* ctx, int max_samples, int slice_idx, int max_slices);
 int vrt_sky_table_io(vrt_ctx* ctx, int which /* VRT_BUF_SKY_SCATTERING | VRT_BUF_SKY_TRANSMITTANCE */, int u0, int u1,
                      void* device_ptr /* f32[u1-u0][sky_res][3] */, int to_library);
-/* Renderer.accumulate (pathtracer.py:1310-1319), n_samples times */
+/* Renderer.accumulate (pathtracer.py:1310-1319), n_samples times.
+ * The call queues its render launches; the ACCUMULATION of a launch (temporal filter -> histories, HDR frame) may be queued later
+ * than the call that rendered it: with a static camera at render scale 1, ReSTIR off and no tile ring (vrt_set_hdr_targets),
+ * history exchange or row stripes, the library accumulates several consecutive launches in one pass, each with the camera and
+ * scene parameters that stood when ITS call was made -- vrt_set_camera (a new jitter), vrt_set_scene and vrt_end_frame between
+ * calls neither force nor disturb it.  The pending accumulation is queued on the context's stream, before anything else the call
+ * does, by every call that can observe or change what a pass per launch would have produced: vrt_sync, every vrt_fetch_*
+ * (blocking, device, async) and vrt_fetch_buffer, vrt_get_stats / vrt_reset_stats, vrt_reset, vrt_set_stream,
+ * vrt_set_hdr_targets, vrt_set_history_exchange / vrt_history_rows_io, vrt_set_row_stripes, vrt_upload_*, vrt_prepare,
+ * vrt_set_instrumented, vrt_set_reference_indexing, vrt_destroy, a vrt_accumulate call whose launch is of another kind (moving
+ * camera, render scale below 1, another pipeline depth) or fails.  Results are those of a pass per launch, bit for bit; a caller
+ * that orders its own work on the context's stream behind a frame (an event for another stream) calls vrt_sync or a fetch first.
+ * vrt_stats counts one accumulation pass per render launch as before. */
 int vrt_accumulate(vrt_ctx* ctx, int n_samples);
 /* Renderer.reset_framebuffer (pathtracer.py:664-668) / copy_prev_matrices (283-287) */
 int vrt_reset(vrt_ctx* ctx);
@@ -213,6 +225,7 @@ int vrt_set_row_stripes(vrt_ctx* ctx, int stripe_rows, int n_parts, int part);
 int vrt_set_history_exchange(vrt_ctx* ctx, int on);
 int vrt_history_rows_io(vrt_ctx* ctx, int row0, int row1, void* device_ptr, int to_library);
 int vrt_fetch_buffer(vrt_ctx* ctx, int which, void* out);
+/* waits for everything queued so far, the accumulation of every rendered launch included (see vrt_accumulate) */
 int vrt_sync(vrt_ctx* ctx);
 int vrt_get_stats(vrt_ctx* ctx, vrt_stats* out);
 int vrt_reset_stats(vrt_ctx* ctx);

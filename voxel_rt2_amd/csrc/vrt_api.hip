@@ -18,7 +18,11 @@
 
 #define VRT_MAX_FUSED 4   // samples of one vrt_accumulate(n) call rendered by a single launch
 #define VRT_MAX_STREAMS 8 // render launches in flight at most (a stream, a pool scratch and a camera-ray table each): 2, 4 or 8 are used
-#define VRT_MAX_SETS 9    // copies of what a render launch writes (set 0 = the canonical buffers): streams + 1 are used
+#define VRT_MAX_SETS 12   // copies of what a render launch writes (set 0 = the canonical buffers): streams + 1 are used, or streams + K
+                          // where the accumulation of K launches is deferred into one pass (flush_deferred)
+#ifndef VRT_DEFER_4DEEP
+#define VRT_DEFER_4DEEP 4 // K of the four-deep pipeline (launches of up to 12 M items).  The two-deep one (4K frames: a set is 1 GB there)
+#endif                    // and the eight-deep one (not measured with K > 1) accumulate every launch in a pass of its own
 #define VRT_GB_ROT (VRT_MAX_SETS + 1)   // rotating g-buffer normal / depth copies: copy j is read by temporal passes j and j + 1, and the
                                        // launch that writes it again only waits for the pass VRT_MAX_SETS launches back
 #define VRT_WORK_SETS 16  // rotating sets of work heads (vrt_kernels.hip: a launch zeroes the set eight launches ahead)
@@ -60,7 +64,7 @@ static struct ProfDump {
     } while (0)
 #endif
 
-struct EventPair { hipEvent_t a, b; int kind; };  // kind 0 render, 1 temporal, 2 gris
+struct EventPair { hipEvent_t a, b; int kind; unsigned weight; };  // kind 0 render, 1 temporal, 2 gris; weight: passes the kernel between them stands for
 
 // Environment switches, read ONCE when a context is created (never on the launch path).
 // The shipped library knows four: VRT_RENDER=pool|fused (which of the two schedules of the same per-path code renders),
@@ -70,7 +74,7 @@ struct EventPair { hipEvent_t a, b; int kind; };  // kind 0 render, 1 temporal, 
 // A build with -DVRT_DEV_KNOBS (build_variants/libvrt_dev.so: `python -m voxel_rt2_amd.build --variant dev -DVRT_DEV_KNOBS`,
 // loaded by tests/test_gpu_pipeline.py and the A/B runs of tools/) adds the development switches: the fault-injection hook
 // VRT_TEST_FAIL_LAUNCH and the A/B switches VRT_CULL, VRT_DENSE, VRT_DEEP_ITEMS, VRT_DEEPER_ITEMS, VRT_STREAMS, VRT_GRID_DIV,
-// VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK.
+// VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER.
 struct Knobs {
     int render = -1;               // -1: the library's choice, 0: fused, 1: pool; -2: a value VRT_RENDER does not know
     bool overlap = true;
@@ -82,6 +86,7 @@ struct Knobs {
     int streams = 0, grid_div = 0; // 0: decided from the frame size (ensure_overlap)
     bool drain_gate = true, fuse_restir = true, overlap_single = true;
     int max_fused = VRT_MAX_FUSED, full_below = 2, chunk = 0, fail_launch = -1, gate_extra = 0, time_every = 0;
+    int defer4 = VRT_DEFER_4DEEP, defer8 = 1;   // render launches whose accumulation runs as one pass, per pipeline depth (VRT_DEFER: both)
 };
 static Knobs read_knobs() {
     Knobs k;
@@ -104,6 +109,7 @@ static Knobs read_knobs() {
     if (const char* e = getenv("VRT_TIME_EVERY")) { const int v = atoi(e); if (v >= 1 && v <= 1024) k.time_every = v; }   // 0 (default): by launch size
     if (const char* e = getenv("VRT_GATE_EXTRA")) { const int v = atoi(e); if (v >= 0 && v <= 4) k.gate_extra = v; }
     if (const char* e = getenv("VRT_FULL_BELOW")) { const int v = atoi(e); if (v >= 1 && v <= 3) k.full_below = v; }
+    if (const char* e = getenv("VRT_DEFER")) { const int v = atoi(e); if (v >= 0 && v <= VRT_MAX_GROUP) k.defer4 = k.defer8 = v < 1 ? 1 : v; }   // 0, 1: a pass per launch
     if (const char* e = getenv("VRT_CHUNK")) { const int v = atoi(e); if (v >= 64 && v <= 4096) k.chunk = v / 64 * 64; }
 #endif
     return k;
@@ -196,6 +202,14 @@ struct vrt_ctx {
     hipStream_t rstream[VRT_MAX_STREAMS] = {};
     hipEvent_t ev_r[VRT_MAX_SETS] = {}, ev_t[VRT_MAX_SETS] = {}, ev_main = nullptr;
     bool ev_t_valid[VRT_MAX_SETS] = {};
+    int ev_t_of[VRT_MAX_SETS] = {};   // the set whose ev_t stands for the pass that last read this one (a grouped pass records one event)
+    // Deferred accumulation: with a static camera the passes of K consecutive overlapped launches run as ONE kernel
+    // (k_temporal_group) once the K-th is queued, or earlier when somebody is about to look (flush_deferred).  A launch's
+    // planes stay occupied until then: n_sets = n_streams + K copies.
+    struct Deferred { TemporalSlice slice; int set; bool timed; };
+    std::vector<Deferred> deferred;
+    int n_sets = 3;      // copies in use (ensure_overlap)
+    int defer_k = 1;     // K of the pipeline mode in use (1: every launch has a pass of its own)
     bool overlap_ready = false, overlap_failed = false;
     // Device time per kind of pass (0 render, 1 accumulation, 2 spatial reuse): every pass is counted, the ones that carry timers
     // are summed (small launches: one in eight, accumulate_impl) and vrt_get_stats scales the sum to all of them.
@@ -248,6 +262,10 @@ static hipError_t dalloc(T** p, size_t n) {
     return e;
 }
 
+// Queues the accumulation of every render launch whose pass was deferred (below, after accumulate's helpers).  Everything that
+// observes or changes what a pass per launch would have produced calls it first.
+static int flush_deferred(vrt_ctx* c, bool split_tail = true);
+
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // Host store to the gate word: every launch queued so far counts as draining.  launch_seq is at least what any launch in
@@ -261,6 +279,7 @@ static void release_gate(vrt_ctx* c) {
 // hipStreamSynchronize with a bound on how long a gated launch may hold the stream: past it the gate is released from
 // the host (harmless when the launches are merely long; the way out when a dispatch never comes).
 static hipError_t sync_guarded(vrt_ctx* c, hipStream_t st) {
+    if (st == c->stream && flush_deferred(c) != VRT_OK) return hipErrorUnknown;   // (the passes the caller is about to wait for)
     if (c->drain_signal && c->drain_signalled) {
         const double limit = c->knobs.gate_watchdog_s;
         const double t0 = now_s();
@@ -301,7 +320,7 @@ static bool gate_self_test(vrt_ctx* c) {
 
 static void account(vrt_ctx* c, const EventPair& ev) {
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) { c->timed_ms[ev.kind] += ms; c->timed_n[ev.kind]++; }
+    if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) { c->timed_ms[ev.kind] += ms; c->timed_n[ev.kind] += ev.weight; }
     hipEventDestroy(ev.a);
     hipEventDestroy(ev.b);
 }
@@ -511,6 +530,7 @@ void vrt_destroy(vrt_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     release_gate(c);   // nothing may be left waiting at a gate
+    if (c->stream && flush_deferred(c, false) != VRT_OK) { (void)hipGetLastError(); c->deferred.clear(); }
     if (c->fetch_stream) hipStreamSynchronize(c->fetch_stream);
     for (int s = 0; s < VRT_MAX_STREAMS; s++) if (c->rstream[s]) hipStreamSynchronize(c->rstream[s]);
     if (c->stream) hipStreamSynchronize(c->stream);
@@ -555,6 +575,7 @@ void vrt_destroy(vrt_ctx* c) {
 int vrt_upload_voxels(vrt_ctx* c, const int8_t* mat, const uint8_t* rgb) {
     if (!c || !mat || !rgb) return fail(VRT_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     const size_t nvox = (size_t)c->cfg.grid_res * c->cfg.grid_res * c->cfg.grid_res;
     HIP_TRY(hipMemcpyAsync(c->d_mat, mat, nvox, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_rgb, rgb, nvox * 3, hipMemcpyHostToDevice, c->stream));
@@ -566,6 +587,7 @@ int vrt_upload_voxels(vrt_ctx* c, const int8_t* mat, const uint8_t* rgb) {
 int vrt_upload_materials(vrt_ctx* c, const float* table) {
     if (!c || !table) return fail(VRT_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     c->main_dirty = true;
     HIP_TRY(hipMemcpyAsync(c->d_mats, table, 128 * 14 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(launch_mat_derived(c->stream, c->d_mats, c->d_mats_x));
@@ -576,6 +598,7 @@ int vrt_upload_cloud_texture(vrt_ctx* c, const uint8_t* rgb) {
     if (!c || !rgb) return fail(VRT_E_INVALID, "null argument");
     if (c->cfg.sky_res <= 0) return fail(VRT_E_STATE, "context was created without sky tables (sky_res = 0)");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     c->main_dirty = true;
     HIP_TRY(hipMemcpyAsync(c->d_cloud_tex, rgb, 256 * 256 * 3, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(sync_guarded(c, c->stream));
@@ -607,6 +630,8 @@ int vrt_reserve_cus(vrt_ctx* c, int n_cus) {
 }
 int vrt_set_row_stripes(vrt_ctx* c, int stripe_rows, int n_parts, int part) {
     if (!c) return fail(VRT_E_INVALID, "null context");
+    HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     if (stripe_rows == 0) { c->stripe_rows = c->stripe_parts = c->stripe_part = 0; return VRT_OK; }
     if (stripe_rows < 8 || stripe_rows % 8 != 0 || n_parts < 1 || part < 0 || part >= n_parts) return fail(VRT_E_INVALID, "stripe_rows must be a multiple of 8, 0 <= part < n_parts");
     if (c->own0 != 0 || c->own1 != c->cfg.height) return fail(VRT_E_INVALID, "row stripes are a property of a whole-frame context (row_begin = row_end = 0)");
@@ -636,6 +661,7 @@ int vrt_set_history_exchange(vrt_ctx* c, int on) {
     if (!on && c->have_cam && c->cam.camera_is_moving && is_row_tile(c))
         return fail(VRT_E_INVALID, "the moving camera on a row tile needs the history exchange: set a static camera first");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     c->hx_on = on != 0;
     if (!c->hx_on || !is_row_tile(c)) { free_history_planes(c); return VRT_OK; }   // a whole-frame context has nothing to import
     if (c->d_hx_hist_d) return VRT_OK;
@@ -663,6 +689,7 @@ int vrt_history_rows_io(vrt_ctx* c, int row0, int row1, void* device_ptr, int to
     if (to_library && row0 < c->own1 && row1 > c->own0) return fail(VRT_E_INVALID, "import: rows must lie outside the context's own rows");
     if (to_library && !c->d_hx_hist_d) return fail(VRT_E_STATE, "import needs vrt_set_history_exchange on a row tile");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     const size_t W = c->cfg.width, rows = (size_t)(row1 - row0);
     char* rec = (char*)device_ptr;
     char* const planes[4] = {rec, rec + rows * W * 16, rec + rows * W * 32, rec + rows * W * 36};
@@ -693,6 +720,7 @@ static int store_history_rows(vrt_ctx* c) {
 int vrt_set_instrumented(vrt_ctx* c, int on) {
     if (!c) return fail(VRT_E_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     c->instrumented = on != 0;
     c->count_as_timed = on == 2;
     c->render_blocks = 0;
@@ -702,6 +730,7 @@ int vrt_set_instrumented(vrt_ctx* c, int on) {
 int vrt_set_reference_indexing(vrt_ctx* c, int on) {
     if (!c) return fail(VRT_E_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     c->ref_oob = on != 0;
     c->render_blocks = 0;   // other kernel instantiations (the instrumented ones carry the code): the grid is sized again
     return VRT_OK;
@@ -710,6 +739,7 @@ int vrt_set_reference_indexing(vrt_ctx* c, int on) {
 int vrt_prepare(vrt_ctx* c) {
     if (!c) return fail(VRT_E_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     c->main_dirty = true;
     HIP_TRY(launch_prepare(c->stream, c->cfg.grid_res, c->d_mat, c->d_rgb, c->d_grid, c->d_l0, c->d_l1, c->d_l2, c->d_l3, c->d_l0c, c->d_l0c_base, c->d_cull));
     {
@@ -798,10 +828,10 @@ int vrt_sky_compute_slice(vrt_ctx* c, int slice_idx, int max_slices) {
     return VRT_OK;
 }
 
-static int record(vrt_ctx* c, int kind, hipEvent_t* a, hipEvent_t* b) {
+static int record(vrt_ctx* c, int kind, hipEvent_t* a, hipEvent_t* b, unsigned weight = 1u) {
     HIP_TRY(hipEventCreate(a));
     HIP_TRY(hipEventCreate(b));
-    c->pending.push_back(EventPair{*a, *b, kind});
+    c->pending.push_back(EventPair{*a, *b, kind, weight});
     return VRT_OK;
 }
 
@@ -831,19 +861,22 @@ static void pipeline_mode_for(const vrt_ctx* c, int g, bool heavy, int* n_stream
     if (c->knobs.grid_div) *grid_div = c->knobs.grid_div;
 }
 // Streams, copies and events for a pipeline `want` launches deep (what a shallower one already has is kept).
-static bool grow_pipeline(vrt_ctx* c, int want) {
+static bool grow_pipeline(vrt_ctx* c, int want, int want_sets) {
     const size_t n = c->npix;
     bool ok = true;
-    for (int s = 0; s < want && ok; s++) {   // stream s, copy s + 1 (alt_*[s]) and, beyond the first, a pool scratch of its own
-        if (c->rstream[s]) continue;
+    for (int s = 0; s < want_sets - 1 && ok; s++) {   // copy s + 1 (alt_*[s])
+        if (c->alt_gb_mat[s]) continue;
         ok = dalloc(&c->alt_multi_d[s], n * VRT_MAX_FUSED) == hipSuccess && dalloc(&c->alt_spec_planes[s], n * VRT_MAX_FUSED) == hipSuccess &&
-             dalloc(&c->alt_refl_planes[s], n * VRT_MAX_FUSED) == hipSuccess && dalloc(&c->alt_gb_pos[s], n) == hipSuccess &&
-             dalloc(&c->alt_gb_mat[s], n) == hipSuccess;
-        if (ok && s > 0)
+             dalloc(&c->alt_refl_planes[s], n * VRT_MAX_FUSED) == hipSuccess && dalloc(&c->alt_gb_pos[s], n) == hipSuccess;
+        ok = ok && dalloc(&c->alt_gb_mat[s], n) == hipSuccess;   // (last: a copy that has it has everything)
+    }
+    for (int s = 0; s < want && ok; s++) {   // stream s and, beyond the first, a pool scratch of its own
+        if (c->rstream[s]) continue;
+        if (s > 0)
             ok = hipMalloc((void**)&c->alt_pool_scratch[s - 1], pool_scratch_bytes(c->cfg.grid_res, c->cfg.use_restir != 0, c->render_blocks, c->render_blocks_d12)) == hipSuccess;
         ok = ok && hipStreamCreateWithFlags(&c->rstream[s], hipStreamNonBlocking) == hipSuccess;   // (last: a stream that exists has everything)
     }
-    for (int s = 0; s < want + 1 && ok; s++)
+    for (int s = 0; s < want_sets && ok; s++)
         if (!c->ev_r[s])
             ok = hipEventCreateWithFlags(&c->ev_r[s], hipEventDisableTiming) == hipSuccess &&
                  hipEventCreateWithFlags(&c->ev_t[s], hipEventDisableTiming) == hipSuccess;
@@ -853,26 +886,38 @@ static bool grow_pipeline(vrt_ctx* c, int want) {
 // The pipeline for a launch of g samples; false (and never tried again) if its streams and copies cannot be had.  The depth
 // follows the launch: a context whose caller changes habit (one sample per call, then four) is drained once and goes on in
 // the other mode -- the set numbering and the gate distance of the two modes do not mix.
+// Whether this context's overlapped launches may have their accumulation deferred: not with a tile ring (a call must queue its own
+// tile), a history exchange or row stripes.  (Overlapped launches are static-camera, render scale 1, ReSTIR off already.)
+static bool can_defer(const vrt_ctx* c) { return c->hdr_targets.empty() && !c->hx_on && c->stripe_rows == 0; }
 static bool ensure_overlap(vrt_ctx* c, int g, bool heavy) {
     if (c->overlap_failed) return false;
     int ns = 0, gd = 0;
     pipeline_mode_for(c, g, heavy, &ns, &gd);
+    // K of the mode: contexts whose launches are never deferred (can_defer) do not pay for the copies
+    int k = !can_defer(c) ? 1 : ns == 4 ? c->knobs.defer4 : ns == 8 ? c->knobs.defer8 : 1;
+    if (k > VRT_MAX_SETS - ns) k = VRT_MAX_SETS - ns;
+    if (k < 1) k = 1;
     if (c->overlap_ready) {
         if (ns == c->n_streams && gd == c->grid_div) return true;
-        if (!grow_pipeline(c, ns)) return true;   // no memory for the other mode: this one goes on
-        if (sync_guarded(c, c->stream) != VRT_OK) return true;
+        if (!grow_pipeline(c, ns, ns + k)) return true;   // no memory for the other mode: this one goes on
+        if (sync_guarded(c, c->stream) != VRT_OK) return true;   // (with the deferred passes of the mode that ends)
         for (int s = 0; s < VRT_MAX_STREAMS; s++) if (c->rstream[s]) (void)hipStreamSynchronize(c->rstream[s]);
         if (sync_guarded(c, c->stream) != VRT_OK) return true;   // (the temporal passes behind those launches)
         (void)hipGetLastError();
         for (int s = 0; s < VRT_MAX_SETS; s++) c->ev_t_valid[s] = false;   // every pass has completed
         c->n_streams = ns;
         c->grid_div = gd;
+        c->n_sets = ns + k;
+        c->defer_k = k;
         c->mode_switches++;
         return true;
     }
-    bool ok = grow_pipeline(c, ns);
+    bool ok = grow_pipeline(c, ns, ns + k);
+    if (!ok && k > 1) { k = 1; ok = grow_pipeline(c, ns, ns + 1); }   // no memory for the deferred launches' copies: a pass per launch
     c->n_streams = ns;
     c->grid_div = gd;
+    c->n_sets = ns + k;
+    c->defer_k = k;
     ok = ok && hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming) == hipSuccess;
     int can_wait = 0;
     bool want_gate = ok;
@@ -901,6 +946,8 @@ static void abort_pipeline(vrt_ctx* c) {
     const std::string keep = g_err;
     release_gate(c);
     c->drain_signalled = false;
+    // the launches that WERE queued are accumulated all the same (the failed one has left no slice behind)
+    if (flush_deferred(c, false) != VRT_OK) { (void)hipGetLastError(); c->deferred.clear(); }
     for (int s = 0; s < VRT_MAX_STREAMS; s++) if (c->rstream[s]) (void)hipStreamSynchronize(c->rstream[s]);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->fetch_stream) (void)hipStreamSynchronize(c->fetch_stream);   // asynchronous fetches queued before the failure have completed
@@ -928,6 +975,61 @@ static f3* next_hdr_target(vrt_ctx* c) {
 static int wait_cbuf_readers(vrt_ctx* c, int b) {   // an asynchronous fetch may still be reading the HDR buffer a pass is about to write
     if (c->cbuf_read_pending[b]) { HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_cbuf_read[b], 0)); c->cbuf_read_pending[b] = false; }
     return VRT_OK;
+}
+
+// One k_temporal_group over deferred[first, first + n): behind those launches, histories and HDR roles swapped ONCE.
+static int queue_group(vrt_ctx* c, size_t first, size_t n) {
+    TemporalGroup tg;
+    memset(&tg, 0, sizeof(tg));
+    tg.W = c->cfg.width; tg.H = c->cfg.height; tg.row0 = c->buf0; tg.row1 = c->buf1;
+    tg.inv_res = mk2((float)(1.0 / (double)tg.W), (float)(1.0 / (double)tg.H));   // (make_frame_params)
+    tg.n_slices = (int)n;
+    bool timed = false;
+    for (size_t i = 0; i < n; i++) {
+        const vrt_ctx::Deferred& d = c->deferred[first + i];
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_r[d.set], 0));
+        tg.slice[i] = d.slice;
+        timed = timed || d.timed;
+    }
+    tg.hist_d_in = c->d_hist_d[c->hist_in]; tg.hist_d_out = c->d_hist_d[c->hist_in ^ 1];
+    tg.hist_s_in = c->d_hist_s[c->hist_in]; tg.hist_s_out = c->d_hist_s[c->hist_in ^ 1];
+    tg.hdr = c->d_cbuf[c->cidx ^ 1];
+    tg.gb_refl_filtered = c->d_gb_refl_f;
+    if (wait_cbuf_readers(c, c->cidx ^ 1) != VRT_OK) return VRT_E_DEVICE;
+    hipEvent_t a = nullptr, b = nullptr;
+    if (timed) {   // a group with a timed launch in it carries the timers, and counts for all of its passes
+        if (record(c, 1, &a, &b, (unsigned)n) != VRT_OK) return VRT_E_DEVICE;
+        HIP_TRY(hipEventRecord(a, c->stream));
+    }
+    HIP_TRY(launch_temporal_group(c->stream, tg, c->own0, c->own1));
+    if (timed) HIP_TRY(hipEventRecord(b, c->stream));
+    const int last_set = c->deferred[first + n - 1].set;   // one event for the group: every copy it read is free behind it
+    HIP_TRY(hipEventRecord(c->ev_t[last_set], c->stream));
+    for (size_t i = 0; i < n; i++) { const int st = c->deferred[first + i].set; c->ev_t_valid[st] = true; c->ev_t_of[st] = last_set; }
+    c->passes_n[1] += (uint32_t)n;   // accumulation passes in the reference's sense: one per render launch
+    c->hist_in ^= 1;
+    c->cidx ^= 1;
+    return VRT_OK;
+}
+// split_tail: while the newest launch is still running the older ones' pass is queued by itself, to run beside that launch --
+// otherwise the tail behind the last launch of a run grows from one launch's accumulation to all the pending ones'.
+static int flush_deferred(vrt_ctx* c, bool split_tail) {
+    const size_t m = c->deferred.size();
+    if (m == 0) return VRT_OK;
+    int rc = VRT_OK;
+    bool split = false;
+    if (split_tail && m > 1) {
+        split = hipEventQuery(c->ev_r[c->deferred.back().set]) == hipErrorNotReady;
+        (void)hipGetLastError();
+    }
+    if (split) {
+        rc = queue_group(c, 0, m - 1);
+        if (rc == VRT_OK) rc = queue_group(c, m - 1, 1);
+    } else {
+        rc = queue_group(c, 0, m);
+    }
+    c->deferred.clear();   // (after a failure too: the caller's abort_pipeline drains what was queued)
+    return rc;
 }
 
 static int accumulate_impl(vrt_ctx* c, int n_samples);
@@ -965,6 +1067,7 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
     // (the instrumented instantiations are the ones that carry the reference's out-of-grid reading: vrt_set_reference_indexing)
     const bool restir = c->cfg.use_restir != 0, instr = c->instrumented || c->ref_oob;
     if (c->render_blocks == 0) {
+        if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;   // (the scratch below is freed behind the context's stream)
         // Two schedules of the same per-path code: the fused one (a lane owns a path, vrt_path.h) and the pooled one
         // (a wave owns a pool of paths in LDS and works stage by stage, vrt_pool.h).  The pooled kernel packs pixel
         // coordinates in 12 bits and the depth in 4, so contexts outside that use the fused one (ReSTIR runs on either:
@@ -1030,7 +1133,11 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
         const bool heavy = c->pooled && c->render_blocks_d12 > 0 && pool_uses_dense12(c->cfg.grid_res, restir, c->dense_grid, make_frame_params(c));
         const bool overlapped = want_overlap && ensure_overlap(c, g, heavy);
         const bool planes = g > 1 || overlapped;   // the launch writes colour planes of its own, not the HDR buffer
-        const int set = overlapped ? (int)(c->pipe_seq % (unsigned)(c->n_streams + 1)) : 0;
+        // Its accumulation is deferred to a pass over defer_k launches (flush_deferred); a launch that is not deferred comes
+        // behind the passes of those that were.
+        const bool defer = overlapped && c->defer_k > 1 && can_defer(c);
+        if (!defer && flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
+        const int set = overlapped ? (int)(c->pipe_seq % (unsigned)c->n_sets) : 0;
         const int lane_of = (int)(c->pipe_seq % (unsigned)c->n_streams);  // which render stream (and pool scratch): consecutive launches take turns
         hipStream_t rs = overlapped ? c->rstream[lane_of] : c->stream;
         // A launch of half the slots only pays with other launches beside it: one that finds the pipeline empty (the caller
@@ -1041,7 +1148,7 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
         bool lone = !overlapped;
         if (overlapped && c->grid_div > 1) {
             int running = 0;
-            const unsigned n_sets = (unsigned)c->n_streams + 1u;
+            const unsigned n_sets = (unsigned)c->n_sets;
             for (unsigned back = 1; back <= 3u && back <= c->pipe_seq; back++)
                 if (hipEventQuery(c->ev_r[(c->pipe_seq - back) % n_sets]) == hipErrorNotReady) running++;
             (void)hipGetLastError();   // (hipErrorNotReady is the expected answer)
@@ -1053,7 +1160,7 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
                 for (int s = 0; s < c->n_streams; s++) HIP_TRY(hipStreamWaitEvent(c->rstream[s], c->ev_main, 0));
                 c->main_dirty = false;
             }
-            if (c->ev_t_valid[set]) HIP_TRY(hipStreamWaitEvent(rs, c->ev_t[set], 0));  // the pass that last read this copy
+            if (c->ev_t_valid[set]) HIP_TRY(hipStreamWaitEvent(rs, c->ev_t[c->ev_t_of[set]], 0));  // the pass that last read this copy
             // dispatch when the launch whose workgroup slots this one will take starts to drain: the one before it, or with
             // launches of half the slots the one before that (the signal carries the number + 1 of the latest launch draining)
             // -- unless the one before it took EVERY slot (a lone launch): then that one has to drain first
@@ -1132,11 +1239,21 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
         if (timed) HIP_TRY(hipEventRecord(b, rs));
         if (overlapped) {
             HIP_TRY(hipEventRecord(c->ev_r[set], rs));
-            HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_r[set], 0));
+            if (!defer) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_r[set], 0));
             c->last_render_set = set;
         }
+        if (defer) {   // what this launch's own pass would have been given, as it stands now (camera, scene, planes)
+            vrt_ctx::Deferred d;
+            d.slice.view_inv = fp.view_inv; d.slice.proj_inv = fp.proj_inv;
+            d.slice.color_d = out.color_d; d.slice.color_s = out.color_s;
+            d.slice.gb_depth = out.gb_depth; d.slice.gb_refl_raw = out.gb_refl_depth;
+            d.slice.max_accum_frames = fp.max_accum_frames;
+            d.slice.n_samples = g; d.slice.sample_stride = out.sample_stride;
+            d.set = set; d.timed = timed;
+            c->deferred.push_back(d);
+        }
         // ReSTIR: spatial reuse and accumulation sample by sample over the planes of the launch (one pass with one sample)
-        const int passes = restir ? g : 1;
+        const int passes = defer ? 0 : restir ? g : 1;
         int hist = c->hist_in, ci = c->cidx;   // (the context's own copies only move once every launch of the iteration is queued)
         for (int s = 0; s < passes; s++) {
             const size_t off = (size_t)s * (size_t)out.sample_stride;   // this sample's plane (ReSTIR; stride 0 with one sample)
@@ -1197,12 +1314,14 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
             c->passes_n[1]++;
             hist ^= 1; ci ^= 1;   // pathtracer.py:1298-1303 copy loop == pointer swaps, once per accumulation pass
         }
-        if (overlapped) {
+        if (defer) {
+            c->pipe_seq += 1;
+        } else if (overlapped) {
             HIP_TRY(hipEventRecord(c->ev_t[set], c->stream));
-            c->ev_t_valid[set] = true;
+            c->ev_t_valid[set] = true; c->ev_t_of[set] = set;
             c->pipe_seq += 1;
         } else if (c->overlap_ready) {  // this pass used copy 0 and the single-copy buffers: later overlapped launches wait for it
-            for (int s = 0; s < c->n_streams + 1; s++) { HIP_TRY(hipEventRecord(c->ev_t[s], c->stream)); c->ev_t_valid[s] = true; }
+            for (int s = 0; s < c->n_sets; s++) { HIP_TRY(hipEventRecord(c->ev_t[s], c->stream)); c->ev_t_valid[s] = true; c->ev_t_of[s] = s; }
         }
         c->last_set = set;
         c->hist_in = hist;
@@ -1213,6 +1332,8 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
         c->frame += (uint32_t)g;
         c->stats.path_samples += (uint64_t)g * (uint64_t)c->cfg.width * (uint64_t)owned_rows(c);
         done += g;
+        // (the K-th launch's pass is queued with it, like a pass of its own would be: no split)
+        if ((int)c->deferred.size() >= c->defer_k && flush_deferred(c, false) != VRT_OK) return VRT_E_DEVICE;
     }
     return VRT_OK;
 }
@@ -1220,6 +1341,7 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
 int vrt_reset(vrt_ctx* c) {
     if (!c) return fail(VRT_E_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     for (int s = 0; s < 2; s++) {
         HIP_TRY(hipMemsetAsync(c->d_hist_d[s], 0, c->npix * sizeof(f4), c->stream));
         HIP_TRY(hipMemsetAsync(c->d_hist_s[s], 0, c->npix * sizeof(f4), c->stream));
@@ -1241,6 +1363,7 @@ int vrt_end_frame(vrt_ctx* c) {
 int vrt_sync(vrt_ctx* c) {
     if (!c) return fail(VRT_E_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     HIP_TRY(sync_guarded(c, c->stream));  // every render launch on the render streams has its temporal pass here
     return VRT_OK;
 }
@@ -1261,11 +1384,13 @@ static int fetch_rows(vrt_ctx* c, const void* dbuf, size_t elem, void* out) {
 int vrt_fetch_hdr(vrt_ctx* c, float* out) {
     if (!c || !out) return fail(VRT_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     return fetch_rows(c, c->d_cbuf[c->cidx], sizeof(f3), out);
 }
 int vrt_fetch_hdr_device(vrt_ctx* c, void* device_ptr) {
     if (!c || !device_ptr) return fail(VRT_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     const size_t W = c->cfg.width;
     size_t done = 0;   // (a striped context's rows: one stripe after the other)
     for (const auto& rr : owned_ranges(c)) {
@@ -1279,6 +1404,7 @@ int vrt_fetch_hdr_device(vrt_ctx* c, void* device_ptr) {
 int vrt_fetch_hdr_device_async(vrt_ctx* c, void* device_ptr) {
     if (!c || !device_ptr) return fail(VRT_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     const size_t W = c->cfg.width;
     size_t done = 0;   // (a striped context's rows: one stripe after the other)
     for (const auto& rr : owned_ranges(c)) {
@@ -1291,6 +1417,7 @@ int vrt_fetch_hdr_device_async(vrt_ctx* c, void* device_ptr) {
 int vrt_set_stream(vrt_ctx* c, void* hip_stream) {
     if (!c) return fail(VRT_E_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     HIP_TRY(sync_guarded(c, c->stream));
     resolve_events(c);
     for (int s = 0; s < VRT_MAX_SETS; s++) c->ev_t_valid[s] = false;  // everything recorded on the old stream has completed
@@ -1304,6 +1431,7 @@ int vrt_fetch_ldr(vrt_ctx* c, float* out) {
     if (!c || !out) return fail(VRT_E_INVALID, "null argument");
     if (!c->have_cam) return fail(VRT_E_STATE, "vrt_set_camera has not been called");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     if (c->ev_fetch_src) {   // asynchronous fetches share d_ldr: theirs first
         HIP_TRY(hipEventRecord(c->ev_fetch_src, c->fetch_stream));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_fetch_src, 0));
@@ -1335,6 +1463,7 @@ static int fetch_async(vrt_ctx* c, void* out, int slot, int what /* 0 HDR, 1 LDR
     if (c->fetch_valid[slot]) return fail(VRT_E_STATE, "this slot's previous fetch has not been collected (vrt_fetch_wait)");
     if (c->stripe_rows) return fail(VRT_E_STATE, "asynchronous fetches are not available on a context with row stripes");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     if (what == 2 && !c->d_ldr8 && dalloc(&c->d_ldr8, c->npix) != hipSuccess) { c->d_ldr8 = nullptr; return fail(VRT_E_DEVICE, "no memory for the 8-bit image"); }
     if (ensure_fetch_stream(c) != VRT_OK) return VRT_E_DEVICE;
     const size_t W = c->cfg.width, rows = (size_t)(c->own1 - c->own0), off = (size_t)(c->own0 - c->buf0) * W;
@@ -1400,6 +1529,7 @@ int vrt_host_free(vrt_ctx* c, void* p) {
 int vrt_set_hdr_targets(vrt_ctx* c, void* const* device_ptrs, int n) {
     if (!c || n < 0 || (n > 0 && !device_ptrs)) return fail(VRT_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     c->hdr_targets.assign(device_ptrs, device_ptrs + n);
     c->hdr_targets_written = c->hdr_targets_committed = 0;
     return VRT_OK;
@@ -1412,6 +1542,7 @@ int vrt_hdr_targets_written(vrt_ctx* c, uint64_t* count) {
 int vrt_fetch_buffer(vrt_ctx* c, int which, void* out) {
     if (!c || !out) return fail(VRT_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     // the g-buffer written by the most recent accumulate (whichever schedule rendered it)
     const f3* pos = c->last_set ? c->alt_gb_pos[c->last_set - 1] : c->d_gb_pos;
     const uint32_t* gmat = c->last_set ? c->alt_gb_mat[c->last_set - 1] : c->d_gb_mat;
@@ -1444,6 +1575,7 @@ int vrt_fetch_buffer(vrt_ctx* c, int which, void* out) {
 int vrt_get_stats(vrt_ctx* c, vrt_stats* out) {
     if (!c || !out) return fail(VRT_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     HIP_TRY(sync_guarded(c, c->stream));
     resolve_events(c);
     Counters h;
@@ -1464,6 +1596,7 @@ int vrt_get_stats(vrt_ctx* c, vrt_stats* out) {
 int vrt_reset_stats(vrt_ctx* c) {
     if (!c) return fail(VRT_E_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
+    if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
     HIP_TRY(sync_guarded(c, c->stream));
     resolve_events(c);
     HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(Counters), c->stream));   // on the stream the counting launches follow on

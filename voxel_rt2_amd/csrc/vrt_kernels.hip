@@ -12,6 +12,7 @@
 //   k_temporal                                            fused temporal accumulation -> HDR (sized to run beside
 //                                                         the next render launch, see vrt_api.hip)
 //   k_temporal_frame_prev                                 the same, moving camera on a row tile with history exchange
+//   k_temporal_group                                      the passes of several consecutive launches in one (static camera)
 //   k_tonemap                                             LDR presentation
 //
 // k_render is a persistent-thread kernel: the grid is sized to the device's residency, each wave
@@ -892,6 +893,14 @@ __global__ __launch_bounds__(64 * VRT_TEMPORAL_ROWS) __attribute__((amdgpu_num_v
     const int v = r0 + blockIdx.y * VRT_TEMPORAL_ROWS + (threadIdx.x >> 6);
     if (u < fp.W && v < r1) temporal_pixel<false, true>(fp, tb, u, v, n_samples);
 }
+// the passes of up to VRT_MAX_GROUP consecutive render launches as one (static camera at render scale 1; the slices are kernel
+// arguments: nothing is copied to the device for them).  Same register budget and workgroup shape as k_temporal: it runs in the
+// same place, beside two render waves.
+__global__ __launch_bounds__(64 * VRT_TEMPORAL_ROWS) __attribute__((amdgpu_num_vgpr(VRT_TEMPORAL_HALF_VGPRS))) void k_temporal_group(TemporalGroup tg, int r0, int r1) {
+    const int u = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int v = r0 + blockIdx.y * VRT_TEMPORAL_ROWS + (threadIdx.x >> 6);
+    if (u < tg.W && v < r1) temporal_group_pixel(tg, u, v);
+}
 __global__ __launch_bounds__(256) void k_tonemap(FrameParams fp, const f3* hdr, f4* ldr, int r0, int r1) {
     const int u = blockIdx.x * 64 + (threadIdx.x & 63);
     const int v = r0 + blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -1078,6 +1087,13 @@ hipError_t launch_temporal(hipStream_t st, const FrameParams& fp, const Temporal
     if (frame_prev) hipLaunchKernelGGL(k_temporal_frame_prev, g, b, 0, st, fp, tb, r0, r1, n_samples);
     else if (fp.stripe_period) hipLaunchKernelGGL(k_temporal_stripes, g, b, 0, st, fp, tb, r1 - r0, n_samples);   // (r0 = 0, r1 = the context's own rows)
     else hipLaunchKernelGGL(k_temporal, g, b, 0, st, fp, tb, r0, r1, n_samples);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_temporal_group(hipStream_t st, const TemporalGroup& tg, int r0, int r1) {
+    if (tg.n_slices < 1 || tg.n_slices > VRT_MAX_GROUP || r0 < tg.row0 || r1 > tg.row1) return hipErrorInvalidValue;
+    dim3 g((tg.W + 63) / 64, (r1 - r0 + VRT_TEMPORAL_ROWS - 1) / VRT_TEMPORAL_ROWS), b(64 * VRT_TEMPORAL_ROWS);
+    hipLaunchKernelGGL(k_temporal_group, g, b, 0, st, tg, r0, r1);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

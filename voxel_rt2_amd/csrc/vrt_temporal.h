@@ -243,6 +243,85 @@ VRT_DEV void temporal_pixel(const FrameParams& fp, const TemporalBuffers& tb, in
     store_hdr<STRIPED>(fp, tb, idx, u, v, col + mk3(hs.x, hs.y, hs.z));
 }
 
+// ---- the accumulation of several render launches in one pass ---------------------------------------------------------------------
+// With a static camera at render scale 1 a pixel's pass reads nothing another pixel's pass wrote, so the passes of consecutive
+// launches can run as ONE per-pixel loop: the histories are read once, advanced launch by launch in registers, and written once
+// with the last HDR value and the last launch's filtered reflection depth (the only one anybody can observe).  A slice is what
+// one launch's own pass would have been given, captured when the launch was queued (vrt_api.hip: deferred accumulation).
+#define VRT_MAX_GROUP 8
+struct TemporalSlice {
+    mat4 view_inv, proj_inv;      // of the launch's FrameParams
+    const f3* color_d;            // the launch's colour planes (n_samples of them, sample_stride apart)
+    const f3* color_s;
+    const float* gb_depth;
+    const float* gb_refl_raw;
+    float max_accum_frames;
+    int n_samples;
+    int sample_stride;
+};
+struct TemporalGroup {
+    int W, H, row0, row1;         // as FrameParams: the same for every slice of a context
+    f2 inv_res;
+    int n_slices;
+    const f4* hist_d_in;
+    f4* hist_d_out;
+    const f4* hist_s_in;
+    f4* hist_s_out;
+    f3* hdr;
+    float* gb_refl_filtered;
+    TemporalSlice slice[VRT_MAX_GROUP];
+};
+// One pixel through every slice in launch order: what temporal_pixel does n_slices times with the histories swapped between,
+// expression for expression (static camera, render scale 1: the moving-camera code is not instantiated here).
+VRT_DEV void temporal_group_pixel(const TemporalGroup& tg, int u, int v) {
+    FrameParams fp;
+    fp.W = tg.W; fp.H = tg.H; fp.row0 = tg.row0; fp.row1 = tg.row1;
+    fp.inv_res = tg.inv_res;
+    fp.render_scale = 1.0f;
+    const int idx = (v - fp.row0) * fp.W + u;
+    const f2 tc = pixel_texcoord(fp, (float)u, (float)v);
+    f4 hd = tg.hist_d_in[idx], hs = tg.hist_s_in[idx];
+    f3 hdr = mk3(0.0f);
+    for (int s = 0; s < tg.n_slices; s++) {
+        const TemporalSlice& sl = tg.slice[s];
+        const float nl_depth = sl.gb_depth[idx];
+        const f3 x1 = xform(sl.view_inv, screen_to_view(tc, nl_depth, sl.proj_inv), 1.0f);
+        if (near_zero3(x1)) {   // this launch's pass is skipped: the histories persist, the colour is its scrubbed last diffuse sample
+            hdr = scrub(sl.color_d[(sl.n_samples - 1) * sl.sample_stride + idx]);
+            continue;
+        }
+        fp.max_accum_frames = sl.max_accum_frames;
+        for (int k = 0; k < sl.n_samples; k++) {
+            f3 cur_d, cur_s;
+            bilinear_color2(fp, sl.color_d + k * sl.sample_stride, sl.color_s + k * sl.sample_stride, tc, cur_d, cur_s);
+            blend_history(fp, 1.0f, hd, cur_d);
+            blend_history(fp, 1.0f, hs, cur_s);
+        }
+        hdr = mk3(hd.x, hd.y, hd.z) + mk3(hs.x, hs.y, hs.z);
+    }
+    // prepass of the LAST slice's last plane (temporal_pixel: the 16 taps fetched before any is looked at)
+    const TemporalSlice& ls = tg.slice[tg.n_slices - 1];
+    const int last = (ls.n_samples - 1) * ls.sample_stride;
+    float rsum = 0.0f, rcount = 0.0f;
+    {
+        float rd[16];
+        bool in[16];
+#pragma unroll
+        for (int t = 0; t < 16; t++) {
+            const int tx = u + (t >> 2) - 1, ty = v + (t & 3) - 1;
+            in[t] = !(tx < 0 || ty < 0 || tx > fp.W - 1 || ty > fp.H - 1) && !(ty < fp.row0 || ty >= fp.row1);
+            rd[t] = ls.gb_refl_raw[last + (in[t] ? (ty - fp.row0) * fp.W + tx : idx)];
+        }
+#pragma unroll
+        for (int t = 0; t < 16; t++)
+            if (in[t] && rd[t] != 0.0f) { rcount += 1.0f; rsum += rd[t]; }
+    }
+    tg.gb_refl_filtered[idx] = (rcount > 0.01f) ? rsum / rcount : 0.0f;
+    tg.hist_d_out[idx] = hd;
+    tg.hist_s_out[idx] = hs;
+    tg.hdr[idx] = hdr;
+}
+
 // Renderer._render_to_image (pathtracer.py:634-662) with uchimura (math_utils.py:163-186)
 VRT_DEV float uchimura1(float x) {
     const double P = 1.0, a = 1.0, m = 0.22, l = 0.4, c = 1.33, b = 0.0;
