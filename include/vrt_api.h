@@ -93,7 +93,10 @@ typedef struct vrt_stats {
     uint32_t pipeline_flags;      /* bit 0: launches of consecutive vrt_accumulate calls overlap; bit 1: the next launch's dispatch
                                      is held until the running one starts to drain (stream wait on a kernel-raised word; left out
                                      where a self-test finds that queue operations are serialised, e.g. under rocprofv3 --pmc);
-                                     bits 2..4: HALF the render launches the pipeline keeps in flight (1, 2, 4 for 2, 4, 8; 0 while not overlapped);
+                                     bits 2..4: HALF the render launches the pipeline keeps in flight (1, 2, 4 for 2, 4, 8; 0 while not overlapped).
+                                     Launches of half the slots on TWO render streams (value 1 with 2 in bits 5..7) are the shape a runtime
+                                     with fewer hardware queues than the four-deep pipeline has streams runs (GPU_MAX_HW_QUEUES below 6);
+                                     the development build's three-stream shape (VRT_STREAMS=3) reports 2, the launch order it shares;
                                      bits 5..7: a launch takes 1 / this many of the workgroup slots (1, 2 or 4);
                                      bits 8..23: times the host released that wait (error paths, synchronisation watchdog);
                                      bits 24..31: times the pipeline was drained to change its depth (a caller that changes the
@@ -171,7 +174,10 @@ int vrt_fetch_hdr_device_async(vrt_ctx* ctx, void* device_ptr);
  * round trips; NULL returns to a private stream.  The stream must outlive the context or be reset first.
  * Everything a caller can observe (results, fetches, stats) is ordered on this stream.  Render launches of
  * consecutive vrt_accumulate calls may run on two to eight internal streams of the context so that one starts while the
- * previous one drains; each is followed, on THIS stream, by the temporal pass that waits for it. */
+ * previous one drains; each is followed, on THIS stream, by the temporal pass that waits for it (one pass for several
+ * launches where the accumulation is deferred: vrt_accumulate).  How many streams depends on the launch size and on the
+ * hardware queues the HIP runtime was started with (GPU_MAX_HW_QUEUES, read at vrt_create): busy streams that share a
+ * queue serialise, so with the runtime's default of four a 1080p context runs two render streams, with sixteen four. */
 int vrt_set_stream(vrt_ctx* ctx, void* hip_stream);
 /* Renderer.fetch_image (pathtracer.py:1321-1323, 634-662): LDR rgba f32[H][W][4] */
 int vrt_fetch_ldr(vrt_ctx* ctx, float* out);

@@ -74,7 +74,7 @@ struct EventPair { hipEvent_t a, b; int kind; unsigned weight; };  // kind 0 ren
 // A build with -DVRT_DEV_KNOBS (build_variants/libvrt_dev.so: `python -m voxel_rt2_amd.build --variant dev -DVRT_DEV_KNOBS`,
 // loaded by tests/test_gpu_pipeline.py and the A/B runs of tools/) adds the development switches: the fault-injection hook
 // VRT_TEST_FAIL_LAUNCH and the A/B switches VRT_CULL, VRT_DENSE, VRT_DEEP_ITEMS, VRT_DEEPER_ITEMS, VRT_STREAMS, VRT_GRID_DIV,
-// VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER.
+// VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER, VRT_PASS_STREAM.
 struct Knobs {
     int render = -1;               // -1: the library's choice, 0: fused, 1: pool; -2: a value VRT_RENDER does not know
     bool overlap = true;
@@ -84,6 +84,7 @@ struct Knobs {
     int cull = -1, dense = -1;     // -1: decided from the scene (vrt_prepare)
     long long deep_items = (long long)12 << 20, deeper_items = (long long)9 << 19;
     int streams = 0, grid_div = 0; // 0: decided from the frame size (ensure_overlap)
+    int pass_stream = -1;          // -1: decided with the pipeline's shape (pipeline_mode_for), 0: grouped passes on the context's stream, 1: on a render stream
     bool drain_gate = true, fuse_restir = true, overlap_single = true;
     int max_fused = VRT_MAX_FUSED, full_below = 2, chunk = 0, fail_launch = -1, gate_extra = 0, time_every = 0;
     int defer4 = VRT_DEFER_4DEEP, defer8 = 1;   // render launches whose accumulation runs as one pass, per pipeline depth (VRT_DEFER: both)
@@ -100,7 +101,8 @@ static Knobs read_knobs() {
     if (const char* e = getenv("VRT_DENSE")) k.dense = atoi(e) != 0;
     if (const char* e = getenv("VRT_DEEP_ITEMS")) k.deep_items = atoll(e);
     if (const char* e = getenv("VRT_DEEPER_ITEMS")) k.deeper_items = atoll(e);
-    if (const char* e = getenv("VRT_STREAMS")) { const int v = atoi(e); if (v == 2 || v == 4 || v == 8) k.streams = v; }
+    if (const char* e = getenv("VRT_STREAMS")) { const int v = atoi(e); if (v == 2 || v == 3 || v == 4 || v == 8) k.streams = v; }
+    if (const char* e = getenv("VRT_PASS_STREAM")) { const int v = atoi(e); if (v == 0 || v == 1) k.pass_stream = v; }
     if (const char* e = getenv("VRT_GRID_DIV")) { const int v = atoi(e); if (v >= 1 && v <= 4) k.grid_div = v; }
     if (const char* e = getenv("VRT_DRAIN_GATE")) k.drain_gate = atoi(e) != 0;
     if (const char* e = getenv("VRT_FUSE")) { const int v = atoi(e); if (v >= 1 && v <= VRT_MAX_FUSED) k.max_fused = v; }
@@ -206,8 +208,17 @@ struct vrt_ctx {
     // Deferred accumulation: with a static camera the passes of K consecutive overlapped launches run as ONE kernel
     // (k_temporal_group) once the K-th is queued, or earlier when somebody is about to look (flush_deferred).  A launch's
     // planes stay occupied until then: n_sets = n_streams + K copies.
-    struct Deferred { TemporalSlice slice; int set; bool timed; };
+    struct Deferred { TemporalSlice slice; int set; int lane; bool timed; };
     std::vector<Deferred> deferred;
+    // Where a grouped pass runs: on the context's stream, or (development switch VRT_PASS_STREAM=1, an A/B shape that no
+    // configuration selects: pipeline_mode_for) on the render stream of the group's last launch -- behind it in stream order,
+    // behind the others by their events, passes following one another by last_pass_ev; the context's stream then only WAITS
+    // for the pass's event (queue_group), so that whatever is queued on it next, by the library or the caller, comes behind it.
+    bool pass_on_render = false;
+    hipEvent_t last_pass_ev = nullptr;   // event of the most recent pass queued on a render stream (nullptr: none since the streams were drained)
+    int last_pass_lane = -1;
+    bool main_touched = true;   // the context's stream was given work since the last pass on a render stream: that pass's successor waits for it
+    unsigned lane_last_seq[VRT_MAX_STREAMS] = {};   // launch_seq + 1 of the last launch queued on each render stream (0: none)
     int n_sets = 3;      // copies in use (ensure_overlap)
     int defer_k = 1;     // K of the pipeline mode in use (1: every launch has a pass of its own)
     bool overlap_ready = false, overlap_failed = false;
@@ -849,16 +860,32 @@ static int record(vrt_ctx* c, int kind, hipEvent_t* a, hipEvent_t* b, unsigned w
 // (GPU_MAX_HW_QUEUES, which voxel_rt2_amd/_lib.py sets unless the user has).
 // VRT_DEEP_ITEMS / VRT_DEEPER_ITEMS (development build): largest launch (pixels x fused samples) of each kind; VRT_STREAMS /
 // VRT_GRID_DIV override.
-static void pipeline_mode_for(const vrt_ctx* c, int g, bool heavy, int* n_streams, int* grid_div) {
+// The queue-lean shape.  The four-deep pipeline keeps five streams busy (four render streams and the context's, which carries the
+// grouped passes) beside the runtime's null stream.  A runtime with four hardware queues places them on three: two render
+// streams share one queue and the context's stream shares another with a third (profiles/r06_a_queues_q4.txt: the queue ids of
+// the kernel trace), and a launch then sits behind the stream wait or the pass of a stream it has nothing to do with (-7 %
+// against sixteen queues).  With fewer queues than streams the same launches -- half the slots each, two running at any time, one
+// pass per K launches -- go to TWO render streams: launch k follows launch k - 2 in stream order, which says what the dispatch
+// gate would (accumulate_impl leaves the stream wait out), and two render streams and the context's stream have a queue each.
+// Launch k then starts when launch k - 2 has completed, not when it begins to drain: 3.3 % slower than four streams where the
+// queues are there (sixteen: 8 923-8 958 against 9 205-9 259), 4.5 % faster where they are not (four: 8 913-8 955 against
+// 8 547-8 572).  Three render streams lose a quarter at four queues with the pass on either stream (two of them share a queue:
+// 6 650-6 750), the pass on a render stream loses 2.6 % with two (it holds that stream's next launch back: 8 715-8 720) and
+// changes nothing with four (profiles/r06_a_shapes.txt).
+#define VRT_LEAN_STREAMS 2
+static void pipeline_mode_for(const vrt_ctx* c, int g, bool heavy, int* n_streams, int* grid_div, bool* pass_on_render) {
     // (heavy: the dense-grid kernel -- six rays a path instead of two: an item is about twice the work, a rank's 4.1 M items of an
     // 8-way split of a dense 4K frame lose 10 % in the eight-deep pipeline that the same number of S1's items gain 2-17 % from)
     const size_t items = (size_t)c->cfg.width * owned_rows(c) * (size_t)g;
     const bool deep = items <= (size_t)c->knobs.deep_items;                                         // 12 M
     const bool deeper = deep && items * (heavy ? 2u : 1u) <= (size_t)c->knobs.deeper_items && c->knobs.hw_queues >= 16;  // 4.5 M
-    *n_streams = deeper ? 8 : deep ? 4 : 2;
+    const bool lean = deep && !deeper && c->knobs.hw_queues < 4 + 2;   // (the render streams, the context's stream, the null stream)
+    *n_streams = deeper ? 8 : deep ? (lean ? VRT_LEAN_STREAMS : 4) : 2;
     *grid_div = deeper ? 4 : deep ? 2 : 1;
+    *pass_on_render = false;   // (development switch VRT_PASS_STREAM=1: measured, not faster in any shape)
     if (c->knobs.streams) *n_streams = c->knobs.streams;
     if (c->knobs.grid_div) *grid_div = c->knobs.grid_div;
+    if (c->knobs.pass_stream >= 0) *pass_on_render = c->knobs.pass_stream != 0;
 }
 // Streams, copies and events for a pipeline `want` launches deep (what a shallower one already has is kept).
 static bool grow_pipeline(vrt_ctx* c, int want, int want_sets) {
@@ -892,21 +919,24 @@ static bool can_defer(const vrt_ctx* c) { return c->hdr_targets.empty() && !c->h
 static bool ensure_overlap(vrt_ctx* c, int g, bool heavy) {
     if (c->overlap_failed) return false;
     int ns = 0, gd = 0;
-    pipeline_mode_for(c, g, heavy, &ns, &gd);
+    bool por = false;
+    pipeline_mode_for(c, g, heavy, &ns, &gd, &por);
     // K of the mode: contexts whose launches are never deferred (can_defer) do not pay for the copies
-    int k = !can_defer(c) ? 1 : ns == 4 ? c->knobs.defer4 : ns == 8 ? c->knobs.defer8 : 1;
+    int k = !can_defer(c) ? 1 : (ns == 4 || (ns < 4 && gd == 2)) ? c->knobs.defer4 : ns == 8 ? c->knobs.defer8 : 1;
     if (k > VRT_MAX_SETS - ns) k = VRT_MAX_SETS - ns;
     if (k < 1) k = 1;
     if (c->overlap_ready) {
-        if (ns == c->n_streams && gd == c->grid_div) return true;
+        if (ns == c->n_streams && gd == c->grid_div && por == c->pass_on_render) return true;
         if (!grow_pipeline(c, ns, ns + k)) return true;   // no memory for the other mode: this one goes on
         if (sync_guarded(c, c->stream) != VRT_OK) return true;   // (with the deferred passes of the mode that ends)
         for (int s = 0; s < VRT_MAX_STREAMS; s++) if (c->rstream[s]) (void)hipStreamSynchronize(c->rstream[s]);
         if (sync_guarded(c, c->stream) != VRT_OK) return true;   // (the temporal passes behind those launches)
         (void)hipGetLastError();
         for (int s = 0; s < VRT_MAX_SETS; s++) c->ev_t_valid[s] = false;   // every pass has completed
+        c->last_pass_ev = nullptr;
         c->n_streams = ns;
         c->grid_div = gd;
+        c->pass_on_render = por;
         c->n_sets = ns + k;
         c->defer_k = k;
         c->mode_switches++;
@@ -916,6 +946,7 @@ static bool ensure_overlap(vrt_ctx* c, int g, bool heavy) {
     if (!ok && k > 1) { k = 1; ok = grow_pipeline(c, ns, ns + 1); }   // no memory for the deferred launches' copies: a pass per launch
     c->n_streams = ns;
     c->grid_div = gd;
+    c->pass_on_render = por;
     c->n_sets = ns + k;
     c->defer_k = k;
     ok = ok && hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming) == hipSuccess;
@@ -961,6 +992,7 @@ static void abort_pipeline(vrt_ctx* c) {
     (void)hipStreamSynchronize(nullptr);   // (the fill runs on the NULL stream: see dalloc)
     (void)hipGetLastError();
     for (int s = 0; s < VRT_MAX_SETS; s++) c->ev_t_valid[s] = false;
+    c->last_pass_ev = nullptr;   // (every stream was drained above: the passes on the render streams with them)
     c->main_dirty = true;
     c->render_blocks = 0;   // residency and scratch are looked at again
     g_err = keep;
@@ -972,8 +1004,8 @@ static f3* next_hdr_target(vrt_ctx* c) {
     if (c->hdr_targets.empty()) return nullptr;
     return (f3*)c->hdr_targets[(size_t)(c->hdr_targets_written++ % c->hdr_targets.size())];
 }
-static int wait_cbuf_readers(vrt_ctx* c, int b) {   // an asynchronous fetch may still be reading the HDR buffer a pass is about to write
-    if (c->cbuf_read_pending[b]) { HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_cbuf_read[b], 0)); c->cbuf_read_pending[b] = false; }
+static int wait_cbuf_readers(vrt_ctx* c, int b, hipStream_t st = nullptr) {   // an asynchronous fetch may still be reading the HDR buffer a pass (on st) is about to write
+    if (c->cbuf_read_pending[b]) { HIP_TRY(hipStreamWaitEvent(st ? st : c->stream, c->ev_cbuf_read[b], 0)); c->cbuf_read_pending[b] = false; }
     return VRT_OK;
 }
 
@@ -985,9 +1017,21 @@ static int queue_group(vrt_ctx* c, size_t first, size_t n) {
     tg.inv_res = mk2((float)(1.0 / (double)tg.W), (float)(1.0 / (double)tg.H));   // (make_frame_params)
     tg.n_slices = (int)n;
     bool timed = false;
+    // the stream the pass runs on: the context's, or the render stream of the group's last launch (vrt_ctx::pass_on_render)
+    const int lane = c->pass_on_render ? c->deferred[first + n - 1].lane : -1;
+    hipStream_t ps = lane >= 0 ? c->rstream[lane] : c->stream;
+    if (lane >= 0) {
+        if (c->main_touched) {   // histories reset, frames fetched, passes of launches that were not deferred: all on the context's stream
+            HIP_TRY(hipEventRecord(c->ev_main, c->stream));
+            HIP_TRY(hipStreamWaitEvent(ps, c->ev_main, 0));
+            c->main_touched = false;
+        }
+        // the history ping-pong makes passes sequential
+        if (c->last_pass_ev && c->last_pass_lane != lane) HIP_TRY(hipStreamWaitEvent(ps, c->last_pass_ev, 0));
+    }
     for (size_t i = 0; i < n; i++) {
         const vrt_ctx::Deferred& d = c->deferred[first + i];
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_r[d.set], 0));
+        if (d.lane != lane) HIP_TRY(hipStreamWaitEvent(ps, c->ev_r[d.set], 0));   // (a launch on the pass's own stream precedes it there)
         tg.slice[i] = d.slice;
         timed = timed || d.timed;
     }
@@ -995,16 +1039,25 @@ static int queue_group(vrt_ctx* c, size_t first, size_t n) {
     tg.hist_s_in = c->d_hist_s[c->hist_in]; tg.hist_s_out = c->d_hist_s[c->hist_in ^ 1];
     tg.hdr = c->d_cbuf[c->cidx ^ 1];
     tg.gb_refl_filtered = c->d_gb_refl_f;
-    if (wait_cbuf_readers(c, c->cidx ^ 1) != VRT_OK) return VRT_E_DEVICE;
+    if (wait_cbuf_readers(c, c->cidx ^ 1, ps) != VRT_OK) return VRT_E_DEVICE;
     hipEvent_t a = nullptr, b = nullptr;
     if (timed) {   // a group with a timed launch in it carries the timers, and counts for all of its passes
         if (record(c, 1, &a, &b, (unsigned)n) != VRT_OK) return VRT_E_DEVICE;
-        HIP_TRY(hipEventRecord(a, c->stream));
+        HIP_TRY(hipEventRecord(a, ps));
     }
-    HIP_TRY(launch_temporal_group(c->stream, tg, c->own0, c->own1));
-    if (timed) HIP_TRY(hipEventRecord(b, c->stream));
+    HIP_TRY(launch_temporal_group(ps, tg, c->own0, c->own1));
+    if (timed) HIP_TRY(hipEventRecord(b, ps));
     const int last_set = c->deferred[first + n - 1].set;   // one event for the group: every copy it read is free behind it
-    HIP_TRY(hipEventRecord(c->ev_t[last_set], c->stream));
+    HIP_TRY(hipEventRecord(c->ev_t[last_set], ps));
+    if (lane >= 0) {
+        // Whatever comes next on the context's stream -- a fetch, a synchronisation, a pass of a launch that is not deferred,
+        // the caller's own work -- comes behind the pass: a wait, no kernel.
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_t[last_set], 0));
+        c->last_pass_ev = c->ev_t[last_set];
+        c->last_pass_lane = lane;
+    } else {
+        c->main_touched = true;
+    }
     for (size_t i = 0; i < n; i++) { const int st = c->deferred[first + i].set; c->ev_t_valid[st] = true; c->ev_t_of[st] = last_set; }
     c->passes_n[1] += (uint32_t)n;   // accumulation passes in the reference's sense: one per render launch
     c->hist_in ^= 1;
@@ -1015,6 +1068,8 @@ static int queue_group(vrt_ctx* c, size_t first, size_t n) {
 // otherwise the tail behind the last launch of a run grows from one launch's accumulation to all the pending ones'.
 static int flush_deferred(vrt_ctx* c, bool split_tail) {
     const size_t m = c->deferred.size();
+    // (split_tail: every caller but the K-th launch of a group is about to look at, or to queue work on, the context's stream)
+    if (split_tail) c->main_touched = true;
     if (m == 0) return VRT_OK;
     int rc = VRT_OK;
     bool split = false;
@@ -1168,7 +1223,9 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
             const unsigned back = c->prev_launch_full ? 1u : (unsigned)(c->grid_div + c->knobs.gate_extra);
             unsigned target = c->launch_seq + 1u > back ? c->launch_seq + 1u - back : 0u;
             if (target < c->last_full_seq) target = c->last_full_seq;
-            if (c->drain_signal && c->drain_signalled && target > 0u)
+            // (a launch already on this stream that is the target or newer has raised the word by the time this one's turn comes:
+            // stream order says what the wait would)
+            if (c->drain_signal && c->drain_signalled && target > 0u && c->lane_last_seq[lane_of] < target)
                 HIP_TRY(hipStreamWaitValue32(rs, c->drain_signal, target, hipStreamWaitValueGte, 0xFFFFFFFFu));
         } else if (c->last_set != 0) {
             // back to the single copy: whoever reads pixels this launch does not write (moving camera at half render
@@ -1241,6 +1298,7 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
             HIP_TRY(hipEventRecord(c->ev_r[set], rs));
             if (!defer) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_r[set], 0));
             c->last_render_set = set;
+            c->lane_last_seq[lane_of] = seq + 1u;
         }
         if (defer) {   // what this launch's own pass would have been given, as it stands now (camera, scene, planes)
             vrt_ctx::Deferred d;
@@ -1249,11 +1307,12 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
             d.slice.gb_depth = out.gb_depth; d.slice.gb_refl_raw = out.gb_refl_depth;
             d.slice.max_accum_frames = fp.max_accum_frames;
             d.slice.n_samples = g; d.slice.sample_stride = out.sample_stride;
-            d.set = set; d.timed = timed;
+            d.set = set; d.lane = lane_of; d.timed = timed;
             c->deferred.push_back(d);
         }
         // ReSTIR: spatial reuse and accumulation sample by sample over the planes of the launch (one pass with one sample)
         const int passes = defer ? 0 : restir ? g : 1;
+        if (passes) c->main_touched = true;   // (the passes below run on the context's stream)
         int hist = c->hist_in, ci = c->cidx;   // (the context's own copies only move once every launch of the iteration is queued)
         for (int s = 0; s < passes; s++) {
             const size_t off = (size_t)s * (size_t)out.sample_stride;   // this sample's plane (ReSTIR; stride 0 with one sample)
@@ -1422,6 +1481,7 @@ int vrt_set_stream(vrt_ctx* c, void* hip_stream) {
     resolve_events(c);
     for (int s = 0; s < VRT_MAX_SETS; s++) c->ev_t_valid[s] = false;  // everything recorded on the old stream has completed
     c->main_dirty = true;
+    c->main_touched = true;
     if (c->owns_stream && c->stream) hipStreamDestroy(c->stream);
     if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->owns_stream = false; }
     else { HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->owns_stream = true; }
@@ -1589,7 +1649,7 @@ int vrt_get_stats(vrt_ctx* c, vrt_stats* out) {
     }
     c->stats.pipeline_flags = (c->overlap_ready ? 1u : 0u) | (c->drain_signal ? 2u : 0u) | (((uint32_t)c->gate_releases & 0xFFFFu) << 8) |
                               ((c->mode_switches < 255u ? c->mode_switches : 255u) << 24) |
-                              (c->overlap_ready ? ((uint32_t)(c->n_streams >> 1) << 2) | ((uint32_t)c->grid_div << 5) : 0u);
+                              (c->overlap_ready ? ((uint32_t)(c->n_streams == 3 ? 2 : c->n_streams >> 1) << 2) | ((uint32_t)c->grid_div << 5) : 0u);
     *out = c->stats;
     return VRT_OK;
 }
