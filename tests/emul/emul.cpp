@@ -274,7 +274,7 @@ static int accumulate_g(Emu* c, int n_samples) {
         f3* rt = c->cbuf[c->cidx].data();
         f3* hdr = c->cbuf[c->cidx ^ 1].data();
         out.color_d = rt; out.color_s = c->color_s.data();
-        if (c->cam.render_scale != 1.0f) {  // as vrt_api.hip: a partial pass starts from the last pass's g-buffer
+        if (c->cam.render_scale != 1.0f) {  // as vrt_pipeline.hip: a partial pass starts from the last pass's g-buffer
             c->gb_normal[c->cur] = c->gb_normal[c->cur ^ 1];
             c->gb_depth[c->cur] = c->gb_depth[c->cur ^ 1];
         }

@@ -52,7 +52,7 @@ int tg_run(int W, int H, int row0, int row1, int r0, int r1, int K, const int* g
             for (int u = 0; u < W; u++) temporal_group_pixel(tg, u, v);
         return 0;
     }
-    // K passes of their own: histories and HDR buffers swap roles after each (vrt_api.hip, accumulate_impl)
+    // K passes of their own: histories and HDR buffers swap roles after each (vrt_pipeline.hip, accumulate_impl)
     std::vector<f4> hd[2], hs[2];
     std::vector<f3> hdr[2];
     for (int b = 0; b < 2; b++) { hd[b].resize(npix); hs[b].resize(npix); hdr[b].resize(npix); }

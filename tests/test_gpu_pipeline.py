@@ -22,7 +22,7 @@ W, H, DEPTH = 640, 360, 6
 
 def render(calls=(4, 4, 4, 3, 4), reserve=None, dev=False):
     """dev: through build_variants/libvrt_dev.so, the build that reads the development switches (VRT_STREAMS, VRT_DRAIN_GATE,
-    VRT_TEST_FAIL_LAUNCH, ...: csrc/vrt_api.hip read_knobs) -- the shipped library ignores them."""
+    VRT_TEST_FAIL_LAUNCH, ...: csrc/vrt_plan.h read_knobs) -- the shipped library ignores them."""
     mat, rgb, params = scenes.scene_sunlit(0)
     cfg = host.make_config(W, H, voxel_edges=params["voxel_edges"], exposure=params["exposure"], max_depth=DEPTH, seed=5)
     s = NativeSession(_lib.load_dev() if dev else _lib.load(), "vrt_", cfg)

@@ -1,4 +1,4 @@
-"""The shapes of the pipeline of half-size launches (csrc/vrt_api.hip, pipeline_mode_for): four render streams with the grouped
+"""The shapes of the pipeline of half-size launches (csrc/vrt_plan.h, plan_pipeline_shape): four render streams with the grouped
 accumulation pass on the context's stream (what runs where the runtime has six hardware queues or more), two render streams
 without the dispatch gate's stream wait (what runs where it has fewer), and the shapes the development build can force beside
 them: three render streams, the pass on the render stream of the group's last launch.  Every shape renders

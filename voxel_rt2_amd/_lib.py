@@ -40,7 +40,7 @@ def _share_hip_runtime_with_torch():
 
 
 def _want_hw_queues(n=16):
-    """The library renders on up to eight streams of its own beside the caller's (vrt_api.hip, ensure_overlap); a multi-GPU
+    """The library renders on up to eight streams of its own beside the caller's (vrt_pipeline.hip, ensure_overlap); a multi-GPU
     rank adds a gather stream and RCCL's.  The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues
     (default 4) and two streams that share a queue serialise: a wait queued for the gather then holds back the next render
     launch (one rank's share of an 8-way split: 0.418 ms per step with 4 queues, 0.317 with 8; the eight-launch pipeline the
@@ -69,7 +69,7 @@ _dev = None
 
 def load_dev():
     """The same library built with -DVRT_DEV_KNOBS (build_variants/libvrt_dev.so): it also reads the development switches --
-    the fault-injection hook and the A/B switches (csrc/vrt_api.hip, read_knobs) -- which the shipped library does not carry.
+    the fault-injection hook and the A/B switches (csrc/vrt_plan.h, read_knobs) -- which the shipped library does not carry.
     For tests/test_gpu_pipeline.py and the A/B runs of tools/; built here when missing or older than the sources."""
     global _dev
     if _dev is None:

@@ -1,0 +1,161 @@
+// vrt_plan.h -- the launch pipeline's decisions as plain functions over plain values: the environment switches, the pipeline's shape,
+// how many samples a launch fuses, which launches carry timers, what a dispatch waits for, which copy and stream a launch takes.
+// Nothing here knows HIP or vrt_ctx: vrt_pipeline.hip calls these between its HIP calls, tests/emul/plan_emul.cpp calls them on a
+// machine without a GPU (tests/test_pipeline_plan_host.py).
+#pragma once
+#include <cstddef>
+#include <cstdlib>
+#include <cstring>
+
+#define VRT_MAX_FUSED 4   // samples of one vrt_accumulate(n) call rendered by a single launch
+#define VRT_MAX_STREAMS 8 // render launches in flight at most (a stream, a pool scratch and a camera-ray table each): 2, 4 or 8 are used
+#define VRT_MAX_SETS 12   // copies of what a render launch writes: streams + 1 are used, or streams + K
+                          // where the accumulation of K launches is deferred into one pass (flush_deferred)
+#ifndef VRT_DEFER_4DEEP
+#define VRT_DEFER_4DEEP 4 // K of the four-deep pipeline (launches of up to 12 M items).  The two-deep one (4K frames: a set is 1 GB there)
+#endif                    // and the eight-deep one (not measured with K > 1) accumulate every launch in a pass of its own
+#define VRT_MAX_DEFER 8   // largest K a switch may ask for: VRT_MAX_GROUP of vrt_temporal.h (vrt_ctx.h asserts that they agree)
+#define VRT_LEAN_STREAMS 2
+
+// Environment switches, read ONCE when a context is created (never on the launch path).
+// The shipped library knows four: VRT_RENDER=pool|fused (which of the two schedules of the same per-path code renders),
+// VRT_OVERLAP=0 (isolated launches: what the --pmc passes and the tile balancing of bench.py measure on),
+// VRT_GATE_WATCHDOG_MS (how long a synchronisation waits at a gated launch before the host releases the gate) and the HIP
+// runtime's own GPU_MAX_HW_QUEUES (how deep a pipeline the runtime's queues carry).
+// A build with -DVRT_DEV_KNOBS (build_variants/libvrt_dev.so: `python -m voxel_rt2_amd.build --variant dev -DVRT_DEV_KNOBS`,
+// loaded by tests/test_gpu_pipeline.py and the A/B runs of tools/) adds the development switches: the fault-injection hook
+// VRT_TEST_FAIL_LAUNCH and the A/B switches VRT_CULL, VRT_DENSE, VRT_DEEP_ITEMS, VRT_DEEPER_ITEMS, VRT_STREAMS, VRT_GRID_DIV,
+// VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER, VRT_PASS_STREAM.
+struct Knobs {
+    int render = -1;               // -1: the library's choice, 0: fused, 1: pool; -2: a value VRT_RENDER does not know
+    bool overlap = true;
+    double gate_watchdog_s = 2.0;
+    int hw_queues = 4;
+    // development switches: the defaults below are what the shipped library always runs with
+    int cull = -1, dense = -1;     // -1: decided from the scene (vrt_prepare)
+    long long deep_items = (long long)12 << 20, deeper_items = (long long)9 << 19;
+    int streams = 0, grid_div = 0; // 0: decided from the frame size (plan_pipeline_shape)
+    int pass_stream = -1;          // -1: decided with the pipeline's shape (plan_pipeline_shape), 0: grouped passes on the context's stream, 1: on a render stream
+    bool drain_gate = true, fuse_restir = true, overlap_single = true;
+    int max_fused = VRT_MAX_FUSED, full_below = 2, chunk = 0, fail_launch = -1, gate_extra = 0, time_every = 0;
+    int defer4 = VRT_DEFER_4DEEP, defer8 = 1;   // render launches whose accumulation runs as one pass, per pipeline depth (VRT_DEFER: both)
+};
+static Knobs read_knobs() {
+    Knobs k;
+    if (const char* e = getenv("VRT_RENDER")) k.render = strcmp(e, "fused") == 0 ? 0 : strcmp(e, "pool") == 0 ? 1 : -2;
+    if (const char* e = getenv("VRT_OVERLAP")) k.overlap = atoi(e) != 0;
+    if (const char* e = getenv("VRT_GATE_WATCHDOG_MS")) { const double v = atof(e); if (v > 0.0) k.gate_watchdog_s = v * 1e-3; }
+    if (const char* e = getenv("GPU_MAX_HW_QUEUES")) k.hw_queues = atoi(e);
+#if defined(VRT_DEV_KNOBS)
+    if (const char* e = getenv("VRT_TEST_FAIL_LAUNCH")) k.fail_launch = atoi(e);
+    if (const char* e = getenv("VRT_CULL")) k.cull = atoi(e) != 0;
+    if (const char* e = getenv("VRT_DENSE")) k.dense = atoi(e) != 0;
+    if (const char* e = getenv("VRT_DEEP_ITEMS")) k.deep_items = atoll(e);
+    if (const char* e = getenv("VRT_DEEPER_ITEMS")) k.deeper_items = atoll(e);
+    if (const char* e = getenv("VRT_STREAMS")) { const int v = atoi(e); if (v == 2 || v == 3 || v == 4 || v == 8) k.streams = v; }
+    if (const char* e = getenv("VRT_PASS_STREAM")) { const int v = atoi(e); if (v == 0 || v == 1) k.pass_stream = v; }
+    if (const char* e = getenv("VRT_GRID_DIV")) { const int v = atoi(e); if (v >= 1 && v <= 4) k.grid_div = v; }
+    if (const char* e = getenv("VRT_DRAIN_GATE")) k.drain_gate = atoi(e) != 0;
+    if (const char* e = getenv("VRT_FUSE")) { const int v = atoi(e); if (v >= 1 && v <= VRT_MAX_FUSED) k.max_fused = v; }
+    if (const char* e = getenv("VRT_FUSE_RESTIR")) k.fuse_restir = atoi(e) != 0;
+    if (const char* e = getenv("VRT_OVERLAP_SINGLE")) k.overlap_single = atoi(e) != 0;
+    if (const char* e = getenv("VRT_TIME_EVERY")) { const int v = atoi(e); if (v >= 1 && v <= 1024) k.time_every = v; }   // 0 (default): by launch size
+    if (const char* e = getenv("VRT_GATE_EXTRA")) { const int v = atoi(e); if (v >= 0 && v <= 4) k.gate_extra = v; }
+    if (const char* e = getenv("VRT_FULL_BELOW")) { const int v = atoi(e); if (v >= 1 && v <= 3) k.full_below = v; }
+    if (const char* e = getenv("VRT_DEFER")) { const int v = atoi(e); if (v >= 0 && v <= VRT_MAX_DEFER) k.defer4 = k.defer8 = v < 1 ? 1 : v; }   // 0, 1: a pass per launch
+    if (const char* e = getenv("VRT_CHUNK")) { const int v = atoi(e); if (v >= 64 && v <= 4096) k.chunk = v / 64 * 64; }
+#endif
+    return k;
+}
+
+// How deep a launch of `items` work items (pixels x fused samples) wants the pipeline.  A launch lasts at least as long as its
+// deepest path takes alone (about 0.2 ms at 8 bounces), whatever its size, and a workgroup slot its wave has left stays empty
+// until the NEXT launch may start.
+// A launch of every slot can only be followed when it starts to drain (two in flight).  Launches of half the slots each follow
+// one another at half that distance -- two run at full strength while a third drains and a fourth waits its turn.  Measured
+// (profiles/r02_pipeline_depth.txt): 1080p x 4 samples +3.7 %, half of it +5 %, an eighth (one rank's rows of an 8-GPU
+// run) +24 %; thirds and quarters of the slots are worse again; a 4K frame (33 M items a launch) loses 0-7 % and keeps
+// the two-deep pipeline.
+// Deeper still for the smaller launches -- one rank's rows of an 8-GPU split of 1080p are 1 M items: eight launches of a
+// quarter of the slots each (+7.5 % on those rows; with the timers thinned out, below: +2 % on half a frame of 4.1 M items,
+// +17 % on its cheap upper 480 rows, -2 % on a whole frame, -9 % on the sun-lit one: the limit is 4.5 M items).  Each render stream wants a
+// hardware queue of its own (two streams on one queue serialise), so only where the runtime was started with sixteen
+// (GPU_MAX_HW_QUEUES, which voxel_rt2_amd/_lib.py sets unless the user has).
+// VRT_DEEP_ITEMS / VRT_DEEPER_ITEMS (development build): largest launch (pixels x fused samples) of each kind; VRT_STREAMS /
+// VRT_GRID_DIV override.
+// The queue-lean shape.  The four-deep pipeline keeps five streams busy (four render streams and the context's, which carries the
+// grouped passes) beside the runtime's null stream.  A runtime with four hardware queues places them on three: two render
+// streams share one queue and the context's stream shares another with a third (profiles/r06_a_queues_q4.txt: the queue ids of
+// the kernel trace), and a launch then sits behind the stream wait or the pass of a stream it has nothing to do with (-7 %
+// against sixteen queues).  With fewer queues than streams the same launches -- half the slots each, two running at any time, one
+// pass per K launches -- go to TWO render streams: launch k follows launch k - 2 in stream order, which says what the dispatch
+// gate would (plan_gate_wait leaves the stream wait out), and two render streams and the context's stream have a queue each.
+// Launch k then starts when launch k - 2 has completed, not when it begins to drain: 3.3 % slower than four streams where the
+// queues are there (sixteen: 8 923-8 958 against 9 205-9 259), 4.5 % faster where they are not (four: 8 913-8 955 against
+// 8 547-8 572).  Three render streams lose a quarter at four queues with the pass on either stream (two of them share a queue:
+// 6 650-6 750), the pass on a render stream loses 2.6 % with two (it holds that stream's next launch back: 8 715-8 720) and
+// changes nothing with four (profiles/r06_a_shapes.txt).
+struct PipelineShape {
+    int n_streams;         // depth of the launch pipeline: 2, 4 with launches of half the workgroup slots each, or 8 with quarters
+    int grid_div;          // an overlapped launch takes render_blocks / grid_div workgroups
+    bool pass_on_render;   // grouped passes run on a render stream (development switch VRT_PASS_STREAM=1: measured, not faster in any shape)
+    int defer_k;           // K: render launches whose accumulation runs as one pass (1: every launch has a pass of its own)
+};
+static inline PipelineShape plan_pipeline_shape(size_t items, bool heavy, int hw_queues, bool can_defer, const Knobs& knobs) {
+    // (heavy: the dense-grid kernel -- six rays a path instead of two: an item is about twice the work, a rank's 4.1 M items of an
+    // 8-way split of a dense 4K frame lose 10 % in the eight-deep pipeline that the same number of S1's items gain 2-17 % from)
+    const bool deep = items <= (size_t)knobs.deep_items;                                                       // 12 M
+    const bool deeper = deep && items * (heavy ? 2u : 1u) <= (size_t)knobs.deeper_items && hw_queues >= 16;    // 4.5 M
+    const bool lean = deep && !deeper && hw_queues < 4 + 2;   // (the render streams, the context's stream, the null stream)
+    PipelineShape sh;
+    sh.n_streams = deeper ? 8 : deep ? (lean ? VRT_LEAN_STREAMS : 4) : 2;
+    sh.grid_div = deeper ? 4 : deep ? 2 : 1;
+    sh.pass_on_render = false;
+    if (knobs.streams) sh.n_streams = knobs.streams;
+    if (knobs.grid_div) sh.grid_div = knobs.grid_div;
+    if (knobs.pass_stream >= 0) sh.pass_on_render = knobs.pass_stream != 0;
+    // K of the mode: contexts whose launches are never deferred (can_defer) do not pay for the copies
+    const int ns = sh.n_streams;
+    int k = !can_defer ? 1 : (ns == 4 || (ns < 4 && sh.grid_div == 2)) ? knobs.defer4 : ns == 8 ? knobs.defer8 : 1;
+    if (k > VRT_MAX_SETS - ns) k = VRT_MAX_SETS - ns;
+    sh.defer_k = k < 1 ? 1 : k;
+    return sh;
+}
+
+// Samples the next launch of a vrt_accumulate(n) call renders, `left` of them still to go.
+static inline int plan_fused_count(int left, bool can_fuse, int max_fused) {
+    return (can_fuse && left > 1) ? (left < max_fused ? left : max_fused) : 1;
+}
+
+// Timers (two events around each kernel, vrt_stats' device times) cost a short step its rate: the barrier packets they put
+// around the kernel sit in the chain from one launch's drain to the next one's first wave -- a fixed 30-40 us of a step,
+// 3-25 % of the steps of 0.15-0.3 ms that a rank's rows of an 8-GPU split or the reference's one-sample calls take, nothing
+// of a 1 ms step.  What a step will take is not known when it is queued, its size is: launches of the deep pipelines (up to 12 M
+// work items, ReSTIR off) carry timers one time in eight; vrt_get_stats scales the timed launches' sum to all of them.
+static inline unsigned plan_timer_period(int time_every, bool restir, size_t items, long long deep_items) {
+    return time_every > 0 ? (unsigned)time_every : ((!restir && items <= (size_t)deep_items) ? 8u : 1u);
+}
+
+// The value of the drain signal that launch number `launch_seq` is dispatched at.  Dispatch when the launch whose workgroup slots
+// this one will take starts to drain: the one before it, or with launches of half the slots the one before that (the signal
+// carries the number + 1 of the latest launch draining) -- unless the one before it took EVERY slot (a lone launch): then that
+// one has to drain first; and never for a launch OLDER than the last one that took every slot: until that one drains there is no
+// slot at all.  0: nothing to wait for.
+static inline unsigned plan_gate_target(unsigned launch_seq, bool prev_launch_full, int grid_div, int gate_extra, unsigned last_full_seq) {
+    const unsigned back = prev_launch_full ? 1u : (unsigned)(grid_div + gate_extra);
+    const unsigned target = launch_seq + 1u > back ? launch_seq + 1u - back : 0u;
+    return target < last_full_seq ? last_full_seq : target;
+}
+// Whether the stream wait for `target` is queued at all.  (A launch already on this stream that is the target or newer has raised
+// the word by the time this one's turn comes: stream order says what the wait would.)
+static inline bool plan_gate_wait(unsigned target, unsigned lane_last_seq, bool gate_present, bool signalled) {
+    return gate_present && signalled && target > 0u && lane_last_seq < target;
+}
+
+// Workgroups of a launch that shares the chip with others: its part of the slots, in whole rounds of the 8 XCDs.
+static inline int plan_partial_blocks(int all_blocks, int grid_div) { return (all_blocks / grid_div + 7) & ~7; }
+
+// Which copy overlapped launch number `pipe_seq` writes, and which render stream (and pool scratch) it goes to: consecutive
+// launches take turns.
+static inline int plan_set_of(unsigned pipe_seq, int n_sets) { return (int)(pipe_seq % (unsigned)n_sets); }
+static inline int plan_lane_of(unsigned pipe_seq, int n_streams) { return (int)(pipe_seq % (unsigned)n_streams); }
