@@ -273,6 +273,17 @@ int vrt_detmath_probe(int device, int op, int n, const float* a, const float* b,
  * cloud_ambient (f32[3]), when not NULL, replace what vrt_prepare computed.  Needs sky_res > 0. */
 int vrt_sky_probe(vrt_ctx* ctx, int op, int n, const float* in, int in_stride, float* out, int out_stride, const uint16_t* trans_lut,
                   const float* cloud_ambient);
+/* Walk single rays on the device (test hook; the sky functions have vrt_sky_probe).  After vrt_prepare, on the context's grid and
+ * occupancy pyramid (read from global memory) and in the mode vrt_set_reference_indexing selected.  origin_dir holds n rays of
+ * 6 floats -- origin, direction -- in VOXEL units (origin 0..grid_res inside the grid), as VoxelOctreeRaytracer.raytrace takes them
+ * (raytracer.py:72; ray_min_t = eps, ray_max_t = inf as at its only call site, pathtracer.py:201-202).  `out` receives 32 bytes a
+ * ray: distance f32, cell 3 x i32, normal 3 x f32, DDA steps i32.  mode = walk + 4 * box:
+ *   walk 0: the loop of the fused render kernel with the branchy descent | 1: the same loop with the flat descent | 2: the
+ *           resumable record the pooled kernel steps (set up, suspended through a slot's packed fields every third step, result);
+ *   box  0: nothing is culled | 1: rays are tested against the bounding box of the solid voxels grown by 8 voxels, as the render
+ *           launches do (with the reference's indexing they do not, and neither does the probe).
+ * A culled ray reports distance inf, cell -1, normal 0 and 0 steps; at grid_res 128 a walk also ends where it leaves the box. */
+int vrt_trace_probe(vrt_ctx* ctx, int mode, int n, const float* origin_dir, void* out);
 /* Diagnostic builds only (library compiled with -DVRT_DIAG_REGIONS, see tools/diag_regions.py): copy out the
  * 32 x {wave entries, active lanes} counters of the instrumented regions of the render kernel and optionally
  * zero them.  The shipped library returns VRT_E_STATE -- it carries no region counters. */

@@ -165,6 +165,19 @@ void orc_unit_raytrace(orc_ctx* c, const float* o, const float* d, float tmin, f
     out[4] = h.normal.x; out[5] = h.normal.y; out[6] = h.normal.z;
     out[7] = (float)h.iters;
 }
+/* the same for n rays (ray_min_t = eps, ray_max_t = inf: pathtracer.py:201-202) in the record layout of vrt_trace_probe (include/vrt_api.h):
+ * origin_dir n x 6 floats; out n x 32 bytes = distance f32, cell 3 x i32, normal 3 x f32, iterations i32 */
+void orc_unit_raytrace_n(orc_ctx* c, int n, const float* origin_dir, void* out) {
+    for (int k = 0; k < n; k++) {
+        const float* a = origin_dir + (size_t)k * 6;
+        auto h = c->r.voxel_raytracer.raytrace(v3(a[0], a[1], a[2]), v3(a[3], a[4], a[5]), EPS, INF);
+        char* o = (char*)out + (size_t)k * 32;
+        const int32_t cell[3] = {h.ipos.x, h.ipos.y, h.ipos.z};
+        const float nrm[3] = {h.normal.x, h.normal.y, h.normal.z};
+        const int32_t iters = h.iters;
+        memcpy(o, &h.distance, 4); memcpy(o + 4, cell, 12); memcpy(o + 16, nrm, 12); memcpy(o + 28, &iters, 4);
+    }
+}
 /* out: [0] closest, [1..3] normal, [4..6] albedo, [7] hit_light, [8] mat_id */
 void orc_unit_next_hit(orc_ctx* c, const float* o, const float* d, int shadow, float* out) {
     float closest;

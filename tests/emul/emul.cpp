@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include "../../voxel_rt2_amd/csrc/vrt_restir.h"
 #include "../../voxel_rt2_amd/csrc/vrt_temporal.h"
+#include "../../voxel_rt2_amd/csrc/vrt_probe.h"
 
 using namespace vrt;
 
@@ -344,6 +345,23 @@ static int accumulate_g(Emu* c, int n_samples) {
     return 0;
 }
 
+// vrt_trace_probe (include/vrt_api.h) on the host build of the same function (vrt_probe.h): same modes, same 32-byte records
+template <int G>
+static void trace_probe_g(const Emu* c, int mode, int n, const float* rays, ProbeOut* out) {
+    GlobalPyramid<G> P;
+    P.p.l0 = c->l0.data(); P.p.l1 = c->l1.data(); P.p.l2 = c->l2.data(); P.p.l3 = c->l3.data();
+    P.p.l0c = c->l0c.data(); P.p.l0c_base = c->l0c_base.data(); P.p.l0c_count = c->l0c_base.data() + 512;
+    P.p.ref_oob = c->ref_oob ? 1 : 0;
+    const float* cull = c->cull + ((mode & PROBE_CULL_BOX) && !c->ref_oob ? 0 : 8);
+    for (int i = 0; i < n; i++) {
+        const float* a = rays + (size_t)i * 6;
+        const f3 o = mk3(a[0], a[1], a[2]), d = mk3(a[3], a[4], a[5]);
+        if ((mode & 3) == PROBE_WALK_BRANCHY) probe_ray<G, PROBE_WALK_BRANCHY>(P, o, d, cull, out[i]);
+        else if ((mode & 3) == PROBE_WALK_FLAT) probe_ray<G, PROBE_WALK_FLAT>(P, o, d, cull, out[i]);
+        else probe_ray<G, PROBE_WALK_RECORD>(P, o, d, cull, out[i]);
+    }
+}
+
 extern "C" {
 
 int emu_accumulate(Emu* c, int n_samples) { return c->cfg.grid_res == 256 ? accumulate_g<256>(c, n_samples) : accumulate_g<128>(c, n_samples); }
@@ -444,6 +462,12 @@ int emu_bsdf_selftest(int n, uint32_t seed) {
         }
     }
     return bad;
+}
+int emu_trace_probe(Emu* c, int mode, int n, const float* origin_dir, void* out) {
+    if (!c || !origin_dir || !out || n <= 0 || mode < 0 || (mode & ~(3 | PROBE_CULL_BOX)) || (mode & 3) >= PROBE_WALK_COUNT) return VRT_E_INVALID;
+    if (c->cfg.grid_res == 256) trace_probe_g<256>(c, mode, n, origin_dir, (ProbeOut*)out);
+    else trace_probe_g<128>(c, mode, n, origin_dir, (ProbeOut*)out);
+    return 0;
 }
 // host definition of the two half conversions (include/vrt_detmath.h), for tests that pin numpy's against it
 void emu_half_probe(int op, int n, const uint32_t* in, uint32_t* out) {

@@ -7,6 +7,7 @@
 // cover the context's rows plus a halo (row-tile sharding across GPUs renders the halo rows
 // redundantly instead of exchanging them: per-pixel random streams make them bit-identical).
 #include "vrt_ctx.h"
+#include "vrt_probe.h"
 
 // The row ranges this context produces: one, or with vrt_set_row_stripes its stripes.
 static std::vector<std::pair<int, int>> owned_ranges(const vrt_ctx* c) {
@@ -711,6 +712,26 @@ int vrt_sky_probe(vrt_ctx* c, int op, int n, const float* in, int in_stride, flo
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     hipFree(d_in); hipFree(d_out);
     if (e != hipSuccess) return fail(VRT_E_DEVICE, std::string("sky probe: ") + hipGetErrorString(e));
+    return VRT_OK;
+}
+// Test hook: rays through the closest-hit walk on the context's own pyramid (vrt_probe.h, k_trace_probe).
+int vrt_trace_probe(vrt_ctx* c, int mode, int n, const float* origin_dir, void* out) {
+    if (!c || !origin_dir || !out || n <= 0 || mode < 0 || (mode & ~(3 | PROBE_CULL_BOX)) || (mode & 3) >= PROBE_WALK_COUNT) return fail(VRT_E_INVALID, "bad argument");
+    if (!c->prepared) return fail(VRT_E_STATE, "needs vrt_prepare");
+    if (enter(c) != VRT_OK) return VRT_E_DEVICE;
+    float* d_in = nullptr;
+    ProbeOut* d_out = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_in, (size_t)n * 6 * sizeof(float)));
+    if (hipMalloc((void**)&d_out, (size_t)n * sizeof(ProbeOut)) != hipSuccess) { hipFree(d_in); return fail(VRT_E_DEVICE, "no memory for the probe"); }
+    // with the reference's indexing a ray clear of every solid voxel can still "hit" outside the grid: no box then, as in culling()
+    const float* cull = c->d_cull + ((mode & PROBE_CULL_BOX) && !c->ref_oob ? 0 : 8);
+    hipError_t e = hipMemcpyAsync(d_in, origin_dir, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(ProbeOut), c->stream);
+    if (e == hipSuccess) e = launch_trace_probe(c->stream, c->cfg.grid_res, mode & 3, make_scene_data(c).pyr, cull, n, d_in, d_out);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * sizeof(ProbeOut), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = sync_guarded(c, c->stream);
+    hipFree(d_in); hipFree(d_out);
+    if (e != hipSuccess) return fail(VRT_E_DEVICE, std::string("trace probe: ") + hipGetErrorString(e));
     return VRT_OK;
 }
 // diagnostic builds (-DVRT_DIAG_REGIONS) only: 32 x {wave entries, active lanes} per instrumented code region

@@ -33,6 +33,8 @@
 
 namespace vrt {
 
+struct ProbeOut;   // vrt_probe.h (test hook; vrt_kernels.hip and vrt_api.hip include it)
+
 // grid_res (128 or 256) selects the kernel instantiation everywhere below (GridDim, vrt_types.h)
 hipError_t launch_prepare(hipStream_t st, int grid_res, const int8_t* mat, const uint8_t* rgb, uint32_t* grid, unsigned long long* l0,
                           unsigned long long* l1, unsigned long long* l2, unsigned long long* l3, unsigned long long* l0c, uint32_t* l0c_base,
@@ -64,6 +66,8 @@ hipError_t launch_tonemap(hipStream_t st, const FrameParams& fp, const f3* hdr, 
 hipError_t launch_tonemap8(hipStream_t st, const FrameParams& fp, const f3* hdr, uint32_t* ldr8 /* rgba, 8 bits each */, int r0, int r1);
 hipError_t launch_diag_read(hipStream_t st, unsigned long long* out, int reset);  // -DVRT_DIAG_REGIONS builds only
 hipError_t launch_detmath_probe(hipStream_t st, int op, int n, const float* a, const float* b, float* out);
+// n rays (origin, direction: 6 floats each, voxel units) through walk PROBE_WALK_* against `cull`'s box (vrt_probe.h)
+hipError_t launch_trace_probe(hipStream_t st, int grid_res, int walk, const Pyramid& pyr, const float* cull, int n, const float* rays, ProbeOut* out);
 
 // sky precompute (vrt_sky_kernels.hip)
 struct SkyPrecompute {

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "vrt_kernels.h"
+#include "vrt_probe.h"
 
 namespace vrt {
 
@@ -956,6 +957,19 @@ __global__ void k_detmath_probe(int op, int n, const float* a, const float* b, f
     out[i] = r;
 }
 
+// Test hook (vrt_trace_probe): one ray per lane through the closest-hit walk of the pyramid in global memory (vrt_probe.h).
+template <int G, int WALK>
+__global__ __launch_bounds__(64) void k_trace_probe(Pyramid pyr, const float* cull, int n, const float* rays, ProbeOut* out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    GlobalPyramid<G> P;
+    P.p = pyr;
+    const float* a = rays + (size_t)i * 6;
+    ProbeOut r;
+    probe_ray<G, WALK>(P, mk3(a[0], a[1], a[2]), mk3(a[3], a[4], a[5]), cull, r);
+    out[i] = r;
+}
+
 // ---- host-side launchers -----------------------------------------------------------------------
 #define VRT_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
@@ -1111,6 +1125,15 @@ hipError_t launch_tonemap8(hipStream_t st, const FrameParams& fp, const f3* hdr,
 }
 hipError_t launch_detmath_probe(hipStream_t st, int op, int n, const float* a, const float* b, float* out) {
     hipLaunchKernelGGL(k_detmath_probe, dim3((n + 255) / 256), dim3(256), 0, st, op, n, a, b, out);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_trace_probe(hipStream_t st, int grid_res, int walk, const Pyramid& pyr, const float* cull, int n, const float* rays, ProbeOut* out) {
+    const dim3 g((n + 63) / 64), b(64);
+    if (walk == PROBE_WALK_BRANCHY) VRT_BY_GRID(grid_res, hipLaunchKernelGGL((k_trace_probe<G, PROBE_WALK_BRANCHY>), g, b, 0, st, pyr, cull, n, rays, out));
+    else if (walk == PROBE_WALK_FLAT) VRT_BY_GRID(grid_res, hipLaunchKernelGGL((k_trace_probe<G, PROBE_WALK_FLAT>), g, b, 0, st, pyr, cull, n, rays, out));
+    else if (walk == PROBE_WALK_RECORD) VRT_BY_GRID(grid_res, hipLaunchKernelGGL((k_trace_probe<G, PROBE_WALK_RECORD>), g, b, 0, st, pyr, cull, n, rays, out));
+    else return hipErrorInvalidValue;
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

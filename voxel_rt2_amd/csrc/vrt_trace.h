@@ -276,7 +276,7 @@ VRT_DEV bool cull_ray(const float* cull, f3 o, f3 d, float& t_exit) {
     const f3 a = (mk3(cull[0], cull[1], cull[2]) - o) * inv, b = (mk3(cull[3], cull[4], cull[5]) - o) * inv;
     const float tn = dm_max(dm_max(dm_min(a.x, b.x), dm_min(a.y, b.y)), dm_min(a.z, b.z));
     const float tf = dm_min(dm_min(dm_max(a.x, b.x), dm_max(a.y, b.y)), dm_max(a.z, b.z));
-    if (!(tf >= dm_max(tn, 0.0f))) return false;   // also an empty box (lo > hi: no solids at all) and a NaN
+    if (!(tf >= dm_max(tn, 0.0f))) return false;   // also a NaN.  (NOT the box of a grid without solids, lo = 2^20 - 8 > hi: min / max read it as a huge box, its rays are walked -- and miss)
     t_exit = tf;
     return true;
 }
