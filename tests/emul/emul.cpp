@@ -269,7 +269,7 @@ static int accumulate_g(Emu* c, int n_samples) {
         sc.sky.res = c->cfg.sky_res; sc.sky.fres = c->cfg.sky_res > 0 ? (float)(1.0 / (double)c->cfg.sky_res) : 0.0f;
         sc.counters = nullptr;
         // off by default: the CPU tests compare traversal counters with the oracle's; and off with the reference's indexing, where
-        // a ray clear of every solid voxel can still "hit" outside the grid (vrt_api.hip, culling())
+        // a ray clear of every solid voxel can still "hit" outside the grid (plan_render_variant, vrt_plan.h)
         sc.cull = c->cull + (getenv("VRT_EMU_CULL") && !c->ref_oob ? 0 : 8);
         PixelBuffers out;
         f3* rt = c->cbuf[c->cidx].data();

@@ -17,6 +17,21 @@ void plan_shape(long long items, int heavy, int hw_queues, int can_defer, const 
     const PipelineShape sh = plan_pipeline_shape((size_t)items, heavy != 0, hw_queues, can_defer != 0, k);
     out[0] = sh.n_streams; out[1] = sh.grid_div; out[2] = sh.pass_on_render ? 1 : 0; out[3] = sh.defer_k;
 }
+// in: RenderInputs in declaration order, the booleans as 0 / 1.  Returns the variant as bits, in RenderVariant's order:
+// pooled 1, restir 2, instr 4, cull 8, black_sun 16, dense12 32, share_primary 64.
+int plan_variant(const int* in) {
+    RenderInputs r;
+    r.width = in[0]; r.height = in[1]; r.max_depth = in[2];
+    r.knob_render = in[3]; r.knob_cull = in[4];
+    r.use_restir = in[5] != 0;
+    r.instrumented = in[6] != 0; r.count_as_timed = in[7] != 0;
+    r.ref_oob = in[8] != 0;
+    r.cull_active = in[9] != 0; r.dense_grid = in[10] != 0;
+    r.light_emits = in[11] != 0;
+    r.fused = in[12];
+    const RenderVariant v = plan_render_variant(r);
+    return (v.pooled ? 1 : 0) | (v.restir ? 2 : 0) | (v.instr ? 4 : 0) | (v.cull ? 8 : 0) | (v.black_sun ? 16 : 0) | (v.dense12 ? 32 : 0) | (v.share_primary ? 64 : 0);
+}
 int plan_fused(int left, int can_fuse, int max_fused) { return plan_fused_count(left, can_fuse != 0, max_fused); }
 unsigned plan_period(int time_every, int restir, long long items) { return plan_timer_period(time_every, restir != 0, (size_t)items, Knobs().deep_items); }
 long long plan_deep_items(void) { return Knobs().deep_items; }

@@ -9,6 +9,7 @@ import functools
 import numpy as np
 
 import orc
+import plan
 from voxel_rt2_amd import _abi, camera, host, scenes
 
 BUFS = (_abi.BUF_GBUF_DEPTH, _abi.BUF_GBUF_NORMAL, _abi.BUF_GBUF_POSITION, _abi.BUF_GBUF_MAT, _abi.BUF_GBUF_REFL_DEPTH,
@@ -121,13 +122,20 @@ def check_matrix(session_of, case):
 
 def check_guards(report=print):
     """The oracle's frames alone: the sunlit poses show the scene (so a comparison of black frames cannot pass for coverage).
-    And the inputs on which the launcher picks the twelve-wave dense kernel for `dense` under the pooled schedule (vrt_prepare:
-    at least half of the 4x4x4 bricks hold a voxel; pool_uses_dense12: ReSTIR off and a sun that emits).  The context does not
-    report which kernel a launch took, so this states the conditions, not the choice."""
+    And the `dense` cases take the twelve-wave dense kernel under the pooled schedule: the inputs (vrt_prepare: at least half of the
+    4x4x4 bricks hold a voxel; ReSTIR off and a sun that emits), and the choice the library's own plan_render_variant (vrt_plan.h,
+    compiled for the host) makes on them."""
     mat, _, params = scene("dense")
     G = mat.shape[0]
-    assert (mat > 0).reshape(G // 4, 4, G // 4, 4, G // 4, 4).any(axis=(1, 3, 5)).mean() >= 0.5 and any(c != 0 for c in params["light_color"])
+    dense = (mat > 0).reshape(G // 4, 4, G // 4, 4, G // 4, 4).any(axis=(1, 3, 5)).mean() >= 0.5
+    sp = host.make_scene_params(**params)   # what the sessions are given (orc.setup)
+    emits = any(c != 0 for c in sp.light_color) and sp.light_weight != 0
+    assert dense and any(c != 0 for c in params["light_color"])
     assert not any(restir for name, _, _, restir, _ in CASES if name == "dense")
+    for name, W, H, restir, _ in CASES:
+        if name == "dense":
+            v = plan.variant(width=W, height=H, max_depth=DEPTH, use_restir=restir, dense_grid=dense, light_emits=emits, fused=SPP)
+            assert "dense12" in v and "pooled" in v, v
     for case, (name, W, H, restir, poses) in enumerate(CASES):
         if name != "sunlit":
             continue

@@ -1,45 +1,11 @@
-"""The launch pipeline's decisions (voxel_rt2_amd/csrc/vrt_plan.h: shape, deferral depth, fused sample count, timer period, dispatch
-gate, workgroups, set and lane of a launch) as plain functions, compiled for the host (tests/emul/plan_emul.cpp).  The expected
+"""The launch pipeline's decisions (voxel_rt2_amd/csrc/vrt_plan.h: render kernel variant, shape, deferral depth, fused sample count,
+timer period, dispatch gate, workgroups, set and lane of a launch) as plain functions, compiled for the host (tests/emul/plan_emul.cpp).  The expected
 values are literals: what the library decided before the decisions were lifted out of vrt_accumulate.  No GPU."""
-import ctypes as C
-import os
-import subprocess
+import itertools
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-_SO = os.path.join(HERE, "emul", "_plan_emul.so")
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        src = os.path.join(HERE, "emul", "plan_emul.cpp")
-        deps = [src, os.path.join(ROOT, "voxel_rt2_amd", "csrc", "vrt_plan.h")]
-        if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
-            subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unused-function", "-o", _SO, src],
-                           check=True, capture_output=True)
-        _lib = C.CDLL(_SO)
-        _lib.plan_shape.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        _lib.plan_period.argtypes = [C.c_int, C.c_int, C.c_longlong]
-        _lib.plan_period.restype = C.c_uint
-        _lib.plan_deep_items.restype = C.c_longlong
-        _lib.plan_target.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_int, C.c_uint]
-        _lib.plan_target.restype = C.c_uint
-        _lib.plan_wait.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_int]
-        _lib.plan_set.argtypes = _lib.plan_lane.argtypes = [C.c_uint, C.c_int]
-    return _lib
-
-
-def shape(items, queues, heavy=False, can_defer=True, streams=None, grid_div=None, pass_stream=None, defer4=None, defer8=None):
-    """((n_streams, grid_div), defer_k, pass_on_render)"""
-    knobs = (C.c_int * 5)(*[-100 if v is None else v for v in (streams, grid_div, pass_stream, defer4, defer8)])
-    out = (C.c_int * 4)()
-    lib().plan_shape(items, int(heavy), queues, int(can_defer), knobs, out)
-    return (out[0], out[1]), out[3], bool(out[2])
-
+from plan import lib, shape, variant
 
 P1080 = 1920 * 1080
 DEEP = 12 << 20
@@ -141,3 +107,60 @@ def test_set_and_lane_take_turns():
     assert [L.plan_lane(q, 2) for q in range(5)] == [0, 1, 0, 1, 0]
     assert (L.plan_set(13, 8), L.plan_lane(13, 4)) == (5, 1)
     assert (L.plan_set(2**32 - 1, 12), L.plan_lane(2**32 - 1, 8)) == (3, 7)
+
+
+# the dense random fill: its solids reach every face of the grid (nothing to cull), half its bricks and more hold a voxel, its sun emits
+DENSE_4K = dict(width=3840, height=2160, cull_active=False, dense_grid=True, light_emits=True)
+# what the project runs -> the RenderVariant fields that are set (the kernel follows: vrt_plan.h)
+VARIANTS = [
+    ("bench config 1: S1, 256x256, 1 spp", dict(width=256, height=256, fused=1), {"pooled", "cull", "black_sun"}),                    # k_render_pool<G, 0, 1, 1>
+    ("bench config 2: S1, 1080p, 4 spp", dict(), {"pooled", "cull", "black_sun", "share_primary"}),
+    ("bench config 3: S6, sky + clouds + ReSTIR", dict(use_restir=True, light_emits=True), {"pooled", "restir", "cull", "share_primary"}),   # k_render_pool_restir<G, 0, 1>
+    ("bench config 4: dense 128^3, 4K", DENSE_4K, {"pooled", "dense12", "share_primary"}),                                          # k_render_pool_dense12<G, 0, 0>
+    ("bench config 5: dense 256^3, 4K", DENSE_4K, {"pooled", "dense12", "share_primary"}),                                          # (the grid size picks G, not the variant)
+    ("sunlit, 1 spp", dict(light_emits=True, fused=1), {"pooled", "cull"}),                                                         # k_render_pool<G, 0, 0, 1>
+    ("instrumented: every ray walked, no shared camera rays", dict(instrumented=True), {"pooled", "instr", "black_sun"}),
+    ("instrumented, counting as the timed schedule", dict(instrumented=True, count_as_timed=True), {"pooled", "instr", "cull", "black_sun", "share_primary"}),
+    ("reference indexing", dict(ref_oob=True), {"pooled", "instr", "black_sun"}),
+    ("reference indexing, counting as the timed schedule", dict(ref_oob=True, instrumented=True, count_as_timed=True), {"pooled", "instr", "black_sun", "share_primary"}),
+    ("VRT_RENDER=fused", dict(knob_render=0), {"cull", "black_sun"}),                                                               # k_render<G, 0, 0>
+    ("VRT_RENDER=pool", dict(knob_render=1), {"pooled", "cull", "black_sun", "share_primary"}),
+    ("8192 wide: 12-bit pixel coordinates do not hold it", dict(width=8192, height=1080), {"cull", "black_sun"}),
+    ("4097 high", dict(height=4097), {"cull", "black_sun"}),
+    ("4096 x 4096, depth 15: the largest pooled context", dict(width=4096, height=4096, max_depth=15), {"pooled", "cull", "black_sun", "share_primary"}),
+    ("depth 16: 4 bits do not hold it", dict(max_depth=16), {"cull", "black_sun"}),
+    ("dense on the fused schedule", dict(DENSE_4K, width=8192), set()),
+    ("VRT_CULL=0", dict(knob_cull=0), {"pooled", "black_sun", "share_primary"}),
+    ("VRT_CULL=1 does not force a box the scene has not", dict(knob_cull=1, cull_active=False), {"pooled", "black_sun", "share_primary"}),
+    ("dense grid under a black sun: no shadow rays to speak of", dict(DENSE_4K, light_emits=False), {"pooled", "black_sun", "share_primary"}),
+    ("dense grid with ReSTIR", dict(DENSE_4K, use_restir=True), {"pooled", "restir", "share_primary"}),
+]
+
+
+@pytest.mark.parametrize("inputs,want", [v[1:] for v in VARIANTS], ids=[v[0] for v in VARIANTS])
+def test_render_variant(inputs, want):
+    assert variant(**inputs) == want
+
+
+def test_render_variant_every_combination():
+    """plan_render_variant against its rules restated here, over every combination of the boolean inputs, at sizes on both sides of
+    each limit of the pooled kernel, every value of the two switches and fused counts on both sides of 1."""
+    sizes = [(64, 40, 5), (4096, 4096, 15), (4097, 40, 5), (64, 4097, 5), (64, 40, 16)]
+    n = 0
+    for (W, H, depth), render, cull_knob, fused in itertools.product(sizes, (-2, -1, 0, 1), (-1, 0, 1), (1, 2, 4)):
+        for restir, instrumented, timed, oob, cull_active, dense, emits in itertools.product((False, True), repeat=7):
+            pooled = W <= 4096 and H <= 4096 and depth <= 15 and render != 0
+            instr = instrumented or oob
+            want = {
+                "pooled": pooled,
+                "restir": restir,
+                "instr": instr,
+                "cull": cull_active and not (instrumented and not timed) and not oob and cull_knob != 0,
+                "black_sun": not emits,
+                "dense12": pooled and not restir and dense and emits,
+                "share_primary": pooled and fused > 1 and (not instr or timed),
+            }
+            got = variant(W, H, depth, render, cull_knob, restir, instrumented, timed, oob, cull_active, dense, emits, fused)
+            assert got == {k for k, on in want.items() if on}, (W, H, depth, render, cull_knob, fused, restir, instrumented, timed, oob, cull_active, dense, emits)
+            n += 1
+    assert n == 5 * 4 * 3 * 3 * 2 ** 7

@@ -64,13 +64,14 @@ static FrameParams make_frame_params(const vrt_ctx* c) {
     }
     return fp;
 }
-// launches that count the reference's work walk every ray, as the reference and the oracle do; VRT_CULL=0 for A/B runs
-static bool culling(const vrt_ctx* c) {
-    // with the reference's indexing a ray clear of every solid voxel can still "hit" outside the grid: every ray is walked
-    bool cull = c->cull_active && !(c->instrumented && !c->count_as_timed) && !c->ref_oob;
-    if (c->knobs.cull == 0) cull = false;
-    return cull;
+// What plan_render_variant (vrt_plan.h) decides on, as the context stands, for a launch of `fused` samples.
+static RenderInputs render_inputs(const vrt_ctx* c, int fused) {
+    const float* lc = c->scene.light_color;
+    const bool emits = (lc[0] != 0.0f || lc[1] != 0.0f || lc[2] != 0.0f) && c->scene.light_weight != 0.0f;
+    return RenderInputs{c->cfg.width, c->cfg.height, c->cfg.max_depth, c->knobs.render, c->knobs.cull, c->cfg.use_restir != 0,
+                        c->instrumented, c->count_as_timed, c->ref_oob, c->cull_active, c->dense_grid, emits, fused};
 }
+static RenderVariant render_variant(const vrt_ctx* c, int fused) { return plan_render_variant(render_inputs(c, fused)); }
 static SceneData make_scene_data(const vrt_ctx* c) {
     SceneData sc;
     sc.pyr.l0 = c->d_l0; sc.pyr.l1 = c->d_l1; sc.pyr.l2 = c->d_l2; sc.pyr.l3 = c->d_l3;
@@ -83,7 +84,7 @@ static SceneData make_scene_data(const vrt_ctx* c) {
     sc.sky.res = c->cfg.sky_res;
     sc.sky.fres = c->cfg.sky_res > 0 ? (float)(1.0 / (double)c->cfg.sky_res) : 0.0f;
     sc.counters = c->d_counters;
-    sc.cull = c->d_cull + (culling(c) ? 0 : 8);
+    sc.cull = c->d_cull + (render_variant(c, 1).cull ? 0 : 8);   // (cull does not depend on the fused count)
     return sc;
 }
 static SkyPrecompute make_sky(const vrt_ctx* c) {
@@ -723,8 +724,10 @@ int vrt_trace_probe(vrt_ctx* c, int mode, int n, const float* origin_dir, void* 
     ProbeOut* d_out = nullptr;
     HIP_TRY(hipMalloc((void**)&d_in, (size_t)n * 6 * sizeof(float)));
     if (hipMalloc((void**)&d_out, (size_t)n * sizeof(ProbeOut)) != hipSuccess) { hipFree(d_in); return fail(VRT_E_DEVICE, "no memory for the probe"); }
-    // with the reference's indexing a ray clear of every solid voxel can still "hit" outside the grid: no box then, as in culling()
-    const float* cull = c->d_cull + ((mode & PROBE_CULL_BOX) && !c->ref_oob ? 0 : 8);
+    // cull = (mode & PROBE_CULL_BOX) && !ref_oob: the MODE asks for the box (cull_active), whatever the counters (instrumented) and VRT_CULL say
+    RenderInputs in = render_inputs(c, 1);
+    in.cull_active = (mode & PROBE_CULL_BOX) != 0; in.instrumented = false; in.knob_cull = -1;
+    const float* cull = c->d_cull + (plan_render_variant(in).cull ? 0 : 8);
     hipError_t e = hipMemcpyAsync(d_in, origin_dir, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, (size_t)n * sizeof(ProbeOut), c->stream);
     if (e == hipSuccess) e = launch_trace_probe(c->stream, c->cfg.grid_res, mode & 3, make_scene_data(c).pyr, cull, n, d_in, d_out);

@@ -96,9 +96,9 @@ struct vrt_ctx {
     bool owns_stream = true;
     std::vector<void*> device_allocs; // every device buffer the context owns (dalloc, dmalloc): what vrt_destroy frees
     int n_cu = 0, render_blocks = 0;
-    int render_blocks_d12 = 0;        // ... of the twelve-wave geometry a dense 128^3 grid renders on (k_render_pool_dense12)
+    int render_blocks_d12 = 0;        // ... of the twelve-wave geometry a dense grid renders on (k_render_pool_dense12; 0: never taken)
+    size_t pool_scratch_bytes = 0;    // a lane's scratch: room for either geometry
     int reserved_cus = 0;             // CUs' worth of workgroup slots the persistent render grid leaves free (vrt_reserve_cus)
-    bool pooled = false;              // render through k_render_pool (vrt_pool.h) instead of k_render
     // rows
     int own0 = 0, own1 = 0;   // rows this context produces
     int stripe_rows = 0, stripe_parts = 0, stripe_part = 0;   // ... or, of them, every stripe_parts-th stripe of stripe_rows rows (vrt_set_row_stripes)

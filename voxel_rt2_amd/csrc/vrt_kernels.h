@@ -11,6 +11,7 @@
 #include "vrt_pool.h"
 #include "vrt_restir.h"
 #include "vrt_temporal.h"
+#include "vrt_plan.h"
 
 #define VRT_RENDER_THREADS 256
 #ifndef VRT_RENDER_MIN_WAVES
@@ -42,19 +43,13 @@ hipError_t launch_prepare(hipStream_t st, int grid_res, const int8_t* mat, const
 hipError_t query_render_residency(int grid_res, bool restir, bool instr, int* blocks_per_cu);
 hipError_t launch_render(hipStream_t st, int grid_res, bool restir, bool instr, int n_blocks, const FrameParams& fp, const SceneData& sc,
                          const PixelBuffers& out, unsigned* work_counters, unsigned launch_seq, int n_samples, int chunk_override);
-// pooled schedule (vrt_pool.h).  `cold` holds pool_scratch_bytes(grid_res, restir, n_blocks) bytes.
-hipError_t query_render_pool_residency(int grid_res, bool restir, bool instr, int* blocks_per_cu);
-int pool_waves_per_block(int grid_res);
-size_t pool_scratch_bytes(int grid_res, bool restir, int n_blocks, int n_blocks_dense12);
-hipError_t query_render_pool_dense12_residency(int grid_res, bool instr, int* blocks_per_cu);
-bool pool_uses_dense12(int grid_res, bool restir, bool dense, const FrameParams& fp);
-hipError_t launch_render_pool(hipStream_t st, int grid_res, bool restir, bool instr, int n_blocks, const FrameParams& fp, const SceneData& sc,
+// pooled schedule (vrt_pool.h).  `v` (plan_render_variant, vrt_plan.h) picks the kernel and with it the workgroup geometry: the query
+// answers for the kernel a launch with the same `v` runs.  `cold` holds n_blocks x scratch_per_block bytes at least.
+hipError_t query_render_pool(int grid_res, const RenderVariant& v, int* blocks_per_cu, size_t* scratch_per_block);
+hipError_t launch_render_pool(hipStream_t st, int grid_res, const RenderVariant& v, int n_blocks, const FrameParams& fp, const SceneData& sc,
                               const PixelBuffers& out, unsigned* work_counters, unsigned launch_seq, int n_samples, uint32_t* cold,
                               uint32_t* drain_signal,   // signal memory (or null): receives launch_seq + 1 when the launch starts to drain
-                              PrimaryRecord* prim_cache,        // per-pixel camera-ray records shared by the fused samples (or null), npix entries
-                              bool cull,                        // the instantiation that tests rays against sc.cull (cull_ray, vrt_trace.h)
-                              bool dense,                       // ... whose SHADE walks its shadow rays with the branchy descent (dense grids)
-                              bool dense12);                    // ... on the twelve-wave geometry (pool_uses_dense12; n_blocks counts ITS workgroups)
+                              PrimaryRecord* prim_cache);       // per-pixel camera-ray records shared by the fused samples (or null), npix entries
 hipError_t launch_mat_derived(hipStream_t st, const float* mats, float* mats_x /*[128][8]*/);  // after every material upload
 // spatial reuse over rows [r0, r1); first a per-pixel prepare pass over all rows the launch holds (fp.row0..fp.row1) into gb.geo / gb.src
 hipError_t launch_gris(hipStream_t st, int grid_res, bool instr, const FrameParams& fp, const SceneData& sc, const GrisBuffers& gb, int r0, int r1);

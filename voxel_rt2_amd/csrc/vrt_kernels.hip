@@ -2,9 +2,9 @@
 //
 //   k_pack_grid / k_build_l0 / k_build_coarse / k_build_l0c   prepare_data: packed voxel texels, the bit-brick
 //                                                         occupancy pyramid and its compacted fine level
-//   k_render_pool<INSTR>                                  persistent wave64 path tracer, pooled schedule (vrt_pool.h):
-//                                                         a wave owns 128 path records in LDS and runs them stage by
-//                                                         stage (WALK / SHADE / ESCAPE / BEGIN); default without ReSTIR
+//   k_render_pool / _restir / _dense12                    persistent wave64 path tracer, pooled schedule (vrt_pool.h): a wave owns a
+//                                                         pool of path records in LDS and runs them stage by stage (WALK / SHADE /
+//                                                         ESCAPE / BEGIN); the default.  Which of them: plan_render_variant, pool_kernel()
 //   k_render<RESTIR, INSTR>                               persistent wave64 path tracer, one path per lane (vrt_path.h)
 //   k_gris_prepare / k_gris                               ReSTIR spatial reuse: per-pixel records (decoded sample, shading
 //                                                         basis), then 32 taps x 2 reconnection shifts per pixel
@@ -216,12 +216,14 @@ struct LdsPyramid2<256, CULL_, SHBR_, OOB_> {
         base = 0u;
     }
 };
-template <int G> struct PoolGeom { static constexpr int waves = VRT_POOL_WAVES; };   // waves (= path pools) per workgroup
-template <> struct PoolGeom<256> { static constexpr int waves = 8; };
 #ifndef VRT_POOL_SLOTS_128
 #define VRT_POOL_SLOTS_128 VRT_POOL_SLOTS   // (experiments: another pool size at 128^3 only -- the 256^3 workgroup has no LDS to spare)
 #endif
-template <int G> struct PoolSlots { static constexpr int value = G == 256 ? VRT_POOL_SLOTS : VRT_POOL_SLOTS_128; };
+// The pooled kernels' two workgroup geometries (render_pool_body): waves (= path pools) per workgroup, slots per pool.
+struct PoolShape { int waves, slots; };
+template <int G> constexpr PoolShape pool_shape(bool twelve) {
+    return twelve ? PoolShape{12, G == 256 ? 88 : 96} : PoolShape{G == 256 ? 8 : VRT_POOL_WAVES, G == 256 ? VRT_POOL_SLOTS : VRT_POOL_SLOTS_128};
+}
 
 __device__ __forceinline__ void flush_stats(const TraceStats& ts, Counters* c) {
     // wave-level sum, one atomic per counter per wave
@@ -347,7 +349,7 @@ __device__ __forceinline__ int lane_rank(unsigned long long m) {  // set bits of
 // WAVES path pools of SLOTS slots per workgroup: 4 x 128 with two workgroups per CU (two waves per SIMD) by default; the whole l1
 // level of a 256^3 grid leaves room for one workgroup of 8 x 128 per CU; a DENSE 128^3 grid runs one workgroup of 12 x 96 per CU
 // -- three waves per SIMD at 168 registers (k_render_pool_dense12 below).
-template <int G, bool RESTIR, bool INSTR, bool BLACK_SUN, bool CULL, bool SHBR = false, int WAVES = PoolGeom<G>::waves, int SLOTS = PoolSlots<G>::value>
+template <int G, bool RESTIR, bool INSTR, bool BLACK_SUN, bool CULL, bool D12 = false>   // D12: twelve waves, and SHADE's shadow rays with the branchy descent
 // 208 registers per wave (the attribute counts half of the unified file): two waves per SIMD then leave the 96 that
 // k_temporal runs in beside them (see there).  The allocator would take 238; the cap costs 28 bytes of scratch.
 // The ReSTIR instantiation (no overlapped launches, so nothing runs beside it) takes the two-wave maximum of 256.
@@ -355,6 +357,7 @@ template <int G, bool RESTIR, bool INSTR, bool BLACK_SUN, bool CULL, bool SHBR =
 #define VRT_POOL_HALF_VGPRS 104
 #endif
 __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const SceneData& sc, const PixelBuffers& out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache) {
+    constexpr int WAVES = pool_shape<G>(D12).waves, SLOTS = pool_shape<G>(D12).slots;
     constexpr int WORDS = (SLOTS + 63) / 64;
     constexpr bool BIG = (G == 256);   // which coarse levels are staged how: see LdsPyramid2
     __shared__ ulonglong2 s_l12[BIG ? 1 : 512];
@@ -367,7 +370,7 @@ __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const Sc
     __shared__ uint32_t s_pool[WAVES][PF_COUNT * SLOTS];
     __shared__ uint32_t s_state[WAVES][WORDS * 64];
     __shared__ uint32_t s_list[WAVES][SLOTS];
-    LdsPyramid2<G, CULL, SHBR, INSTR> P;
+    LdsPyramid2<G, CULL, D12, INSTR> P;
     P.l0 = sc.pyr.l0; P.l2 = s_l2;
     P.oob = sc.pyr.ref_oob != 0;
     if constexpr (BIG) {
@@ -630,32 +633,22 @@ __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const Sc
 }
 // (the register attribute takes a literal, hence one kernel per budget around the shared body)
 template <int G, bool INSTR, bool BLACK_SUN, bool CULL>
-__global__ __launch_bounds__(64 * PoolGeom<G>::waves, VRT_POOL_MIN_WAVES) __attribute__((amdgpu_num_vgpr(VRT_POOL_HALF_VGPRS))) void k_render_pool(FrameParams fp, SceneData sc, PixelBuffers out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache) {
+__global__ __launch_bounds__(64 * pool_shape<G>(false).waves, VRT_POOL_MIN_WAVES) __attribute__((amdgpu_num_vgpr(VRT_POOL_HALF_VGPRS))) void k_render_pool(FrameParams fp, SceneData sc, PixelBuffers out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache) {
     render_pool_body<G, false, INSTR, BLACK_SUN, CULL>(fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, drain_value, prim_cache);
 }
-// a dense grid under an emitting sun: the shadow rays of SHADE with the branchy descent (shadow_branchy_of, vrt_trace.h)
-template <int G, bool INSTR, bool CULL>
-__global__ __launch_bounds__(64 * PoolGeom<G>::waves, VRT_POOL_MIN_WAVES) __attribute__((amdgpu_num_vgpr(VRT_POOL_HALF_VGPRS))) void k_render_pool_dense(FrameParams fp, SceneData sc, PixelBuffers out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache) {
-    render_pool_body<G, false, INSTR, false, CULL, true>(fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, drain_value, prim_cache);
-}
-// ... and at 128^3 the same with THREE waves per SIMD: one workgroup of twelve waves per CU, 96 slots per pool (12 x 10.4 KB of pools
+// A DENSE grid under an emitting sun: the shadow rays of SHADE with the branchy descent (shadow_branchy_of, vrt_trace.h), and
+// THREE waves per SIMD: one workgroup of twelve waves per CU, 96 slots per pool (12 x 10.4 KB of pools
 // + 25 KB of pyramid and materials = 148 KB of LDS), 168 registers (21-36 spilled).  A dense grid's rays end after a step or two, so
 // its waves spend their time in SHADE waiting on texel and shadow-ray loads, which a third wave covers: the dense 4K frame
 // 2 673 -> 2 953 Mpath-samples/s.  A sparse scene loses as much with it (config 2 -3.6 %, sun-lit -6 %: fewer slots per pool
-// thin the WALK stage out, and the spills cost), so only launches the dense variant would take anyway use it.
+// thin the WALK stage out, and the spills cost), so only launches over a dense grid under an emitting sun use it.
 // At 256^3 the staged l1 level (32 KB) leaves the twelve pools 88 slots each (153 KB of LDS in all).
-#define VRT_D12_WAVES 12
-#define VRT_D12_SLOTS 96
-#ifndef VRT_D12_SLOTS_256
-#define VRT_D12_SLOTS_256 88
-#endif
-template <int G> struct D12Slots { static constexpr int value = G == 256 ? VRT_D12_SLOTS_256 : VRT_D12_SLOTS; };
 template <int G, bool INSTR, bool CULL>
-__global__ __launch_bounds__(64 * VRT_D12_WAVES, 3) __attribute__((amdgpu_num_vgpr(84))) void k_render_pool_dense12(FrameParams fp, SceneData sc, PixelBuffers out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache) {
-    render_pool_body<G, false, INSTR, false, CULL, true, VRT_D12_WAVES, D12Slots<G>::value>(fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, drain_value, prim_cache);
+__global__ __launch_bounds__(64 * pool_shape<G>(true).waves, 3) __attribute__((amdgpu_num_vgpr(84))) void k_render_pool_dense12(FrameParams fp, SceneData sc, PixelBuffers out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache) {
+    render_pool_body<G, false, INSTR, false, CULL, true>(fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, drain_value, prim_cache);
 }
 template <int G, bool INSTR, bool CULL>
-__global__ __launch_bounds__(64 * PoolGeom<G>::waves, VRT_POOL_MIN_WAVES) __attribute__((amdgpu_num_vgpr(128))) void k_render_pool_restir(FrameParams fp, SceneData sc, PixelBuffers out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache) {
+__global__ __launch_bounds__(64 * pool_shape<G>(false).waves, VRT_POOL_MIN_WAVES) __attribute__((amdgpu_num_vgpr(128))) void k_render_pool_restir(FrameParams fp, SceneData sc, PixelBuffers out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache) {
     render_pool_body<G, true, INSTR, false, CULL>(fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, drain_value, prim_cache);
 }
 
@@ -1024,54 +1017,34 @@ hipError_t launch_render(hipStream_t st, int grid_res, bool restir, bool instr, 
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }
-int pool_waves_per_block(int grid_res) { return grid_res == 256 ? PoolGeom<256>::waves : PoolGeom<128>::waves; }
-hipError_t query_render_pool_dense12_residency(int grid_res, bool instr, int* blocks_per_cu) {
-    hipError_t e = hipSuccess;
-    VRT_BY_GRID(grid_res, VRT_BY_2(instr, false, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_render_pool_dense12<G, A, true>, 64 * VRT_D12_WAVES, 0)));
-    return e;
+// The ONE place a pooled launch's variant (plan_render_variant, vrt_plan.h) becomes a kernel and its geometry: block size, residency,
+// scratch size.  (restir: the reservoir needs the light sample whatever the sun's colour.)
+typedef void (*pool_kernel_fn)(FrameParams, SceneData, PixelBuffers, unsigned*, unsigned*, int, uint32_t*, uint32_t*, uint32_t, PrimaryRecord*);
+struct PoolKernel { pool_kernel_fn fn; PoolShape shape; };
+static PoolKernel pool_kernel(int grid_res, const RenderVariant& v) {
+    PoolKernel k{nullptr, {0, 0}};
+    VRT_BY_GRID(grid_res, VRT_BY_2(v.instr, v.cull,
+        k = (v.restir ? PoolKernel{k_render_pool_restir<G, A, B>, pool_shape<G>(false)}
+           : v.dense12 ? PoolKernel{k_render_pool_dense12<G, A, B>, pool_shape<G>(true)}
+           : v.black_sun ? PoolKernel{k_render_pool<G, A, true, B>, pool_shape<G>(false)}
+                         : PoolKernel{k_render_pool<G, A, false, B>, pool_shape<G>(false)})));
+    return k;
 }
-hipError_t query_render_pool_residency(int grid_res, bool restir, bool instr, int* blocks_per_cu) {
-    hipError_t e = hipSuccess;
-    if (restir) VRT_BY_GRID(grid_res, VRT_BY_2(instr, false, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_render_pool_restir<G, A, true>, 64 * PoolGeom<G>::waves, 0)));
-    else VRT_BY_GRID(grid_res, VRT_BY_2(instr, false, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_render_pool<G, A, B, true>, 64 * PoolGeom<G>::waves, 0)));
-    return e;
+hipError_t query_render_pool(int grid_res, const RenderVariant& v, int* blocks_per_cu, size_t* scratch_per_block) {
+    const PoolKernel k = pool_kernel(grid_res, v);
+    *scratch_per_block = (size_t)k.shape.waves * k.shape.slots * (v.restir ? ColdLine<true>::count : ColdLine<false>::count) * sizeof(uint32_t);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k.fn, 64 * k.shape.waves, 0);
 }
-size_t pool_scratch_bytes(int grid_res, bool restir, int n_blocks, int n_blocks_dense12) {   // room for either geometry
-    const size_t line = (size_t)(restir ? ColdLine<true>::count : ColdLine<false>::count) * sizeof(uint32_t);
-    const size_t a = (size_t)n_blocks * pool_waves_per_block(grid_res) * (grid_res == 256 ? PoolSlots<256>::value : PoolSlots<128>::value) * line;
-    const size_t b = (size_t)n_blocks_dense12 * VRT_D12_WAVES * VRT_D12_SLOTS * line;
-    return a > b ? a : b;
-}
-hipError_t launch_render_pool(hipStream_t st, int grid_res, bool restir, bool instr, int n_blocks, const FrameParams& fp, const SceneData& sc,
+hipError_t launch_render_pool(hipStream_t st, int grid_res, const RenderVariant& v, int n_blocks, const FrameParams& fp, const SceneData& sc,
                               const PixelBuffers& out, unsigned* work_counters, unsigned launch_seq, int n_samples, uint32_t* cold,
-                              uint32_t* drain_signal, PrimaryRecord* prim_cache, bool cull, bool dense, bool dense12) {
+                              uint32_t* drain_signal, PrimaryRecord* prim_cache) {
     unsigned* work_counter = work_counters + (launch_seq & 15u) * (VRT_WORK_HEADS * VRT_WORK_HEAD_STRIDE);
     unsigned* next_counter = work_counters + ((launch_seq + 8u) & 15u) * (VRT_WORK_HEADS * VRT_WORK_HEAD_STRIDE);
-    dim3 g(n_blocks), b(64 * (dense12 ? VRT_D12_WAVES : pool_waves_per_block(grid_res)));
+    const PoolKernel k = pool_kernel(grid_res, v);
     // the signal carries launch_seq + 1 of the latest launch that has begun to drain
-    // the black-sun variant (scene.py's default light) compiles the light sample out of the shading stage
-    const bool black_sun = !((fp.light_color.x != 0.0f || fp.light_color.y != 0.0f || fp.light_color.z != 0.0f) && fp.light_weight != 0.0f);
-#define VRT_POOL_ARGS g, b, 0, st, fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, launch_seq + 1u, prim_cache
-    if (restir) {  // the reservoir needs the light sample whatever the sun's colour
-        if (cull) VRT_BY_GRID(grid_res, VRT_BY_2(instr, false, hipLaunchKernelGGL((k_render_pool_restir<G, A, true>), VRT_POOL_ARGS)));
-        else VRT_BY_GRID(grid_res, VRT_BY_2(instr, false, hipLaunchKernelGGL((k_render_pool_restir<G, A, false>), VRT_POOL_ARGS)));
-    } else if (dense12) {               // (the caller's choice: pool_uses_dense12)
-        VRT_BY_GRID(grid_res, VRT_BY_2(instr, cull, hipLaunchKernelGGL((k_render_pool_dense12<G, A, B>), VRT_POOL_ARGS)));
-    } else if (dense && !black_sun) {   // (with a black sun SHADE walks next to no shadow rays)
-        VRT_BY_GRID(grid_res, VRT_BY_2(instr, cull, hipLaunchKernelGGL((k_render_pool_dense<G, A, B>), VRT_POOL_ARGS)));
-    } else {
-        if (cull) VRT_BY_GRID(grid_res, VRT_BY_2(instr, black_sun, hipLaunchKernelGGL((k_render_pool<G, A, B, true>), VRT_POOL_ARGS)));
-        else VRT_BY_GRID(grid_res, VRT_BY_2(instr, black_sun, hipLaunchKernelGGL((k_render_pool<G, A, B, false>), VRT_POOL_ARGS)));
-    }
-#undef VRT_POOL_ARGS
+    hipLaunchKernelGGL(k.fn, dim3(n_blocks), dim3(64 * k.shape.waves), 0, st, fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, launch_seq + 1u, prim_cache);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
-}
-// the launches that take the twelve-wave geometry: the ones the dense variant takes at 128^3
-bool pool_uses_dense12(int grid_res, bool restir, bool dense, const FrameParams& fp) {
-    const bool black_sun = !((fp.light_color.x != 0.0f || fp.light_color.y != 0.0f || fp.light_color.z != 0.0f) && fp.light_weight != 0.0f);
-    (void)grid_res;
-    return !restir && dense && !black_sun;
 }
 hipError_t launch_mat_derived(hipStream_t st, const float* mats, float* mats_x) {
     hipLaunchKernelGGL(k_mat_derived, dim3(1), dim3(128), 0, st, mats, mats_x);

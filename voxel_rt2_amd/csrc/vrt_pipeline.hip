@@ -65,8 +65,6 @@ static bool gate_self_test(vrt_ctx* c) {
     return by_itself;
 }
 
-static size_t pool_scratch_size(const vrt_ctx* c) { return pool_scratch_bytes(c->cfg.grid_res, c->cfg.use_restir != 0, c->render_blocks, c->render_blocks_d12); }
-
 // Streams, copies and events for a pipeline `want` launches deep (what a shallower one already has is kept; every buffer is
 // looked at by itself, so an attempt that failed half way is completed, not allocated over).
 static bool grow_pipeline(vrt_ctx* c, int want, int want_sets) {
@@ -81,7 +79,7 @@ static bool grow_pipeline(vrt_ctx* c, int want, int want_sets) {
     for (int s = 0; s < want && ok; s++) {   // stream s and, beyond the first, a pool scratch of its own
         Lane& l = c->lanes[s];
         if (l.stream) continue;
-        ok = (s == 0 || l.pool_scratch || dmalloc(c, &l.pool_scratch, pool_scratch_size(c)) == hipSuccess) &&
+        ok = (s == 0 || l.pool_scratch || dmalloc(c, &l.pool_scratch, c->pool_scratch_bytes) == hipSuccess) &&
              hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking) == hipSuccess;
     }
     for (int s = 0; s < want_sets && ok; s++) {
@@ -271,43 +269,40 @@ static void capture_slice(vrt_ctx* c, const FrameParams& fp, const PixelBuffers&
 
 // ---- vrt_accumulate, step by step --------------------------------------------------------------------------------------------
 static bool restir_on(const vrt_ctx* c) { return c->cfg.use_restir != 0; }
-// (the instrumented instantiations are the ones that carry the reference's out-of-grid reading: vrt_set_reference_indexing)
-static bool instr_on(const vrt_ctx* c) { return c->instrumented || c->ref_oob; }
 
 // The persistent render grid and its scratch, after anything that changes the kernel's residency (render_blocks == 0).
 static int size_render_grid(vrt_ctx* c) {
-    const bool restir = restir_on(c), instr = instr_on(c);
     if (flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;   // (the scratch below is freed behind the context's stream)
-    // Two schedules of the same per-path code: the fused one (a lane owns a path, vrt_path.h) and the pooled one
-    // (a wave owns a pool of paths in LDS and works stage by stage, vrt_pool.h).  The pooled kernel packs pixel
-    // coordinates in 12 bits and the depth in 4, so contexts outside that use the fused one (ReSTIR runs on either:
-    // k_render_pool_restir keeps the reconnection state in the per-slot scratch line).  VRT_RENDER=fused selects the
-    // fused kernel everywhere (A/B measurements, tests).
-    bool pooled = c->cfg.width <= 4096 && c->cfg.height <= 4096 && c->cfg.max_depth <= 15;
+    // Two schedules of the same per-path code: the fused one (a lane owns a path, vrt_path.h) and the pooled one (a wave owns a pool of paths in LDS and
+    // works stage by stage, vrt_pool.h).  A pooled context is sized for BOTH its workgroup geometries: grid and light change without coming here.
+    // (Nor do the answers depend on the cull / black-sun sibling it is in now: launch bounds and LDS are the siblings', the register attribute holds
+    // all of them to two waves per SIMD -- three on the twelve-wave geometry.)  Two query keys, not a launch's choice:
+    const auto on = [c](bool d12) { RenderVariant k = render_variant(c, 1); k.dense12 = d12; return k; };
+    const RenderVariant v = on(false), v_d12 = on(true);
     if (c->knobs.render == -2) return fail(VRT_E_INVALID, "VRT_RENDER must be 'fused' or 'pool'");
-    if (c->knobs.render == 0) pooled = false;
     int per_cu = 0;
-    if (pooled) HIP_TRY(query_render_pool_residency(c->cfg.grid_res, restir, instr, &per_cu));
-    else HIP_TRY(query_render_residency(c->cfg.grid_res, restir, instr, &per_cu));
+    size_t per_block = 0, per_block12 = 0;   // scratch bytes
+    if (v.pooled) HIP_TRY(query_render_pool(c->cfg.grid_res, v, &per_cu, &per_block));
+    else HIP_TRY(query_render_residency(c->cfg.grid_res, v.restir, v.instr, &per_cu));
     if (per_cu < 1) per_cu = 1;
     if (per_cu > 8) per_cu = 8;
     int cus = c->n_cu - c->reserved_cus;
     if (cus < 8) cus = c->n_cu < 8 ? c->n_cu : 8;
     c->render_blocks = per_cu * cus;   // (abort_pipeline zeroes it again if an allocation below fails)
     c->render_blocks_d12 = 0;
-    if (pooled && !restir) {
+    if (v.pooled && !v.restir) {   // the contexts whose launches take the twelve-wave geometry once grid and light call for it
         int per_cu12 = 0;
-        HIP_TRY(query_render_pool_dense12_residency(c->cfg.grid_res, instr, &per_cu12));
+        HIP_TRY(query_render_pool(c->cfg.grid_res, v_d12, &per_cu12, &per_block12));
         c->render_blocks_d12 = (per_cu12 < 1 ? 1 : per_cu12) * cus;
     }
-    c->pooled = pooled;
-    if (!pooled) return VRT_OK;
+    c->pool_scratch_bytes = std::max(c->render_blocks * per_block, c->render_blocks_d12 * per_block12);
+    if (!v.pooled) return VRT_OK;
     HIP_TRY(sync_guarded(c, c->stream));
     for (int s = 0; s < VRT_MAX_STREAMS; s++) {   // lane 0's, then that of every other stream the pipeline has, whatever the depth in use
         Lane& l = c->lanes[s];
         if (s > 0 && !(c->overlap_ready && l.stream)) continue;
         HIP_TRY(dfree(c, &l.pool_scratch));
-        HIP_TRY(dmalloc(c, &l.pool_scratch, pool_scratch_size(c)));
+        HIP_TRY(dmalloc(c, &l.pool_scratch, c->pool_scratch_bytes));
     }
     return VRT_OK;
 }
@@ -390,7 +385,7 @@ static int queue_sample_pass(vrt_ctx* c, const FrameParams& fp, const SceneData&
         gb.geo = c->d_gris_geo; gb.src = c->d_gris_src; gb.tst = c->d_gris_tst; gb.mats_x = c->d_mats_x;
         int g0 = c->own0 - 2 < c->buf0 ? c->buf0 : c->own0 - 2, g1 = c->own1 + 2 > c->buf1 ? c->buf1 : c->own1 + 2;
         if (timer_begin(c, &t, timed, 2, c->stream) != VRT_OK) return VRT_E_DEVICE;
-        HIP_TRY(launch_gris(c->stream, c->cfg.grid_res, instr_on(c), fps, sc, gb, g0, g1));
+        HIP_TRY(launch_gris(c->stream, c->cfg.grid_res, render_variant(c, g).instr, fps, sc, gb, g0, g1));
         c->passes_n[2]++;
         if (timer_end(t) != VRT_OK) return VRT_E_DEVICE;
         cd = c->d_color_d2;
@@ -443,7 +438,7 @@ static void commit_rotation(vrt_ctx* c, int set, bool overlapped, int hist, int 
 }
 
 static int accumulate_impl(vrt_ctx* c, int n_samples) {
-    const bool restir = restir_on(c), instr = instr_on(c);
+    const bool restir = restir_on(c), pooled = render_variant(c, 1).pooled;   // (neither changes in a context's life)
     if (c->render_blocks == 0) {
         const int rc = size_render_grid(c);
         if (rc != VRT_OK) return rc;
@@ -455,7 +450,7 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
     // With ReSTIR on the samples fuse in the RENDER launch all the same (one reservoir plane per sample beside the colour
     // planes; the pooled kernel only): spatial reuse and accumulation then run sample by sample over the planes, as the
     // reference runs them -- the reuse pass of a sample reads nothing an earlier sample's pass wrote.  VRT_FUSE_RESTIR=0: off.
-    const bool fuse_restir = c->pooled && c->knobs.fuse_restir;
+    const bool fuse_restir = pooled && c->knobs.fuse_restir;
     const bool can_fuse = (!restir || fuse_restir) && c->cam.camera_is_moving == 0 && c->cam.render_scale == 1.0f;
     // A persistent render launch ends in a tail: the last paths of every wave bounce on at low occupancy (about 0.16 ms
     // of a 1.5 ms launch at 1080p).  Fused launches of the pooled kernel are therefore OVERLAPPED: launch k+1 goes to
@@ -463,7 +458,7 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
     // and its temporal pass (main stream, waits for launch k only) runs.  With n_streams + 1 copies launch k+n_streams+1
     // reuses launch k's and waits for temporal pass k, so render launches follow each other without a gap and the temporal
     // passes run beside them (ensure_overlap: how deep).  Results are unchanged; VRT_OVERLAP=0 turns it off.
-    const bool may_overlap = c->pooled && can_fuse && !restir && c->knobs.overlap;
+    const bool may_overlap = pooled && can_fuse && !restir && c->knobs.overlap;
     for (int done = 0; done < n_samples;) {
         int g = plan_fused_count(n_samples - done, can_fuse, c->knobs.max_fused);
         // One-sample launches are pipelined like fused ones (the reference's own loop is one sample per call: scene.py:177,
@@ -474,8 +469,8 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
         }
         const size_t items = (size_t)c->cfg.width * owned_rows(c) * (size_t)g;   // work items of the launch
         const FrameParams fp = make_frame_params(c);
-        const bool d12 = c->pooled && c->render_blocks_d12 > 0 && pool_uses_dense12(c->cfg.grid_res, restir, c->dense_grid, fp);
-        const bool overlapped = want_overlap && ensure_overlap(c, items, d12);
+        const RenderVariant v = render_variant(c, g);   // which kernel this launch takes
+        const bool overlapped = want_overlap && ensure_overlap(c, items, v.dense12);
         const bool planes = g > 1 || overlapped;   // the launch writes colour planes of its own, not the HDR buffer
         // Its accumulation is deferred to a pass over defer_k launches (flush_deferred); a launch that is not deferred comes
         // behind the passes of those that were.
@@ -510,18 +505,18 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
         // test hook (tests/test_gpu_pipeline.py): launch number VRT_TEST_FAIL_LAUNCH (read at vrt_create) is reported as failed instead of queued
         if (c->knobs.fail_launch >= 0 && (unsigned)c->knobs.fail_launch == seq) return fail(VRT_E_DEVICE, "injected launch failure (VRT_TEST_FAIL_LAUNCH)");
         PrimaryRecord* prim = nullptr;  // fused samples share their camera rays through this table (vrt_pool.h)
-        if (c->pooled && g > 1 && (!instr || c->count_as_timed)) {  // counting the reference's work: every camera ray is walked
+        if (v.share_primary) {
             Lane& l = c->lanes[lane];
             if (!l.prim_cache && dalloc(c, &l.prim_cache, c->npix) != hipSuccess) { (void)hipGetLastError(); (void)dfree(c, &l.prim_cache); }
             prim = l.prim_cache;
         }
-        const int all_blocks = d12 ? c->render_blocks_d12 : c->render_blocks;
+        const int all_blocks = v.dense12 ? c->render_blocks_d12 : c->render_blocks;
         const int blocks = lone ? all_blocks : plan_partial_blocks(all_blocks, c->grid_div);
-        if (c->pooled) HIP_TRY(launch_render_pool(rs, c->cfg.grid_res, restir, instr, blocks, fp, sc, out, c->d_work, seq, g, c->lanes[lane].pool_scratch, c->drain_signal, prim, culling(c), c->dense_grid, d12));
-        else HIP_TRY(launch_render(rs, c->cfg.grid_res, restir, instr, c->render_blocks, fp, sc, out, c->d_work, seq, g, c->knobs.chunk));
-        c->drain_signalled = c->pooled && c->drain_signal != nullptr;
+        if (pooled) HIP_TRY(launch_render_pool(rs, c->cfg.grid_res, v, blocks, fp, sc, out, c->d_work, seq, g, c->lanes[lane].pool_scratch, c->drain_signal, prim));
+        else HIP_TRY(launch_render(rs, c->cfg.grid_res, restir, v.instr, c->render_blocks, fp, sc, out, c->d_work, seq, g, c->knobs.chunk));
+        c->drain_signalled = pooled && c->drain_signal != nullptr;
         c->prev_launch_full = blocks == all_blocks;
-        if (c->prev_launch_full && c->pooled) c->last_full_seq = seq + 1u;
+        if (c->prev_launch_full && pooled) c->last_full_seq = seq + 1u;
         if (timer_end(t) != VRT_OK) return VRT_E_DEVICE;
         PlaneSet& p = c->sets[set];
         if (overlapped) {

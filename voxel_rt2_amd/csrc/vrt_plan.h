@@ -1,5 +1,5 @@
-// vrt_plan.h -- the launch pipeline's decisions as plain functions over plain values: the environment switches, the pipeline's shape,
-// how many samples a launch fuses, which launches carry timers, what a dispatch waits for, which copy and stream a launch takes.
+// vrt_plan.h -- the launch pipeline's decisions as plain functions over plain values: the environment switches, which render kernel a launch takes, the
+// pipeline's shape, how many samples a launch fuses, which launches carry timers, what a dispatch waits for, which copy and stream a launch takes.
 // Nothing here knows HIP or vrt_ctx: vrt_pipeline.hip calls these between its HIP calls, tests/emul/plan_emul.cpp calls them on a
 // machine without a GPU (tests/test_pipeline_plan_host.py).
 #pragma once
@@ -66,6 +66,39 @@ static Knobs read_knobs() {
     if (const char* e = getenv("VRT_CHUNK")) { const int v = atoi(e); if (v >= 64 && v <= 4096) k.chunk = v / 64 * 64; }
 #endif
     return k;
+}
+
+// Which instantiation of the render kernel a launch takes, decided HERE and nowhere else.  vrt_api.hip fills the inputs from the context
+// (render_inputs); vrt_kernels.hip maps the result to a kernel: k_render<G, restir, instr> on the fused schedule; on the pooled one
+// (pool_kernel) k_render_pool_restir<G, instr, cull>, else with dense12 k_render_pool_dense12<G, instr, cull>, else
+// k_render_pool<G, instr, black_sun, cull>.
+struct RenderInputs {
+    int width, height, max_depth, knob_render, knob_cull;     // (Knobs::render, Knobs::cull)
+    bool use_restir, instrumented, count_as_timed, ref_oob;   // vrt_set_instrumented, vrt_set_reference_indexing
+    bool cull_active, dense_grid, light_emits;                // the scene's (vrt_prepare); a colour component of the light is non-zero and so is its weight
+    int fused;                                                // samples the launch renders (plan_fused_count)
+};
+struct RenderVariant {
+    bool pooled, restir;  // the pooled schedule (vrt_pool.h), not the fused one (vrt_path.h); ReSTIR runs on either
+    bool instr;           // counts the reference's work; also the instantiations that carry the reference's out-of-grid reading
+    bool cull;            // rays that cannot hit a voxel are not walked (cull_ray, vrt_trace.h): sc.cull is the scene's box, not the open one
+    bool black_sun;       // scene.py's default light: the light sample is compiled out of the shading stage
+    bool dense12;         // the twelve-wave geometry of a dense grid under an emitting sun; also `heavy` of plan_pipeline_shape
+    bool share_primary;   // fused samples share their camera rays through a per-pixel table (vrt_pool.h)
+};
+static inline RenderVariant plan_render_variant(const RenderInputs& in) {
+    RenderVariant v;
+    // the pooled kernel packs pixel coordinates in 12 bits and the depth in 4; VRT_RENDER=fused: A/B measurements, tests
+    v.pooled = in.width <= 4096 && in.height <= 4096 && in.max_depth <= 15 && in.knob_render != 0;
+    v.restir = in.use_restir;
+    v.instr = in.instrumented || in.ref_oob;
+    // launches that count the reference's work walk every ray, as the reference and the oracle do; with the reference's indexing a
+    // ray clear of every solid voxel can still "hit" outside the grid: every ray is walked; VRT_CULL=0 for A/B runs
+    v.cull = in.cull_active && !(in.instrumented && !in.count_as_timed) && !in.ref_oob && in.knob_cull != 0;
+    v.black_sun = !in.light_emits;
+    v.dense12 = v.pooled && !v.restir && in.dense_grid && !v.black_sun;   // (with a black sun SHADE walks next to no shadow rays)
+    v.share_primary = v.pooled && in.fused > 1 && (!v.instr || in.count_as_timed);   // (counting the reference's work: every camera ray is walked)
+    return v;
 }
 
 // How deep a launch of `items` work items (pixels x fused samples) wants the pipeline.  A launch lasts at least as long as its
