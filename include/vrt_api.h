@@ -284,6 +284,24 @@ int vrt_sky_probe(vrt_ctx* ctx, int op, int n, const float* in, int in_stride, f
  *           launches do (with the reference's indexing they do not, and neither does the probe).
  * A culled ray reports distance inf, cell -1, normal 0 and 0 steps; at grid_res 128 a walk also ends where it leaves the box. */
 int vrt_trace_probe(vrt_ctx* ctx, int mode, int n, const float* origin_dir, void* out);
+/* Evaluate single shading functions on the device (test hook; the rows the reference's own bsdf.py, math_utils.py, reservoir.py and
+ * Renderer.shift were executed on: tests/golden/reference/functions.npz and functions_edges.npz).  After vrt_prepare: the shift reads the
+ * context's materials, scene and camera.  `in` holds n rows of in_stride floats, `out` n rows of out_stride floats; integers and bit patterns
+ * travel as float bit patterns.  One row per lane.  op (row layouts as oracle/orc_api.cpp's orc_unit_* probes take them):
+ *   0  mat 14, v, n, l, form            -> diffuse rgb, specular rgb, pdf (disney_evaluate_split + pdf_disney, bsdf.py:138-172, 383-393)
+ *   1  mat 14, v, n, l, lobe, form      -> pdf_disney_lobewise (:365-381)
+ *   2  mat 14, v, n, seed, count        -> count x (direction, brdf rgb, pdf, lobe): sample_disney (:395-458), draw i from stream (seed, 0, i, 0)
+ *   3  cos_max, n, seed, count          -> count x direction: sample_cone_oriented (math_utils.py:44-59)
+ *   4  v -> octahedral code | 5 code -> v | 6 id, albedo -> packed material | 7 packed material -> albedo | 8 x, y, z -> hash3 | 9 x -> uchimura
+ *   10 sample 21, M, weight             -> the same 23 floats after a Reservoir's encode -> decode (reservoir.py:104-141)
+ *   11 dst_pos, dst_normal, dst_mat 14, src_pos, sample 21, view, dst_M
+ *                                       -> diffuse rgb, specular rgb, jacobian of Renderer.shift (pathtracer.py:672-812), then the Jacobian alone
+ *                                          as the reuse pass's classify kernel works it out, then 1 / 0: that kernel skips / evaluates the shift.
+ *   form: the device code has three formulations of the BSDF -- 0 the render kernels', 1 the reuse pass's, 2 the reuse pass's for a
+ *   reconnection vertex -- which must agree bit for bit.  sample = F, rc_pos, rc_normal, rc_incident_dir, rc_incident_L, rc_NEE_dir,
+ *   rc_mat_info, cached_jacobian_term, lobes.  count <= 16 and out_stride >= count x the floats of one draw.
+ * VRT_E_INVALID: op outside 0..11, a stride smaller than the op's row, NULL pointers, n <= 0; VRT_E_STATE: before vrt_prepare. */
+int vrt_shade_probe(vrt_ctx* ctx, int op, int n, const float* in, int in_stride, float* out, int out_stride);
 /* Diagnostic builds only (library compiled with -DVRT_DIAG_REGIONS, see tools/diag_regions.py): copy out the
  * 32 x {wave entries, active lanes} counters of the instrumented regions of the render kernel and optionally
  * zero them.  The shipped library returns VRT_E_STATE -- it carries no region counters. */

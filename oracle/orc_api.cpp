@@ -210,6 +210,20 @@ void orc_unit_shift(orc_ctx* c, const float* dst_pos, const float* dst_n, const 
                &d, &sp, &jac, nullptr);
     out[0] = d.x; out[1] = d.y; out[2] = d.z; out[3] = sp.x; out[4] = sp.y; out[5] = sp.z; out[6] = jac;
 }
+/* the view vector shift() works out for a destination (pathtracer.py:732): n positions in, n unit vectors toward the camera out */
+void orc_unit_view(orc_ctx* c, int n, const float* pos, float* out) {
+    for (int k = 0; k < n; k++) {
+        V3 v = normalized(c->r.camera_pos - v3(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]));
+        out[3 * k] = v.x; out[3 * k + 1] = v.y; out[3 * k + 2] = v.z;
+    }
+}
+/* math_utils.py:238-247, the albedo half: the three bytes above the id as floats */
+void orc_unit_decode_albedo(uint32_t enc, float* out) {
+    int id;
+    V3 a;
+    decode_material_bits(enc, &id, &a);
+    out[0] = a.x; out[1] = a.y; out[2] = a.z;
+}
 static DisneyMaterial mat_from(const float* m) {
     DisneyMaterial dm;
     memcpy(&dm, m, 14 * sizeof(float));

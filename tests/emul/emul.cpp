@@ -16,6 +16,7 @@
 #include "../../voxel_rt2_amd/csrc/vrt_restir.h"
 #include "../../voxel_rt2_amd/csrc/vrt_temporal.h"
 #include "../../voxel_rt2_amd/csrc/vrt_probe.h"
+#include "../../voxel_rt2_amd/csrc/vrt_shade_probe.h"
 
 using namespace vrt;
 
@@ -44,6 +45,7 @@ struct Emu {
     mat4 prev_view{}, prev_proj{};
     TraceStats ts;
     bool ref_oob = false;            // vrt_set_reference_indexing
+    bool prepared = false;           // emu_prepare has run (emu_shade_probe)
 };
 
 static FrameParams frame_params(const Emu* c) {
@@ -170,7 +172,7 @@ int emu_upload_materials(Emu* c, const float* t) { memcpy(c->mats.data(), t, 128
 int emu_upload_cloud_texture(Emu*, const uint8_t*) { return 0; }
 int emu_set_scene(Emu* c, const vrt_scene_params* s) { c->scene = *s; return 0; }
 int emu_set_camera(Emu* c, const vrt_camera* cam) { c->cam = *cam; return 0; }
-int emu_prepare(Emu*) { return 0; }
+int emu_prepare(Emu* c) { c->prepared = true; return 0; }
 int emu_set_reference_indexing(Emu* c, int on) { c->ref_oob = on != 0; return 0; }
 // The rows a striped launch renders (vrt_set_row_stripes): the render kernels' enumeration -- tile rows through launch_tile_row(), pixels
 // through launch_renders_row() (vrt_types.h) -- marked in out[H].  Returns the number of tile rows enumerated.
@@ -467,6 +469,25 @@ int emu_trace_probe(Emu* c, int mode, int n, const float* origin_dir, void* out)
     if (!c || !origin_dir || !out || n <= 0 || mode < 0 || (mode & ~(3 | PROBE_CULL_BOX)) || (mode & 3) >= PROBE_WALK_COUNT) return VRT_E_INVALID;
     if (c->cfg.grid_res == 256) trace_probe_g<256>(c, mode, n, origin_dir, (ProbeOut*)out);
     else trace_probe_g<128>(c, mode, n, origin_dir, (ProbeOut*)out);
+    return 0;
+}
+// vrt_shade_probe (include/vrt_api.h) on the host build of the same row function (vrt_shade_probe.h): same ops, same row layouts, same
+// return codes.  `prepared`: emu_prepare has run (the host build needs nothing of it; the flag keeps the hook's contract testable).
+int emu_shade_probe(Emu* c, int op, int n, const float* in, int in_stride, float* out, int out_stride) {
+    if (!c || !in || !out || n <= 0 || op < 0 || op >= SHADE_OP_COUNT || in_stride < shade_probe_in_width(op) || out_stride < shade_probe_out_width(op))
+        return VRT_E_INVALID;
+    if (!c->prepared) return VRT_E_STATE;
+    if (c->mats_x.empty()) derive_materials(c);
+    const FrameParams fp = frame_params(c);
+    SceneData sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.mats = c->mats.data();
+    sc.sky.scattering = c->sky_scat.data(); sc.sky.transmittance = c->sky_trans.data();
+    sc.sky.res = c->cfg.sky_res; sc.sky.fres = c->cfg.sky_res > 0 ? (float)(1.0 / (double)c->cfg.sky_res) : 0.0f;
+    std::vector<float> lane(op == SHADE_SHIFT ? VRT_SHADE_LANE_TABLE : 1, 0.0f);
+    memset(out, 0, (size_t)n * out_stride * sizeof(float));
+    for (int i = 0; i < n; i++)
+        shade_probe_row(fp, sc, c->mats_x.data(), op, in + (size_t)i * in_stride, out + (size_t)i * out_stride, out_stride, lane.data());
     return 0;
 }
 // host definition of the two half conversions (include/vrt_detmath.h), for tests that pin numpy's against it

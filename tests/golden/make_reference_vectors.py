@@ -524,6 +524,105 @@ def function_vectors(path, n=300, seed=9):
     print(os.path.basename(path), {k: v.shape for k, v in out.items() if hasattr(v, "shape") and v.shape}, flush=True)
 
 
+def edge_function_vectors(path):
+    """The functions of function_vectors on the EDGE rows of tests/shading.py (functions_edges.npz): every CSV material and each
+    parameter at the ends of its range, the renderer's own normals, grazing and degenerate directions, every lobe code; shifts of every
+    kind of sample with the geometric tests straddled and the cached Jacobian term / a material row at their special values.  The rows
+    are stored beside the results; tests/shading.py checks that they are still the rows it builds."""
+    import taichi as ti
+    import make_golden
+    from taichi.math import vec3
+    from voxel_rt2_amd import scenes
+    import renderer.math_utils as mu
+    import renderer.reservoir as rs
+    import orc
+    import shading
+    t0 = time.time()
+    case = ("sunlit", 0, 16, 8, 2, 0, False, [])
+    sess = ReferenceSession(make_golden.config_of(case))
+    mat_s, rgb_s, params = scenes.scene_sunlit(0)
+    orc.setup(sess, mat_s, rgb_s, params)
+    r, bsdf = sess.r, sess.r.bsdf
+    L, fptr = sess.L, sess._fptr
+    V = lambda a: ti.Vector([x for x in a])  # noqa: E731
+
+    def stream(i, count, sd):
+        out = np.zeros(count, np.float32)
+        L.orc_unit_rng(C.c_uint32(sd), C.c_uint32(0), C.c_uint32(i), C.c_uint32(0), count, fptr(out))
+        return out
+
+    def material(row):
+        return bsdf.disney_material(base_col=vec3(row[0], row[1], row[2]), **{k: row[3 + j] for j, k in enumerate(MAT_FIELDS)})
+
+    b = shading.edge_bsdf_rows()
+    n, D = len(b["mat"]), shading.EDGE_DRAWS
+    out = {"bsdf_" + k: np.array(a) for k, a in b.items()}
+    out.update(bsdf_eval=np.zeros((n, 7), np.float32), bsdf_lobe_pdf=np.zeros(n, np.float32), bsdf_sample=np.zeros((n, D, 8), np.float32))
+    for k in range(n):
+        m = material(b["mat"][k])
+        vv, nn, ll = V(b["v"][k]), V(b["n"][k]), V(b["l"][k])
+        t, bt = mu.make_orthonormal_basis(nn)
+        d, sp = bsdf.disney_evaluate_split(m, vv, nn, ll, t, bt)
+        out["bsdf_eval"][k] = d.to_list() + sp.to_list() + [bsdf.pdf_disney(m, vv, nn, ll, t, bt)]
+        out["bsdf_lobe_pdf"][k] = bsdf.pdf_disney_lobewise(m, vv, nn, ll, t, bt, int(b["lobe"][k]))
+        for i in range(D):
+            ti.set_random_source(stream(i, 16, shading.SAMPLE_SEED + k))
+            sd, brdf, pdf, lobe = bsdf.sample_disney(m, vv, nn, t, bt)
+            out["bsdf_sample"][k, i] = sd.to_list() + brdf.to_list() + [pdf, lobe]
+    print(f"  {n} BSDF rows {time.time() - t0:.0f} s", flush=True)
+    c = shading.edge_cone_rows()
+    out.update({"cone_" + k: np.array(a) for k, a in c.items()})
+    out["cone_out"] = np.zeros((len(c["cos"]), D, 3), np.float32)
+    for k in range(len(c["cos"])):
+        for i in range(D):
+            ti.set_random_source(stream(i, 4, shading.CONE_SEED))
+            out["cone_out"][k, i] = mu.sample_cone_oriented(c["cos"][k], V(c["n"][k])).to_list()
+    m_ = shading.edge_misc_rows()
+    out.update({k: np.array(a) for k, a in m_.items()})
+    out["oct_code"] = np.zeros((len(m_["oct_in"]), 2), np.uint16)
+    out["oct_out"] = np.zeros((len(m_["oct_in"]), 3), np.float32)
+    for k, v in enumerate(m_["oct_in"]):
+        code = mu.encode_unit_vector_3x16(V(v))
+        out["oct_code"][k] = np.array(code.to_list(), np.float16).view(np.uint16)
+        out["oct_out"][k] = mu.decode_unit_vector_3x16(code).to_list()
+    out["matenc"] = np.array([int(mu.encode_material(int(i), V(a))) for i, a in zip(m_["matenc_id"], m_["matenc_albedo"])], np.uint32)
+    out["albedo_out"] = np.array([mu.decode_material(r.mats.mat_list, np.uint32(e))[0].base_col.to_list() for e in out["matenc"]], np.float32)
+    out["hash_out"] = np.array([int(mu.hash3(*[np.uint32(x) for x in row])) for row in m_["hash_in"]], np.uint32)
+    out["uchimura_out"] = np.array([float(mu.uchimura(V([x, x, x])).x) for x in m_["uchimura_in"]], np.float32)
+
+    def reservoir(row):
+        q = rs.Reservoir()
+        q.init()
+        q.z.F, q.z.rc_pos, q.z.rc_normal, q.z.rc_incident_dir = V(row[0:3]), V(row[3:6]), V(row[6:9]), V(row[9:12])
+        q.z.rc_incident_L, q.z.rc_NEE_dir = V(row[12:15]), V(row[15:18])
+        q.z.rc_mat_info, q.z.cached_jacobian_term, q.z.lobes = row[18:19].view(np.uint32)[0], row[19], int(row[20])
+        q.M, q.weight = row[21], row[22]
+        return q
+    out["res_out"] = np.zeros((len(m_["res_in"]), 23), np.float32)
+    for k, row in enumerate(np.array(m_["res_in"])):
+        q = rs.Reservoir()
+        q.init()
+        q.decode(reservoir(row).encode())
+        o = q.z.F.to_list() + q.z.rc_pos.to_list() + q.z.rc_normal.to_list() + q.z.rc_incident_dir.to_list() + q.z.rc_incident_L.to_list() + q.z.rc_NEE_dir.to_list()
+        out["res_out"][k, :18] = o
+        out["res_out"][k, 18] = np.array([q.z.rc_mat_info], np.uint32).view(np.float32)[0]
+        out["res_out"][k, 19:] = [q.z.cached_jacobian_term, q.z.lobes, q.M, q.weight]
+    print(f"  single functions {time.time() - t0:.0f} s", flush=True)
+    s = shading.edge_shift_rows()
+    S = len(s["dst_pos"])
+    out.update({"shift_" + k: np.array(a) for k, a in s.items()})
+    out["shift_out"], out["shift_view"] = np.zeros((S, 7), np.float32), np.zeros((S, 3), np.float32)
+    for k in range(S):
+        q = reservoir(np.concatenate([s["sample"][k], [1.0, 1.0]]).astype(np.float32))
+        dm = material(s["dst_mat"][k])
+        d, sp, jac = r.shift(V(s["dst_pos"][k]), V(s["dst_n"][k]), dm, V(s["src_pos"][k]), V(s["dst_n"][k]), dm, q)
+        out["shift_out"][k] = d.to_list() + sp.to_list() + [jac]
+        out["shift_view"][k] = (r.camera_pos[None] - V(s["dst_pos"][k])).normalized().to_list()       # pathtracer.py:732
+    np.savez_compressed(path, **out)
+    print(os.path.basename(path), {k: v.shape for k, v in out.items() if hasattr(v, "shape") and v.shape}, os.path.getsize(path), "bytes",
+          f"{time.time() - t0:.0f} s", flush=True)
+
+
 SKY_OPS = {"rsi": (0, 7, 2), "ozone": (1, 1, 1), "density": (2, 1, 3), "cloud_phase": (3, 2, 1), "cloud_density": (4, 3, 1),
            "cloud_shadow_od": (5, 7, 1), "ray_transmittance": (6, 6, 3), "clouds_scattering": (7, 15, 5),
            "atmos_scattering_d0": (8, 15, 6), "atmos_scattering_d1": (9, 15, 6)}    # name -> (probe op, floats in, floats out)
@@ -773,8 +872,12 @@ def main(argv):
     if "--check-golden" in argv:
         return check_golden([a for a in argv if not a.startswith("--")])
     libm = "--libm" in argv
-    names = [a for a in argv if not a.startswith("--")] or list(CASES) + ["rays", "functions", "functions_sky"]
+    names = [a for a in argv if not a.startswith("--")] or list(CASES) + ["rays", "functions", "functions_sky", "functions_edges"]
     os.makedirs(OUT, exist_ok=True)
+    if "functions_edges" in names:
+        names.remove("functions_edges")
+        if not os.path.exists(os.path.join(OUT, "functions_edges.npz")) or "--force" in argv:
+            edge_function_vectors(os.path.join(OUT, "functions_edges.npz"))
     if "rays" in names:
         names.remove("rays")
         if not os.path.exists(os.path.join(OUT, "rays_sunlit.npz")) or "--force" in argv:

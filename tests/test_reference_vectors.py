@@ -60,7 +60,7 @@ DENSE = sorted(n for n in CASES if "undefined_px" in np.load(os.path.join(HERE, 
 
 def test_every_case_has_a_fixture():
     have = {f[:-4] for f in os.listdir(os.path.join(HERE, "golden", "reference")) if f.endswith(".npz")}
-    have -= {"rays_sunlit", "functions", "functions_sky"}    # single rays and single functions: the tests at the end
+    have -= {"rays_sunlit", "functions", "functions_sky", "functions_edges"}    # single rays and single functions: the tests at the end
     assert have == set(CASES)
 
 
@@ -237,6 +237,55 @@ def test_oracle_functions_equal_reference_source():
         L.orc_unit_unproject_sky(C.c_void_p(o._ctx), f(np.ascontiguousarray(v["sky_uv_in"][k])), f(out))
         assert _same(out, v["sky_dir_out"][k]), ("unproject_sky", k)
     o.close()
+
+
+def test_oracle_edge_functions_equal_reference_source():
+    """functions_edges.npz: the functions of functions.npz on the edge rows of tests/shading.py (make_reference_vectors.edge_function_vectors)
+    -- every CSV material and each parameter at the ends of its range, the renderer's normals, grazing and degenerate directions, every
+    lobe code, shifts of every kind with their tests straddled -- against the oracle's probes, bit for bit."""
+    import ctypes as C
+    import shading
+    e = np.load(os.path.join(HERE, "golden", "reference", "functions_edges.npz"))
+    L, f = orc.lib(), orc.fptr
+    eb, ec, es, em = shading.edge_bsdf_rows(), shading.edge_cone_rows(), shading.edge_shift_rows(), shading.edge_misc_rows()
+    shading.assert_fixture_rows(e, "bsdf", eb, ("mat", "v", "n", "l", "lobe"))
+    shading.assert_fixture_rows(e, "cone", ec, ("cos", "n"))
+    shading.assert_fixture_rows(e, "shift", es, ("dst_pos", "dst_n", "dst_mat", "src_pos", "sample", "dst_M"))
+    for k, a in em.items():
+        assert np.ascontiguousarray(e[k]).tobytes() == np.ascontiguousarray(a).tobytes(), k
+    got = shading.oracle_bsdf(eb, shading.EDGE_DRAWS)
+    for key in ("eval", "lobe_pdf", "sample"):
+        ok = shading.same(got[key], e["bsdf_" + key]).reshape(len(eb["mat"]), -1).all(axis=1)
+        bad = np.flatnonzero(~ok)
+        assert bad.size == 0, (key, [(int(k), str(eb["cls"][k])) for k in bad[:5]], got[key][bad[0]], e["bsdf_" + key][bad[0]])
+    assert _same(shading.oracle_cone(ec, shading.EDGE_DRAWS), e["cone_out"])
+    for k in range(len(e["oct_in"])):
+        code, dec = np.zeros(2, np.uint16), np.zeros(3, np.float32)
+        L.orc_unit_oct_encode(f(np.ascontiguousarray(e["oct_in"][k])), f(code))
+        want = e["oct_code"][k]
+        nan16 = lambda h: (h & 0x7C00) == 0x7C00 and (h & 0x3FF) != 0  # noqa: E731
+        assert all(int(c) == int(w) or (nan16(int(c)) and nan16(int(w))) for c, w in zip(code, want)), ("oct encode", k, code, want)
+        L.orc_unit_oct_decode(f(np.ascontiguousarray(want)), f(dec))
+        assert _same(dec, e["oct_out"][k]), ("oct decode", k)
+    for k in range(len(e["matenc"])):
+        assert L.orc_unit_encode_material(int(e["matenc_id"][k]), f(np.ascontiguousarray(e["matenc_albedo"][k]))) == int(e["matenc"][k]), ("encode_material", k)
+        alb = np.zeros(3, np.float32)
+        L.orc_unit_decode_albedo(C.c_uint32(int(e["matenc"][k])), f(alb))
+        assert _same(alb, e["albedo_out"][k]), ("decode_material", k)
+    for k in range(len(e["hash_out"])):
+        assert L.orc_unit_hash3(*[int(x) for x in e["hash_in"][k]]) == int(e["hash_out"][k])
+    out = np.zeros(len(e["uchimura_in"]), np.float32)
+    L.orc_unit_uchimura(f(np.ascontiguousarray(e["uchimura_in"])), len(out), f(out))
+    assert _same(out, e["uchimura_out"]), (out, e["uchimura_out"])
+    for k in range(len(e["res_in"])):
+        out = np.zeros(23, np.float32)
+        L.orc_unit_reservoir_roundtrip(f(np.ascontiguousarray(e["res_in"][k])), f(out))
+        assert _same(out, e["res_out"][k]), ("reservoir", k, out, e["res_out"][k])
+    got = shading.oracle_shift(es)
+    ok = shading.same_shift(got, e["shift_out"], es["cls"]).all(axis=1)
+    bad = np.flatnonzero(~ok)
+    assert bad.size == 0, ([(int(k), str(es["cls"][k])) for k in bad[:5]], got[bad[0]], e["shift_out"][bad[0]])
+    assert _same(shading.view_vectors(es["dst_pos"]), e["shift_view"])
 
 
 SKY_OPS = {"rsi": (0, 2), "ozone": (1, 1), "density": (2, 3), "cloud_phase": (3, 1), "cloud_density": (4, 1), "cloud_shadow_od": (5, 1),

@@ -118,6 +118,8 @@ def _open(path):
     lib.vrt_sky_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.vrt_trace_probe.restype = C.c_int
     lib.vrt_trace_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.vrt_shade_probe.restype = C.c_int
+    lib.vrt_shade_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     return lib
 
 

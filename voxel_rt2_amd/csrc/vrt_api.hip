@@ -8,6 +8,7 @@
 // redundantly instead of exchanging them: per-pixel random streams make them bit-identical).
 #include "vrt_ctx.h"
 #include "vrt_probe.h"
+#include "vrt_shade_probe.h"
 
 // The row ranges this context produces: one, or with vrt_set_row_stripes its stripes.
 static std::vector<std::pair<int, int>> owned_ranges(const vrt_ctx* c) {
@@ -735,6 +736,27 @@ int vrt_trace_probe(vrt_ctx* c, int mode, int n, const float* origin_dir, void* 
     if (e == hipSuccess) e = sync_guarded(c, c->stream);
     hipFree(d_in); hipFree(d_out);
     if (e != hipSuccess) return fail(VRT_E_DEVICE, std::string("trace probe: ") + hipGetErrorString(e));
+    return VRT_OK;
+}
+// Test hook: rows of arguments through single shading functions on the context's materials, scene and camera (vrt_shade_probe.h, k_shade_probe).
+int vrt_shade_probe(vrt_ctx* c, int op, int n, const float* in, int in_stride, float* out, int out_stride) {
+    if (!c || !in || !out || n <= 0 || op < 0 || op >= SHADE_OP_COUNT || in_stride < shade_probe_in_width(op) || out_stride < shade_probe_out_width(op))
+        return fail(VRT_E_INVALID, "bad argument");
+    if (!c->prepared) return fail(VRT_E_STATE, "needs vrt_prepare");
+    if (enter(c) != VRT_OK) return VRT_E_DEVICE;
+    float *d_in = nullptr, *d_out = nullptr, *d_lane = nullptr;
+    const size_t n_in = (size_t)n * in_stride, n_out = (size_t)n * out_stride, n_lane = op == SHADE_SHIFT ? (size_t)n * VRT_SHADE_LANE_TABLE : 0;
+    hipError_t e = hipMalloc((void**)&d_in, n_in * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_out, n_out * sizeof(float));
+    if (e == hipSuccess && n_lane) e = hipMalloc((void**)&d_lane, n_lane * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, n_in * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, n_out * sizeof(float), c->stream);
+    if (e == hipSuccess && n_lane) e = hipMemsetAsync(d_lane, 0, n_lane * sizeof(float), c->stream);
+    if (e == hipSuccess) e = launch_shade_probe(c->stream, make_frame_params(c), make_scene_data(c), c->d_mats_x, op, n, d_in, in_stride, d_out, out_stride, d_lane);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = sync_guarded(c, c->stream);
+    hipFree(d_in); hipFree(d_out); hipFree(d_lane);
+    if (e != hipSuccess) return fail(VRT_E_DEVICE, std::string("shade probe: ") + hipGetErrorString(e));
     return VRT_OK;
 }
 // diagnostic builds (-DVRT_DIAG_REGIONS) only: 32 x {wave entries, active lanes} per instrumented code region

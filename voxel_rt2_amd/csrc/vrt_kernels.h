@@ -63,6 +63,9 @@ hipError_t launch_diag_read(hipStream_t st, unsigned long long* out, int reset);
 hipError_t launch_detmath_probe(hipStream_t st, int op, int n, const float* a, const float* b, float* out);
 // n rays (origin, direction: 6 floats each, voxel units) through walk PROBE_WALK_* against `cull`'s box (vrt_probe.h)
 hipError_t launch_trace_probe(hipStream_t st, int grid_res, int walk, const Pyramid& pyr, const float* cull, int n, const float* rays, ProbeOut* out);
+// n rows of in_stride floats through shading function `op` (vrt_shade_probe.h); lane_tables: n x VRT_SHADE_LANE_TABLE floats for SHADE_SHIFT, else null
+hipError_t launch_shade_probe(hipStream_t st, const FrameParams& fp, const SceneData& sc, const float* mats_x, int op, int n, const float* in, int in_stride,
+                              float* out, int out_stride, float* lane_tables);
 
 // sky precompute (vrt_sky_kernels.hip)
 struct SkyPrecompute {

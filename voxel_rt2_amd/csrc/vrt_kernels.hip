@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include "vrt_kernels.h"
 #include "vrt_probe.h"
+#include "vrt_shade_probe.h"
 
 namespace vrt {
 
@@ -963,6 +964,15 @@ __global__ __launch_bounds__(64) void k_trace_probe(Pyramid pyr, const float* cu
     out[i] = r;
 }
 
+// Test hook (vrt_shade_probe): one row of arguments per lane through one shading function (vrt_shade_probe.h).
+__global__ __launch_bounds__(64) void k_shade_probe(FrameParams fp, SceneData sc, const float* mats_x, int op, int n, const float* in, int in_stride,
+                                                    float* out, int out_stride, float* lane_tables) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    shade_probe_row(fp, sc, mats_x, op, in + (size_t)i * in_stride, out + (size_t)i * out_stride, out_stride,
+                    lane_tables ? lane_tables + (size_t)i * VRT_SHADE_LANE_TABLE : nullptr);
+}
+
 // ---- host-side launchers -----------------------------------------------------------------------
 #define VRT_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
@@ -1098,6 +1108,13 @@ hipError_t launch_tonemap8(hipStream_t st, const FrameParams& fp, const f3* hdr,
 }
 hipError_t launch_detmath_probe(hipStream_t st, int op, int n, const float* a, const float* b, float* out) {
     hipLaunchKernelGGL(k_detmath_probe, dim3((n + 255) / 256), dim3(256), 0, st, op, n, a, b, out);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_shade_probe(hipStream_t st, const FrameParams& fp, const SceneData& sc, const float* mats_x, int op, int n, const float* in, int in_stride,
+                              float* out, int out_stride, float* lane_tables) {
+    if (op == SHADE_SHIFT && !lane_tables) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_shade_probe, dim3((n + 63) / 64), dim3(64), 0, st, fp, sc, mats_x, op, n, in, in_stride, out, out_stride, lane_tables);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -350,35 +350,30 @@ struct GrisBuffers {
     ReservoirRec* res_out;
 };
 
-// once per pixel of every row the launch holds (the rows it renders and their halo)
-VRT_DEV void gris_prepare_pixel(const FrameParams& fp, const SceneData& sc, const GrisBuffers& gb, int u, int v) {
-    const int idx = (v - fp.row0) * fp.W + u;
-    GrisGeo g;
-    g.n = oct_decode(gb.gb_normal[idx]);
-    g.x1 = xform(fp.view_inv, screen_to_view(pixel_texcoord(fp, (float)u, (float)v), gb.gb_depth[idx], fp.proj_inv), 1.0f);
-    g.dist = len3(g.x1 - fp.camera_pos);
-    g.mat = gb.gb_mat[idx];
-    g.v = norm3(fp.camera_pos - g.x1);
-    Reservoir r;
-    reservoir_init(r);
-    reservoir_decode(r, gb.res_in[idx]);
-    g.M = r.M;
+// The three records of one pixel from what the g-buffer and the stored reservoir hold of it: normal, primary vertex, packed
+// material, unit vector toward the camera, decoded reservoir.  `m`, `id` = material_from_bits(sc.mats, mat, id), looked up by the
+// caller (the shade probe hands in a base colour that is no 8-bit code).  Everything but g.dist, which the caller fills.
+// Two halves, so that the prepare pass can store the first record before it works out the second (registers).
+VRT_DEV void gris_fill_geo(const float* mats_x, f3 n, f3 x1, uint32_t mat, const Material& m, int id, f3 view, float M, GrisGeo& g, bool& dst_ok) {
+    g.n = n;
+    g.x1 = x1;
+    g.mat = mat;
+    g.v = view;
+    g.M = M;
     f3 tx;
     ortho_basis(g.n, tx, g.ty);
     g.pad = 0u;
-    bool dst_ok;
     {   // the pixel's own shading point as every neighbour's shift will set it up (gris_pixel, first tap loop)
-        int id;
-        const Material m = material_from_bits(sc.mats, g.mat, id);
         Surf ds;
-        surf_set(ds, m, load_mat_derived(gb.mats_x, id), g.n, g.v, cross3(g.n, g.ty), g.ty);
-        dst_ok = !(ds.n_v > 0.0f) || (ds.n_v >= 1e-5f && gb.mats_x[8 * (id & 127) + 6] != 0.0f);   // shift_is_constant()
+        surf_set(ds, m, load_mat_derived(mats_x, id), g.n, g.v, cross3(g.n, g.ty), g.ty);
+        dst_ok = !(ds.n_v > 0.0f) || (ds.n_v >= 1e-5f && mats_x[8 * (id & 127) + 6] != 0.0f);   // shift_is_constant()
         const SurfShared c = surf_shared(ds, true, true, true);
         g.base = m.base; g.fv = c.fv; g.lambert = c.lambert; g.g_v = c.g_v; g.sheen_col = c.sheen_col; g.gc_v = c.gc_v;
         g.spec_col = c.spec_col; g.pad3 = 0u;
     }
-    gb.geo[idx] = g;
-    GrisSrc s;
+}
+VRT_DEV void gris_fill_src(const FrameParams& fp, const SceneData& sc, const float* mats_x, const Reservoir& r, GrisSrc& s) {
+    f3 tx;
     s.F = r.z.F; s.M = r.M; s.rc_pos = r.z.rc_pos; s.weight = r.weight; s.rc_normal = r.z.rc_normal; s.jac = r.z.jac;
     s.rc_incident_dir = r.z.rc_incident_dir; s.lobes = r.z.lobes; s.rc_incident_L = r.z.rc_incident_L;
     s.rc_mat_info = r.z.rc_mat_info; s.rc_nee_dir = r.z.rc_nee_dir; s.pad0 = 0u; s.pad1 = 0u;
@@ -388,23 +383,45 @@ VRT_DEV void gris_prepare_pixel(const FrameParams& fp, const SceneData& sc, cons
     s.sky_t = (fp.use_sky == 1 && !near_zero3(r.z.rc_nee_dir)) ? sky_transmittance(sc.sky, r.z.rc_nee_dir) : mk3(1.0f);
     s.pad2 = 0u;
     {   // the reconnection vertex as shift_sample() sets it up, minus the view vector
-        int id;
-        const Material m = material_from_bits(sc.mats, r.z.rc_mat_info, id);
-        const MatDerived x = load_mat_derived(gb.mats_x, id);
-        const MatColours mc = mat_colours(m);
+        int rc_id;
+        const Material rm = material_from_bits(sc.mats, r.z.rc_mat_info, rc_id);
+        const MatDerived x = load_mat_derived(mats_x, rc_id);
+        const MatColours mc = mat_colours(rm);
         const f3 rtx = cross3(r.z.rc_normal, s.rc_ty);
         const DirTerms a = dir_terms(r.z.rc_normal, rtx, s.rc_ty, x.ax, x.ay, r.z.rc_incident_dir);
         const DirTerms b = dir_terms(r.z.rc_normal, rtx, s.rc_ty, x.ax, x.ay, r.z.rc_nee_dir);
-        s.base = m.base; s.lambert = mc.lambert; s.sheen_col = mc.sheen_col; s.spec_col = mc.spec_col;
+        s.base = rm.base; s.lambert = mc.lambert; s.sheen_col = mc.sheen_col; s.spec_col = mc.spec_col;
         s.inc_nl = a.nl; s.inc_fl = a.fl; s.inc_g = a.g_l; s.inc_gc = a.gc_l; s.inc_pd = a.pd;
         s.nee_nl = b.nl; s.nee_fl = b.fl; s.nee_g = b.g_l; s.nee_gc = b.gc_l; s.nee_pd = b.pd;
         s.pad4 = 0u; s.pad5 = 0u;
     }
-    gb.src[idx] = s;
+}
+VRT_DEV GrisTest gris_test_record(f3 n, float dist, f3 x1, float M, bool dst_ok, const GrisSrc& s) {
     GrisTest t;
-    t.n = g.n; t.dist = g.dist; t.rc_pos = s.rc_pos; t.jac = s.jac; t.rc_normal = s.rc_normal; t.M = g.M;
-    t.x1 = g.x1; t.dst_ok = dst_ok ? 1u : 0u;
-    gb.tst[idx] = t;
+    t.n = n; t.dist = dist; t.rc_pos = s.rc_pos; t.jac = s.jac; t.rc_normal = s.rc_normal; t.M = M;
+    t.x1 = x1; t.dst_ok = dst_ok ? 1u : 0u;
+    return t;
+}
+// once per pixel of every row the launch holds (the rows it renders and their halo): the part that reads the g-buffer
+VRT_DEV void gris_prepare_pixel(const FrameParams& fp, const SceneData& sc, const GrisBuffers& gb, int u, int v) {
+    const int idx = (v - fp.row0) * fp.W + u;
+    const f3 n = oct_decode(gb.gb_normal[idx]);
+    const f3 x1 = xform(fp.view_inv, screen_to_view(pixel_texcoord(fp, (float)u, (float)v), gb.gb_depth[idx], fp.proj_inv), 1.0f);
+    const uint32_t mat = gb.gb_mat[idx];
+    Reservoir r;
+    reservoir_init(r);
+    reservoir_decode(r, gb.res_in[idx]);
+    int id;
+    const Material m = material_from_bits(sc.mats, mat, id);
+    GrisGeo g;
+    bool dst_ok;
+    gris_fill_geo(gb.mats_x, n, x1, mat, m, id, norm3(fp.camera_pos - x1), r.M, g, dst_ok);
+    g.dist = len3(g.x1 - fp.camera_pos);
+    gb.geo[idx] = g;
+    GrisSrc s;
+    gris_fill_src(fp, sc, gb.mats_x, r, s);
+    gb.src[idx] = s;
+    gb.tst[idx] = gris_test_record(g.n, g.dist, g.x1, g.M, dst_ok, s);
 }
 VRT_DEV void gris_load_src(Reservoir& r, f3& rc_ty, f3& sky_t, RcPre& pre, const GrisSrc& s) {
     r.z.F = s.F; r.M = s.M; r.z.rc_pos = s.rc_pos; r.weight = s.weight; r.z.rc_normal = s.rc_normal; r.z.jac = s.jac;
