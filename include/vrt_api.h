@@ -133,6 +133,21 @@ int vrt_set_camera(vrt_ctx* ctx, const vrt_camera* cam);
 /* Renderer.prepare_data (pathtracer.py:314-323): packed voxel grid, occupancy pyramid,
  * and with use_physical_sky the transmittance LUT + cloud ambient + cleared sky tables. */
 int vrt_prepare(vrt_ctx* ctx);
+/* Edit a PREPARED scene: replace the voxels of the box [lo, hi) -- coordinates in the index space of vrt_upload_voxels,
+ * 0 <= lo <= hi <= grid_res per axis -- by mat int8[hx][hy][hz] and rgb uint8[hx][hy][hz][3] (C order, h = hi - lo).
+ * on_device = 0: host arrays, borrowed for the call; on_device = 1: device memory that the kernel reads directly (a torch tensor's
+ * data_ptr()), queued on the context's stream -- the caller keeps it unchanged until work queued on that stream behind the call
+ * has run.  Afterwards everything vrt_prepare derives from the voxels (stored materials and colours, packed texels, every level of
+ * the occupancy pyramid, the compacted fine level, the culling box and the host's view of it) is exactly what
+ * vrt_upload_voxels(final grid) + vrt_prepare would have left, at a cost that follows the box and not the grid; what vrt_prepare
+ * does that does not depend on voxels is left alone: the sky preparation, both sky tables, the cloud passes.  Histories and
+ * g-buffers are NOT touched: the accumulated frame goes on blending old and new grid; a caller who wants a fresh accumulation
+ * calls vrt_reset.  Render launches queued before the call see the old grid, launches queued after it the new one.  The call
+ * synchronises with the device once (it reads the culling record back, as vrt_prepare does).
+ * VRT_E_INVALID: NULL arguments, lo > hi, a box outside the grid, on_device not 0 or 1; VRT_E_STATE: before vrt_prepare, or after a
+ * vrt_upload_voxels that no vrt_prepare has followed; an empty box returns VRT_OK and does nothing.  No counterpart in the
+ * reference: its scene is authored before finish(), which never returns. */
+int vrt_update_voxels(vrt_ctx* ctx, const int32_t lo[3], const int32_t hi[3], const void* mat, const void* rgb, int on_device);
 /* Renderer.accumulate_clouds / compute_atmosphere (pathtracer.py:325-329) */
 int vrt_sky_accumulate_clouds(vrt_ctx* ctx, int max_samples);
 int vrt_sky_compute_slice(vrt_ctx* ctx, int slice_idx, int max_slices);
@@ -152,7 +167,7 @@ int vrt_sky_table_io(vrt_ctx* ctx, int which /* VRT_BUF_SKY_SCATTERING | VRT_BUF
  * calls neither force nor disturb it.  The pending accumulation is queued on the context's stream, before anything else the call
  * does, by every call that can observe or change what a pass per launch would have produced: vrt_sync, every vrt_fetch_*
  * (blocking, device, async) and vrt_fetch_buffer, vrt_get_stats / vrt_reset_stats, vrt_reset, vrt_set_stream,
- * vrt_set_hdr_targets, vrt_set_history_exchange / vrt_history_rows_io, vrt_set_row_stripes, vrt_upload_*, vrt_prepare,
+ * vrt_set_hdr_targets, vrt_set_history_exchange / vrt_history_rows_io, vrt_set_row_stripes, vrt_upload_*, vrt_update_voxels, vrt_prepare,
  * vrt_set_instrumented, vrt_set_reference_indexing, vrt_destroy, a vrt_accumulate call whose launch is of another kind (moving
  * camera, render scale below 1, another pipeline depth) or fails.  Results are those of a pass per launch, bit for bit; a caller
  * that orders its own work on the context's stream behind a frame (an event for another stream) calls vrt_sync or a fetch first.

@@ -8,6 +8,7 @@
 #   bench           the judged line with everything else it measures (bench.py --full) + a short digest
 #   scenes[:names]  tools/bench_scenes.py [names, comma separated]
 #   refidx          tools/ref_indexing_diff.py on configs 4 and 5 (GPU)
+#   editcost        tools/edit_cost.py: vrt_update_voxels against upload + prepare -> the table of profiles/edit_cost.md, written under this run's output folder
 #   trace:CASE      rocprofv3 --kernel-trace --stats of bench_scenes.py CASE (CASE = bench: the bench command, config 2)
 #   pmc:CASE        tools/pmc.sh CASE + summary
 #   timeline:CASE[:MODE[:LAG]]  launches and copies in time (tools/timeline.py)
@@ -41,6 +42,9 @@ for l in open('$O/scenes${arg:+_}${arg//,/_}.jsonl'):
     d=json.loads(l); print(' ', d.get('name'), d.get('mpaths_per_s'), {k:v for k,v in d.items() if k.endswith('_ms')})" ;;
     refidx)
       for c in 4 5; do timeout -k 10 600 python tools/ref_indexing_diff.py --backend gpu --config $c > $O/refidx_config$c.json 2> $O/refidx.err || { rc=$?; tail -5 $O/refidx.err; fail refidx $rc; }; cat $O/refidx_config$c.json; done ;;
+    editcost)
+      timeout -k 10 300 python tools/edit_cost.py --out $O/edit_cost.md > $O/edit_cost.jsonl 2> $O/edit_cost.err || { rc=$?; tail -5 $O/edit_cost.err; fail editcost $rc; }
+      cat $O/edit_cost.md ;;
     trace)
       ( cd /tmp; export TMPDIR=/tmp
         if [ "$arg" == "bench" ]; then timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -o t -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.json 2> $O/trace_bench.err

@@ -66,6 +66,7 @@ def declare(lib, prefix):
     sig("set_scene", C.c_int, P, C.POINTER(VrtSceneParams))
     sig("set_camera", C.c_int, P, C.POINTER(VrtCamera))
     sig("prepare", C.c_int, P)
+    sig("update_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
     sig("sky_accumulate_clouds", C.c_int, P, C.c_int)
     sig("sky_compute_slice", C.c_int, P, C.c_int, C.c_int)
     sig("sky_accumulate_clouds_slice", C.c_int, P, C.c_int, C.c_int, C.c_int)

@@ -72,6 +72,24 @@ class NativeSession:
             raise ValueError(f"voxel arrays must be int8[{g},{g},{g}] and uint8[{g},{g},{g},3] (grid_res = {g})")
         self._call("upload_voxels", mat.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p))
 
+    def update_voxels(self, lo, hi, mat, rgb, on_device=False):
+        """Replace the voxels of the box [lo, hi) of a prepared scene (include/vrt_api.h, vrt_update_voxels).  Host path: `mat` and
+        `rgb` are arrays of shape hi - lo and (hi - lo, 3).  Device path (on_device=True): they are integer device pointers to
+        int8[hx][hy][hz] and uint8[hx][hy][hz][3] (a torch tensor's data_ptr()), read on the context's stream."""
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError("lo and hi are three coordinates each")
+        if on_device:
+            pm, pr = C.c_void_p(int(mat)), C.c_void_p(int(rgb))
+        else:
+            shape = tuple(max(h - l, 0) for l, h in zip(lo, hi))
+            mat = np.ascontiguousarray(mat, dtype=np.int8)
+            rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+            if mat.shape != shape or rgb.shape != shape + (3,):
+                raise ValueError(f"box arrays must be int8{list(shape)} and uint8{list(shape + (3,))} for the box {lo}..{hi}")
+            pm, pr = mat.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p)
+        self._call("update_voxels", (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), pm, pr, int(bool(on_device)))
+
     def upload_materials(self, table):
         table = np.ascontiguousarray(table, dtype=np.float32)
         if table.shape != (128, 14):

@@ -394,6 +394,52 @@ int vrt_prepare(vrt_ctx* c) {
     c->prepared = true;
     return VRT_OK;
 }
+// The culling record's host side behind an edit, as vrt_prepare reads it behind its own k_cull_box: is there anything to cull, is the
+// grid dense.  One synchronisation: source and destination of the copy are on this stack frame.
+static int read_cull_record(vrt_ctx* c) {
+    float box[8];
+    HIP_TRY(hipMemcpyAsync(box, c->d_cull, sizeof(box), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(sync_guarded(c, c->stream));
+    c->cull_active = box[6] != 0.0f;
+    // at least half of the 4x4x4 bricks hold a voxel: a dense grid (shadow rays end after a step or two: launch_render_pool)
+    c->dense_grid = box[7] >= 0.5f;
+    if (c->knobs.dense >= 0) c->dense_grid = c->knobs.dense != 0;   // A/B
+    return VRT_OK;
+}
+// Replace the voxels of the box [lo, hi) of a prepared context and bring what vrt_prepare derives from the voxels up to date, at the
+// box's cost (launch_edit).  Ordered like vrt_upload_voxels: the pending accumulation first, the work on the context's stream --
+// behind every render launch queued so far, whose pass is on it -- and main_dirty holds later launches back until it is done.
+int vrt_update_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], const void* mat, const void* rgb, int on_device) {
+    if (!c || !lo || !hi || !mat || !rgb) return fail(VRT_E_INVALID, "null argument");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    EditBox box;
+    for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
+    if (!edit_box_valid(box, c->cfg.grid_res)) return fail(VRT_E_INVALID, "the box must satisfy 0 <= lo <= hi <= grid_res on every axis");
+    if (!c->prepared) return fail(VRT_E_STATE, "vrt_update_voxels edits a prepared grid: call vrt_prepare first (also after vrt_upload_voxels)");
+    const size_t nv = (size_t)edit_box_voxels(box);
+    if (nv == 0) return VRT_OK;
+    if (enter(c) != VRT_OK) return VRT_E_DEVICE;
+    const int8_t* box_mat = (const int8_t*)mat;
+    const uint8_t* box_rgb = (const uint8_t*)rgb;
+    if (!on_device) {
+        const size_t rgb_at = (nv + 255) & ~(size_t)255, need = rgb_at + 3 * nv;
+        if (c->edit_stage_bytes < need) {   // (hipFree waits for the device: no kernel is still reading the old one)
+            HIP_TRY(dfree(c, &c->d_edit_stage));
+            c->edit_stage_bytes = 0;
+            HIP_TRY(dmalloc(c, &c->d_edit_stage, need));
+            c->edit_stage_bytes = need;
+        }
+        c->main_dirty = true;
+        HIP_TRY(hipMemcpyAsync(c->d_edit_stage, mat, nv, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_edit_stage + rgb_at, rgb, 3 * nv, hipMemcpyHostToDevice, c->stream));
+        box_mat = (const int8_t*)c->d_edit_stage;
+        box_rgb = c->d_edit_stage + rgb_at;
+    }
+    c->main_dirty = true;
+    HIP_TRY(launch_edit(c->stream, c->cfg.grid_res, box, box_mat, box_rgb, c->d_mat, c->d_rgb, c->d_grid, c->d_l0, c->d_l1, c->d_l2, c->d_l3,
+                        c->d_l0c, c->d_l0c_base, c->d_cull));
+    return read_cull_record(c);   // (the wait also ends the loan of the host arrays)
+}
 int vrt_sky_accumulate_clouds(vrt_ctx* c, int max_samples) {
     if (!c || max_samples <= 0) return fail(VRT_E_INVALID, "bad argument");
     if (!c->prepared || c->scene.use_physical_sky != 1) return fail(VRT_E_STATE, "needs vrt_prepare with use_physical_sky");

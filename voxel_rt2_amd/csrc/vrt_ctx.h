@@ -112,6 +112,8 @@ struct vrt_ctx {
     bool cull_active = false;        // the grown box leaves part of the grid out: there are rays to cull (read back by vrt_prepare)
     bool dense_grid = false;         // half of the bricks or more are non-empty (read back by vrt_prepare)
     float* d_cull = nullptr;         // [8] grown bounding box of the solid voxels + flag, [8] the same with the flag off (cull_ray, vrt_trace.h)
+    uint8_t* d_edit_stage = nullptr;  // vrt_update_voxels, host path: the box arrays on their way to k_edit_store (grown on demand)
+    size_t edit_stage_bytes = 0;
     float* d_mats = nullptr;
     Counters* d_counters = nullptr;
     unsigned* d_work = nullptr;

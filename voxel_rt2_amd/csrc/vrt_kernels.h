@@ -12,6 +12,7 @@
 #include "vrt_restir.h"
 #include "vrt_temporal.h"
 #include "vrt_plan.h"
+#include "vrt_edit.h"
 
 #define VRT_RENDER_THREADS 256
 #ifndef VRT_RENDER_MIN_WAVES
@@ -40,6 +41,11 @@ struct ProbeOut;   // vrt_probe.h (test hook; vrt_kernels.hip and vrt_api.hip in
 hipError_t launch_prepare(hipStream_t st, int grid_res, const int8_t* mat, const uint8_t* rgb, uint32_t* grid, unsigned long long* l0,
                           unsigned long long* l1, unsigned long long* l2, unsigned long long* l3, unsigned long long* l0c, uint32_t* l0c_base,
                           float* cull /*[6]: cull_ray()'s box, vrt_trace.h*/);
+// vrt_update_voxels: the voxels of `box` (valid, not empty) replaced by box_mat / box_rgb (device memory, [hx][hy][hz] and [hx][hy][hz][3]),
+// and everything launch_prepare derives from them brought up to date -- the levels' words the box touches, l0c and the culling box whole
+hipError_t launch_edit(hipStream_t st, int grid_res, const EditBox& box, const int8_t* box_mat, const uint8_t* box_rgb, int8_t* mat, uint8_t* rgb,
+                       uint32_t* grid, unsigned long long* l0, unsigned long long* l1, unsigned long long* l2, unsigned long long* l3,
+                       unsigned long long* l0c, uint32_t* l0c_base, float* cull);
 hipError_t query_render_residency(int grid_res, bool restir, bool instr, int* blocks_per_cu);
 hipError_t launch_render(hipStream_t st, int grid_res, bool restir, bool instr, int n_blocks, const FrameParams& fp, const SceneData& sc,
                          const PixelBuffers& out, unsigned* work_counters, unsigned launch_seq, int n_samples, int chunk_override);

@@ -137,6 +137,25 @@ __global__ void k_build_l0c(const unsigned long long* __restrict__ l0, const uns
     }
 }
 
+// ---- vrt_update_voxels: the same data for a box of voxels (vrt_edit.h holds the arithmetic) -----
+// One thread per voxel of the box, z fastest: a wave reads runs of the box arrays and writes runs of hz voxels of the grid's.
+template <int G>
+__global__ void k_edit_store(EditBox box, const int8_t* __restrict__ box_mat, const uint8_t* __restrict__ box_rgb, int8_t* __restrict__ mat,
+                             uint8_t* __restrict__ rgb, uint32_t* __restrict__ grid) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < edit_box_voxels(box)) edit_store_voxel<G>(box, i, box_mat, box_rgb, mat, rgb, grid);
+}
+// One thread per 4x4x4 brick the box touches.
+__global__ void k_edit_fine(EditBox box, const int8_t* __restrict__ mat, unsigned long long* __restrict__ l0, int G) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < edit_cell_count(edit_cells(box, 2))) edit_rebuild_fine(box, i, mat, l0, G);
+}
+// One thread per word the box touches of the level with cells of (1 << shift) voxels.
+__global__ void k_edit_coarse(EditBox box, int shift, const unsigned long long* __restrict__ fine, unsigned long long* __restrict__ coarse, int G) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < edit_cell_count(edit_cells(box, shift))) edit_rebuild_coarse(box, shift, i, fine, coarse, G);
+}
+
 // ---- render ----------------------------------------------------------------------------------
 // OOB: the instantiation can read cells outside the grid the reference's way (oob_capable_of, vrt_trace.h).  It is the INSTRUMENTED
 // instantiations that can (a context with vrt_set_reference_indexing launches those): the timed kernels carry no test for it.
@@ -996,6 +1015,31 @@ hipError_t launch_prepare(hipStream_t st, int G, const int8_t* mat, const uint8_
     } else {         // the compacted fine level of the pooled kernel's LDS copy (128^3 only)
         hipLaunchKernelGGL(k_build_l0c, dim3(1), dim3(512), 0, st, (const unsigned long long*)l0, (const unsigned long long*)l1, l0c, l0c_base);
     }
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+// What launch_prepare leaves, for a grid that differs from the prepared one inside `box` (valid and not empty: the caller checks).
+// Box-sized: store and pack, the fine words, the l1 and l2 words the box touches, each level after the one below it.  Whole-level,
+// as in launch_prepare: the l3 word or the compacted fine level (one new brick moves every later word of it), and the culling box --
+// they cost bricks, not voxels.
+hipError_t launch_edit(hipStream_t st, int G, const EditBox& box, const int8_t* box_mat, const uint8_t* box_rgb, int8_t* mat, uint8_t* rgb,
+                       uint32_t* grid, unsigned long long* l0, unsigned long long* l1, unsigned long long* l2, unsigned long long* l3,
+                       unsigned long long* l0c, uint32_t* l0c_base, float* cull) {
+    const int n = edit_box_voxels(box);
+    if (G == 256) hipLaunchKernelGGL(k_edit_store<256>, dim3((n + 255) / 256), dim3(256), 0, st, box, box_mat, box_rgb, mat, rgb, grid);
+    else hipLaunchKernelGGL(k_edit_store<128>, dim3((n + 255) / 256), dim3(256), 0, st, box, box_mat, box_rgb, mat, rgb, grid);
+    VRT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_edit_fine, dim3((edit_cell_count(edit_cells(box, 2)) + 63) / 64), dim3(64), 0, st, box, (const int8_t*)mat, l0, G);
+    VRT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_edit_coarse, dim3((edit_cell_count(edit_cells(box, 4)) + 63) / 64), dim3(64), 0, st, box, 4, (const unsigned long long*)l0, l1, G);
+    VRT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_edit_coarse, dim3((edit_cell_count(edit_cells(box, 6)) + 63) / 64), dim3(64), 0, st, box, 6, (const unsigned long long*)l1, l2, G);
+    VRT_LAUNCH_CHECK();
+    if (G == 256) hipLaunchKernelGGL(k_edit_coarse, dim3(1), dim3(64), 0, st, box, 8, (const unsigned long long*)l2, l3, G);
+    else hipLaunchKernelGGL(k_build_l0c, dim3(1), dim3(512), 0, st, (const unsigned long long*)l0, (const unsigned long long*)l1, l0c, l0c_base);
+    VRT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_cull_box, dim3(1), dim3(256), 0, st, (const unsigned long long*)l0, G / 4, cull);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -59,6 +59,7 @@ class VoxelStore:
         self.voxel_material = np.frombuffer(self._mat, dtype=np.int8).reshape(g, g, g)
         self.voxel_color = np.frombuffer(self._rgb, dtype=np.uint8).reshape(g, g, g, 3)
         self._voxels_dirty = True
+        self._dirty_lo, self._dirty_hi = [0, 0, 0], [g, g, g]   # bounding box of the voxels written since the last upload
 
     def set_voxel(self, idx, mat, color):
         g = self.voxel_grid_res
@@ -75,6 +76,15 @@ class VoxelStore:
             c = 0.0 if c < 0.0 else (1.0 if c > 1.0 else c)
             rgb[j + k] = int(_f32(c * 255.0))
         self._voxels_dirty = True
+        lo, hi = self._dirty_lo, self._dirty_hi
+        if lo[0] >= hi[0]:   # nothing written since the last upload
+            lo[:], hi[:] = (x, y, z), (x + 1, y + 1, z + 1)
+        else:
+            for a, v in enumerate((x, y, z)):
+                if v < lo[a]:
+                    lo[a] = v
+                if v >= hi[a]:
+                    hi[a] = v + 1
 
     def get_voxel(self, ijk):
         g = self.voxel_grid_res
@@ -91,6 +101,16 @@ class VoxelStore:
         self.voxel_material[...] = mat
         self.voxel_color[...] = rgb
         self._voxels_dirty = True
+        g = self.voxel_grid_res
+        self._dirty_lo, self._dirty_hi = [0, 0, 0], [g, g, g]
+
+    def dirty_box(self):
+        """(lo, hi): bounding box [lo, hi) of the voxels written since the last upload, in array indices; lo == hi: none."""
+        return tuple(self._dirty_lo), tuple(self._dirty_hi)
+
+    def _voxels_uploaded(self):
+        self._voxels_dirty = False
+        self._dirty_lo, self._dirty_hi = [0, 0, 0], [0, 0, 0]
 
 
 class Renderer(VoxelStore):
@@ -204,8 +224,24 @@ class Renderer(VoxelStore):
         self._push()
         if self._voxels_dirty:
             self._s.upload_voxels(self.voxel_material, self.voxel_color)
-            self._voxels_dirty = False
+            self._voxels_uploaded()
         self._s.prepare()
+        self._prepared = True
+
+    def update_voxels(self, reset=True):
+        """Send the voxels written since the last upload (set_voxel, set_voxel_arrays) to a scene that prepare_data() has already
+        prepared, as one box: the library brings texels, occupancy pyramid and culling box up to date at the box's cost and leaves
+        the sky precompute alone (include/vrt_api.h, vrt_update_voxels).  reset: start a fresh accumulation (reset_framebuffer).
+        Before the first prepare_data() this IS prepare_data().  No counterpart in the reference."""
+        if not getattr(self, "_prepared", False):
+            self.prepare_data()
+        elif self._voxels_dirty:
+            self._push()
+            (x0, y0, z0), (x1, y1, z1) = self.dirty_box()
+            self._s.update_voxels((x0, y0, z0), (x1, y1, z1), self.voxel_material[x0:x1, y0:y1, z0:z1], self.voxel_color[x0:x1, y0:y1, z0:z1])
+            self._voxels_uploaded()
+        if reset:
+            self.reset_framebuffer()
 
     def accumulate_clouds(self, max_samples):
         self._push()
