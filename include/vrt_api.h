@@ -148,6 +148,39 @@ int vrt_prepare(vrt_ctx* ctx);
  * vrt_upload_voxels that no vrt_prepare has followed; an empty box returns VRT_OK and does nothing.  No counterpart in the
  * reference: its scene is authored before finish(), which never returns. */
 int vrt_update_voxels(vrt_ctx* ctx, const int32_t lo[3], const int32_t hi[3], const void* mat, const void* rgb, int on_device);
+/* Ask a PREPARED scene: n caller-supplied rays, in WORLD units, through the reference's next_hit (pathtracer.py:218-244: floor plane,
+ * hierarchical DDA, surface lookup) on the context's current grid, floor, voxel_edges and scene parameters, in the mode
+ * vrt_set_reference_indexing selected -- a query sees what the frames see.  Ray k gets next_hit(origin, dir, t_max,
+ * shadow_ray = flags & VRT_RAY_ANY_HIT) in hits[k]:
+ *   t       distance along the ray.  Directions are NOT normalised (the render's are not either): the hit point is origin + t * dir,
+ *           and t is a distance in world units only for a unit dir;
+ *   kind    VRT_HIT_MISS / VRT_HIT_FLOOR / VRT_HIT_VOXEL;
+ *   cell    the voxel, in the index space of vrt_upload_voxels -- what vrt_update_voxels takes as lo (hi = lo + 1); -1 for the floor
+ *           (with vrt_set_reference_indexing a "hit" outside the grid reports the coordinate -1 or grid_res it was read at);
+ *   normal  facing the ray; albedo, mat_id: the edge-darkened colour (voxel_edges) and the material byte as the texel decodes it, or
+ *           the floor's.  Zero for a VRT_RAY_ANY_HIT ray: no surface lookup is made for it; t, kind and cell are filled as for a full hit.
+ * A miss is: nothing nearer than t_max (strictly: t < t_max, the floor tested first, so a floor / voxel tie is the floor's): t = +inf,
+ * kind = 0, cell = -1, everything else zero.  t_max = +inf is the ordinary case.  INVALID rays are not walked and get the miss record:
+ * a non-finite origin or direction component, a direction of all zeros, t_max NaN or <= 0.  Every other ray ends: the walk takes at
+ * most 512 steps (raytracer.py:103) and a step descends at most one level per query, whatever finite values the ray holds.
+ * on_device = 0: host arrays, borrowed for the call, staged in chunks (n is limited by memory only); the call returns when `hits` is
+ * filled.  on_device = 1: both are device memory (a torch tensor's data_ptr()); the work is only queued on the context's stream, no
+ * host synchronisation -- the caller keeps both unchanged until work queued on that stream behind the call has run.  Ordered like
+ * vrt_update_voxels: a query queued after an edit sees the new grid, one queued before it the old.
+ * The query READS scene data and nothing else: no history, g-buffer, counter, frame number or statistic is touched, the pending
+ * accumulation (vrt_accumulate) is not forced, and frames rendered around it are bit for bit the frames rendered without it.
+ * VRT_E_INVALID: NULL arguments, n < 0, on_device not 0 or 1; VRT_E_STATE: before vrt_prepare, or after a vrt_upload_voxels that no
+ * vrt_prepare has followed; n = 0 returns VRT_OK.  No counterpart in the reference: next_hit is a ti.func of its render kernel. */
+typedef struct vrt_ray { float origin[3]; float t_max; float dir[3]; uint32_t flags; } vrt_ray;   /* 32 bytes */
+typedef struct vrt_ray_hit { float t; int32_t kind; int32_t cell[3]; float normal[3]; float albedo[3]; int32_t mat_id; } vrt_ray_hit;   /* 48 bytes */
+enum { VRT_HIT_MISS = 0, VRT_HIT_FLOOR = 1, VRT_HIT_VOXEL = 2 };
+enum { VRT_RAY_ANY_HIT = 1 };
+int vrt_cast_rays(vrt_ctx* ctx, int64_t n, const vrt_ray* rays, vrt_ray_hit* hits, int on_device);
+/* The mirror image of vrt_update_voxels: the stored materials and colours of the box [lo, hi) copied out as mat int8[hx][hy][hz] and
+ * rgb uint8[hx][hy][hz][3] -- what a program reads after device-side edits, which the host never saw.  on_device = 0: host arrays, the
+ * call synchronises; 1: device memory, queued on the context's stream.  Box rules and error codes are vrt_update_voxels'; the pending
+ * accumulation is not forced. */
+int vrt_fetch_voxels(vrt_ctx* ctx, const int32_t lo[3], const int32_t hi[3], void* mat, void* rgb, int on_device);
 /* Renderer.accumulate_clouds / compute_atmosphere (pathtracer.py:325-329) */
 int vrt_sky_accumulate_clouds(vrt_ctx* ctx, int max_samples);
 int vrt_sky_compute_slice(vrt_ctx* ctx, int slice_idx, int max_slices);

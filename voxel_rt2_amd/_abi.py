@@ -1,11 +1,20 @@
 """ctypes mirror of include/vrt_api.h (structs and constants only; no library is loaded here)."""
 import ctypes as C
 
+import numpy as np
+
 VRT_OK = 0
 VRT_E_INVALID, VRT_E_DEVICE, VRT_E_STATE = -1, -2, -3
 
 BUF_GBUF_DEPTH, BUF_GBUF_NORMAL, BUF_GBUF_POSITION, BUF_GBUF_MAT, BUF_GBUF_REFL_DEPTH = 1, 2, 3, 4, 5
 BUF_HISTORY_DIFFUSE, BUF_HISTORY_SPECULAR, BUF_SKY_SCATTERING, BUF_SKY_TRANSMITTANCE, BUF_TRANS_LUT = 6, 7, 8, 9, 10
+HIT_MISS, HIT_FLOOR, HIT_VOXEL = 0, 1, 2
+RAY_ANY_HIT = 1
+# vrt_ray / vrt_ray_hit (vrt_cast_rays): arrays of these go in and come out
+RAY = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("dir", np.float32, 3), ("flags", np.uint32)])
+HIT = np.dtype([("t", np.float32), ("kind", np.int32), ("cell", np.int32, 3), ("normal", np.float32, 3), ("albedo", np.float32, 3),
+                ("mat_id", np.int32)])
+assert RAY.itemsize == 32 and HIT.itemsize == 48
 
 
 class VrtConfig(C.Structure):
@@ -67,6 +76,8 @@ def declare(lib, prefix):
     sig("set_camera", C.c_int, P, C.POINTER(VrtCamera))
     sig("prepare", C.c_int, P)
     sig("update_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
+    sig("cast_rays", C.c_int, P, C.c_int64, P, P, C.c_int)
+    sig("fetch_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
     sig("sky_accumulate_clouds", C.c_int, P, C.c_int)
     sig("sky_compute_slice", C.c_int, P, C.c_int, C.c_int)
     sig("sky_accumulate_clouds_slice", C.c_int, P, C.c_int, C.c_int, C.c_int)

@@ -90,6 +90,46 @@ class NativeSession:
             pm, pr = mat.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p)
         self._call("update_voxels", (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), pm, pr, int(bool(on_device)))
 
+    def cast_rays(self, rays, out=None, n=None):
+        """Rays against the prepared scene (include/vrt_api.h, vrt_cast_rays).  Host path: `rays` is an array of _abi.RAY, the result
+        an array of _abi.HIT (`out` if given).  Device path: `rays` and `out` are torch tensors on the device holding the same 32-
+        and 48-byte records (any dtype; `n` rays, by default as many as `rays` holds); the work is queued on the session's stream and
+        `out` is returned, not yet filled."""
+        if hasattr(rays, "data_ptr"):
+            if out is None or not hasattr(out, "data_ptr"):
+                raise ValueError("device path: `out` is a device tensor of 48 bytes a ray")
+            count = rays.numel() * rays.element_size() // _abi.RAY.itemsize if n is None else int(n)
+            if rays.numel() * rays.element_size() < count * _abi.RAY.itemsize or out.numel() * out.element_size() < count * _abi.HIT.itemsize:
+                raise ValueError(f"{count} rays need {count * 32} bytes of rays and {count * 48} bytes of records")
+            if not (rays.is_contiguous() and out.is_contiguous()):
+                raise ValueError("device tensors must be contiguous")
+            self._call("cast_rays", C.c_int64(count), C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr()), 1)
+            return out
+        rays = np.ascontiguousarray(rays, dtype=_abi.RAY).reshape(-1)
+        if out is None:
+            out = np.empty(len(rays), _abi.HIT)
+        if out.dtype != _abi.HIT or out.shape != rays.shape or not out.flags.c_contiguous:
+            raise ValueError("`out` must be a contiguous array of _abi.HIT, one record a ray")
+        if len(rays):   # (an empty array's pointer may be NULL, which the library refuses whatever n is)
+            self._call("cast_rays", C.c_int64(len(rays)), rays.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), 0)
+        return out
+
+    def fetch_voxels(self, lo, hi, mat=None, rgb=None, on_device=False):
+        """The stored voxels of the box [lo, hi) (include/vrt_api.h, vrt_fetch_voxels).  Host path: returns (mat, rgb), arrays of shape
+        hi - lo and (hi - lo, 3).  Device path (on_device=True): `mat` and `rgb` are integer device pointers to int8[hx][hy][hz] and
+        uint8[hx][hy][hz][3], written on the session's stream."""
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError("lo and hi are three coordinates each")
+        if on_device:
+            self._call("fetch_voxels", (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), C.c_void_p(int(mat)), C.c_void_p(int(rgb)), 1)
+            return None
+        shape = tuple(max(h - l, 0) for l, h in zip(lo, hi))
+        mat, rgb = np.zeros(shape, np.int8), np.zeros(shape + (3,), np.uint8)
+        if mat.size:   # (an empty box copies nothing, and an empty array's pointer may be NULL, which the library refuses)
+            self._call("fetch_voxels", (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), mat.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p), 0)
+        return mat, rgb
+
     def upload_materials(self, table):
         table = np.ascontiguousarray(table, dtype=np.float32)
         if table.shape != (128, 14):

@@ -440,6 +440,70 @@ int vrt_update_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], cons
                         c->d_l0c, c->d_l0c_base, c->d_cull));
     return read_cull_record(c);   // (the wait also ends the loan of the host arrays)
 }
+// ---- asking the scene: vrt_cast_rays, vrt_fetch_voxels -------------------------------------------------------------------------
+// Both READ scene data (pyramid, texels, stored voxels), on the context's stream: behind every edit queued so far, ahead of every
+// later one.  Render launches read the same data on their own streams and nothing here writes what they or their passes touch, so
+// neither main_dirty nor the pending accumulation is concerned: no enter(), no flush.
+static int ensure_cast_stage(vrt_ctx* c, size_t need) {
+    if (c->cast_stage_bytes >= need) return VRT_OK;
+    HIP_TRY(dfree(c, &c->d_cast_stage));   // (hipFree waits for the device: no kernel is still using the old one)
+    c->cast_stage_bytes = 0;
+    HIP_TRY(dmalloc(c, &c->d_cast_stage, need));
+    c->cast_stage_bytes = need;
+    return VRT_OK;
+}
+int vrt_cast_rays(vrt_ctx* c, int64_t n, const vrt_ray* rays, vrt_ray_hit* hits, int on_device) {
+    if (!c || !rays || !hits) return fail(VRT_E_INVALID, "null argument");
+    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    if (!c->prepared) return fail(VRT_E_STATE, "vrt_cast_rays asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
+    if (n == 0) return VRT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const FrameParams fp = make_frame_params(c);   // (the floor and voxel_edges are what a query reads of it)
+    SceneData sc = make_scene_data(c);
+    // the scene's box, whatever the render launches count: culled rays are misses either way (cast_row); not with the reference's
+    // indexing, where a ray clear of every solid voxel can still "hit" outside the grid (plan_render_variant)
+    sc.cull = c->d_cull + (c->cull_active && !c->ref_oob && c->knobs.cull != 0 ? 0 : 8);
+    const bool staged = plan_cast_staged((long long)n, c->knobs.cast_view);
+    if (on_device) {
+        HIP_TRY(launch_cast_rays(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, fp, sc, (long long)n, rays, hits));
+        return VRT_OK;
+    }
+    const size_t chunk = (size_t)std::min<long long>(plan_cast_chunk(), (long long)n);
+    if (ensure_cast_stage(c, chunk * (sizeof(vrt_ray) + sizeof(vrt_ray_hit))) != VRT_OK) return VRT_E_DEVICE;
+    vrt_ray* d_rays = (vrt_ray*)c->d_cast_stage;
+    vrt_ray_hit* d_hits = (vrt_ray_hit*)(c->d_cast_stage + chunk * sizeof(vrt_ray));
+    for (size_t at = 0; at < (size_t)n; at += chunk) {   // (stream order lets chunk k + 1 reuse what chunk k's copy back has read)
+        const size_t m = std::min(chunk, (size_t)n - at);
+        HIP_TRY(hipMemcpyAsync(d_rays, rays + at, m * sizeof(vrt_ray), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(launch_cast_rays(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, fp, sc, (long long)m, d_rays, d_hits));
+        HIP_TRY(hipMemcpyAsync(hits + at, d_hits, m * sizeof(vrt_ray_hit), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host arrays)
+    return VRT_OK;
+}
+int vrt_fetch_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], void* mat, void* rgb, int on_device) {
+    if (!c || !lo || !hi || !mat || !rgb) return fail(VRT_E_INVALID, "null argument");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    EditBox box;
+    for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
+    if (!edit_box_valid(box, c->cfg.grid_res)) return fail(VRT_E_INVALID, "the box must satisfy 0 <= lo <= hi <= grid_res on every axis");
+    if (!c->prepared) return fail(VRT_E_STATE, "vrt_fetch_voxels reads a prepared grid: call vrt_prepare first (also after vrt_upload_voxels)");
+    const size_t nv = (size_t)edit_box_voxels(box);
+    if (nv == 0) return VRT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (on_device) {
+        HIP_TRY(launch_fetch_voxels(c->stream, c->cfg.grid_res, box, c->d_mat, c->d_rgb, (int8_t*)mat, (uint8_t*)rgb));
+        return VRT_OK;
+    }
+    const size_t rgb_at = (nv + 255) & ~(size_t)255;
+    if (ensure_cast_stage(c, rgb_at + 3 * nv) != VRT_OK) return VRT_E_DEVICE;
+    HIP_TRY(launch_fetch_voxels(c->stream, c->cfg.grid_res, box, c->d_mat, c->d_rgb, (int8_t*)c->d_cast_stage, c->d_cast_stage + rgb_at));
+    HIP_TRY(hipMemcpyAsync(mat, c->d_cast_stage, nv, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(rgb, c->d_cast_stage + rgb_at, 3 * nv, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(sync_stream_only(c, c->stream));
+    return VRT_OK;
+}
 int vrt_sky_accumulate_clouds(vrt_ctx* c, int max_samples) {
     if (!c || max_samples <= 0) return fail(VRT_E_INVALID, "bad argument");
     if (!c->prepared || c->scene.use_physical_sky != 1) return fail(VRT_E_STATE, "needs vrt_prepare with use_physical_sky");

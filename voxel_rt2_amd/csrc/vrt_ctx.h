@@ -114,6 +114,8 @@ struct vrt_ctx {
     float* d_cull = nullptr;         // [8] grown bounding box of the solid voxels + flag, [8] the same with the flag off (cull_ray, vrt_trace.h)
     uint8_t* d_edit_stage = nullptr;  // vrt_update_voxels, host path: the box arrays on their way to k_edit_store (grown on demand)
     size_t edit_stage_bytes = 0;
+    uint8_t* d_cast_stage = nullptr;  // vrt_cast_rays / vrt_fetch_voxels, host path: rays in and records out, or the box arrays on their way out (grown on demand)
+    size_t cast_stage_bytes = 0;
     float* d_mats = nullptr;
     Counters* d_counters = nullptr;
     unsigned* d_work = nullptr;
@@ -280,6 +282,12 @@ static void wait_bounded(vrt_ctx* c, Query query, Idle idle) {
         idle(waited);
     }
     (void)hipGetLastError();
+}
+// The same wait without the flush: for the entry points that read scene data only (vrt_cast_rays, vrt_fetch_voxels) and so leave the
+// pending accumulation where it is.
+static hipError_t sync_stream_only(vrt_ctx* c, hipStream_t st) {
+    wait_bounded(c, [&] { return hipStreamQuery(st); }, [](double) { std::this_thread::yield(); });
+    return hipStreamSynchronize(st);
 }
 // hipStreamSynchronize with that bound on how long a gated launch may hold the stream.
 static hipError_t sync_guarded(vrt_ctx* c, hipStream_t st) {

@@ -13,6 +13,7 @@
 #include "vrt_temporal.h"
 #include "vrt_plan.h"
 #include "vrt_edit.h"
+#include "vrt_cast.h"
 
 #define VRT_RENDER_THREADS 256
 #ifndef VRT_RENDER_MIN_WAVES
@@ -46,6 +47,13 @@ hipError_t launch_prepare(hipStream_t st, int grid_res, const int8_t* mat, const
 hipError_t launch_edit(hipStream_t st, int grid_res, const EditBox& box, const int8_t* box_mat, const uint8_t* box_rgb, int8_t* mat, uint8_t* rgb,
                        uint32_t* grid, unsigned long long* l0, unsigned long long* l1, unsigned long long* l2, unsigned long long* l3,
                        unsigned long long* l0c, uint32_t* l0c_base, float* cull);
+// vrt_cast_rays: n rays (device memory) through cast_row (vrt_cast.h).  staged: the coarse pyramid levels in LDS, as k_render stages them;
+// else everything through global memory.  oob: the instantiation that can read outside the grid the reference's way (sc.pyr.ref_oob).
+// The grid is n_cu x the kernel's residency at most (plan_cast_blocks).
+hipError_t launch_cast_rays(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n,
+                            const vrt_ray* rays, vrt_ray_hit* hits);
+// vrt_fetch_voxels: the stored voxels of `box` (valid, not empty) gathered into box_mat / box_rgb (device memory)
+hipError_t launch_fetch_voxels(hipStream_t st, int grid_res, const EditBox& box, const int8_t* mat, const uint8_t* rgb, int8_t* box_mat, uint8_t* box_rgb);
 hipError_t query_render_residency(int grid_res, bool restir, bool instr, int* blocks_per_cu);
 hipError_t launch_render(hipStream_t st, int grid_res, bool restir, bool instr, int n_blocks, const FrameParams& fp, const SceneData& sc,
                          const PixelBuffers& out, unsigned* work_counters, unsigned launch_seq, int n_samples, int chunk_override);

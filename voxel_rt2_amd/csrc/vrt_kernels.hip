@@ -14,6 +14,7 @@
 //   k_temporal_frame_prev                                 the same, moving camera on a row tile with history exchange
 //   k_temporal_group                                      the passes of several consecutive launches in one (static camera)
 //   k_tonemap                                             LDR presentation
+//   k_cast_rays / k_fetch_voxels                          vrt_cast_rays: caller-supplied rays through next_hit; vrt_fetch_voxels
 //
 // k_render is a persistent-thread kernel: the grid is sized to the device's residency, each wave
 // keeps 64 path records in registers and pulls pixels (8x8 tiles, tile-major order) from a global
@@ -992,6 +993,55 @@ __global__ __launch_bounds__(64) void k_shade_probe(FrameParams fp, SceneData sc
                     lane_tables ? lane_tables + (size_t)i * VRT_SHADE_LANE_TABLE : nullptr);
 }
 
+// ---- vrt_cast_rays: caller-supplied rays through next_hit (vrt_cast.h holds the per-ray body) ----------------------------------
+// One ray per lane, a grid-stride loop over the batch; the grid is what fits on the chip (plan_cast_blocks), so a workgroup stages
+// the pyramid once however many rays it walks.  STAGED: the coarse levels in LDS exactly as k_render keeps them for LdsPyramid (at
+// 256^3 the 32 KiB l1 level), the fine level through L2; else the batch is small and everything is read from global memory.
+// OOB (STAGED only; GlobalPyramid always can): the instantiation carries the reference's reading of cells outside the grid.
+// VRT_RAY_ANY_HIT is a property of a ray, the surface lookup it saves one of the instantiation: a wave whose rays all carry the
+// flag runs cast_row<true>; a mixed wave runs cast_row<false> once for all of them and drops the lookup's result on the flagged
+// lanes, which is the same record (the walk does not depend on the flag), so no wave walks twice.
+template <int G, bool STAGED, bool OOB>
+__global__ __launch_bounds__(256) void k_cast_rays(FrameParams fp, SceneData sc, long long n, const vrt_ray* __restrict__ rays, vrt_ray_hit* __restrict__ hits) {
+    constexpr int N1 = GridDim<G>::n1 * GridDim<G>::n1 * GridDim<G>::n1, N2 = GridDim<G>::n2 * GridDim<G>::n2 * GridDim<G>::n2;
+    __shared__ unsigned long long s_l1[STAGED ? N1 : 1];
+    __shared__ unsigned long long s_l2[STAGED ? N2 : 1];
+    __shared__ float s_cull[8];
+    typename std::conditional<STAGED, LdsPyramid<G, OOB>, GlobalPyramid<G>>::type P;
+    SceneData scl = sc;
+    if constexpr (STAGED) {
+        for (int i = threadIdx.x; i < N1; i += blockDim.x) s_l1[i] = sc.pyr.l1[i];
+        if (threadIdx.x < N2) s_l2[threadIdx.x] = sc.pyr.l2[threadIdx.x];
+        if (threadIdx.x < 8) s_cull[threadIdx.x] = sc.cull[threadIdx.x];
+        __syncthreads();
+        P.l0 = sc.pyr.l0; P.l1 = s_l1; P.l2 = s_l2;
+        P.w3 = (G == 256) ? sc.pyr.l3[0] : 0ULL;
+        P.oob = sc.pyr.ref_oob != 0;
+        scl.cull = s_cull;
+    } else {
+        P.p = sc.pyr;
+    }
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const vrt_ray r = rays[i];
+        const bool any = (r.flags & VRT_RAY_ANY_HIT) != 0u;
+        vrt_ray_hit h;
+        if (__all(any)) {
+            cast_row<true>(fp, scl, P, r, h);
+        } else {
+            cast_row<false>(fp, scl, P, r, h);
+            if (any) cast_strip_surface(h);
+        }
+        hits[i] = h;
+    }
+}
+// vrt_fetch_voxels: one thread per voxel of the box, z fastest (k_edit_store the other way round)
+__global__ void k_fetch_voxels(EditBox box, int G, const int8_t* __restrict__ mat, const uint8_t* __restrict__ rgb, int8_t* __restrict__ box_mat,
+                               uint8_t* __restrict__ box_rgb) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < edit_box_voxels(box)) fetch_box_voxel(box, G, i, mat, rgb, box_mat, box_rgb);
+}
+
 // ---- host-side launchers -----------------------------------------------------------------------
 #define VRT_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
@@ -1168,6 +1218,25 @@ hipError_t launch_trace_probe(hipStream_t st, int grid_res, int walk, const Pyra
     else if (walk == PROBE_WALK_FLAT) VRT_BY_GRID(grid_res, hipLaunchKernelGGL((k_trace_probe<G, PROBE_WALK_FLAT>), g, b, 0, st, pyr, cull, n, rays, out));
     else if (walk == PROBE_WALK_RECORD) VRT_BY_GRID(grid_res, hipLaunchKernelGGL((k_trace_probe<G, PROBE_WALK_RECORD>), g, b, 0, st, pyr, cull, n, rays, out));
     else return hipErrorInvalidValue;
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+typedef void (*cast_kernel_fn)(FrameParams, SceneData, long long, const vrt_ray*, vrt_ray_hit*);
+hipError_t launch_cast_rays(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n,
+                            const vrt_ray* rays, vrt_ray_hit* hits) {
+    cast_kernel_fn fn = nullptr;
+    if (staged) VRT_BY_GRID(grid_res, VRT_BY_2(oob, false, fn = (k_cast_rays<G, true, A>)));
+    else VRT_BY_GRID(grid_res, fn = (k_cast_rays<G, false, true>));
+    int per_cu = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fn, dim3(plan_cast_blocks(n, n_cu, per_cu)), dim3(256), 0, st, fp, sc, n, rays, hits);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_fetch_voxels(hipStream_t st, int grid_res, const EditBox& box, const int8_t* mat, const uint8_t* rgb, int8_t* box_mat, uint8_t* box_rgb) {
+    hipLaunchKernelGGL(k_fetch_voxels, dim3((edit_box_voxels(box) + 255) / 256), dim3(256), 0, st, box, grid_res, mat, rgb, box_mat, box_rgb);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -25,7 +25,7 @@
 // A build with -DVRT_DEV_KNOBS (build_variants/libvrt_dev.so: `python -m voxel_rt2_amd.build --variant dev -DVRT_DEV_KNOBS`,
 // loaded by tests/test_gpu_pipeline.py and the A/B runs of tools/) adds the development switches: the fault-injection hook
 // VRT_TEST_FAIL_LAUNCH and the A/B switches VRT_CULL, VRT_DENSE, VRT_DEEP_ITEMS, VRT_DEEPER_ITEMS, VRT_STREAMS, VRT_GRID_DIV,
-// VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER, VRT_PASS_STREAM.
+// VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER, VRT_PASS_STREAM, VRT_CAST_VIEW.
 struct Knobs {
     int render = -1;               // -1: the library's choice, 0: fused, 1: pool; -2: a value VRT_RENDER does not know
     bool overlap = true;
@@ -39,6 +39,7 @@ struct Knobs {
     bool drain_gate = true, fuse_restir = true, overlap_single = true;
     int max_fused = VRT_MAX_FUSED, full_below = 2, chunk = 0, fail_launch = -1, gate_extra = 0, time_every = 0;
     int defer4 = VRT_DEFER_4DEEP, defer8 = 1;   // render launches whose accumulation runs as one pass, per pipeline depth (VRT_DEFER: both)
+    int cast_view = -1;            // -1: by the batch size (plan_cast_staged), 0: k_cast_rays on the pyramid in global memory, 1: coarse levels staged in LDS
 };
 static Knobs read_knobs() {
     Knobs k;
@@ -64,6 +65,7 @@ static Knobs read_knobs() {
     if (const char* e = getenv("VRT_FULL_BELOW")) { const int v = atoi(e); if (v >= 1 && v <= 3) k.full_below = v; }
     if (const char* e = getenv("VRT_DEFER")) { const int v = atoi(e); if (v >= 0 && v <= VRT_MAX_DEFER) k.defer4 = k.defer8 = v < 1 ? 1 : v; }   // 0, 1: a pass per launch
     if (const char* e = getenv("VRT_CHUNK")) { const int v = atoi(e); if (v >= 64 && v <= 4096) k.chunk = v / 64 * 64; }
+    if (const char* e = getenv("VRT_CAST_VIEW")) k.cast_view = strcmp(e, "staged") == 0 ? 1 : strcmp(e, "global") == 0 ? 0 : -1;
 #endif
     return k;
 }
@@ -192,3 +194,22 @@ static inline int plan_partial_blocks(int all_blocks, int grid_div) { return (al
 // launches take turns.
 static inline int plan_set_of(unsigned pipe_seq, int n_sets) { return (int)(pipe_seq % (unsigned)n_sets); }
 static inline int plan_lane_of(unsigned pipe_seq, int n_streams) { return (int)(pipe_seq % (unsigned)n_streams); }
+
+// ---- vrt_cast_rays -----------------------------------------------------------------------------------------------------------
+// Which view of the pyramid a batch of n rays is walked on: the coarse levels staged in LDS once per workgroup (k_render's
+// LdsPyramid), or everything through global memory.  Staging is 4 KiB + 64 B a workgroup at 128^3 and 32.5 KiB at 256^3: a cost per
+// WORKGROUP, which a grid sized from the CU count pays a bounded number of times, but which a pick of one ray or a fan of a few
+// hundred pays in full for next to no walking.  VRT_CAST_STAGED_MIN is meant to be where the two curves of tools/cast_rate.py cross on s1;
+// that tool has not run on an MI355X yet, so 4096 -- sixteen workgroups' worth of rays -- is PROVISIONAL.  Results do
+// not depend on it (both instantiations give the same bytes: tests/test_gpu_cast_rays.py).  `knob`: Knobs::cast_view.
+#ifndef VRT_CAST_STAGED_MIN
+#define VRT_CAST_STAGED_MIN 4096
+#endif
+static inline bool plan_cast_staged(long long n, int knob) { return knob >= 0 ? knob != 0 : n >= VRT_CAST_STAGED_MIN; }
+// Rays a host-path call stages at a time (80 bytes of device memory a ray: the batch size is limited by the caller's memory only).
+static inline long long plan_cast_chunk() { return 1 << 18; }
+// Workgroups of a launch over n rays, 256 rays a workgroup per turn of its loop: no more than fit on the chip at once.
+static inline int plan_cast_blocks(long long n, int n_cu, int blocks_per_cu) {
+    const long long want = (n + 255) / 256, fit = (long long)n_cu * (blocks_per_cu > 0 ? blocks_per_cu : 1);
+    return (int)(want < fit ? want : fit);
+}

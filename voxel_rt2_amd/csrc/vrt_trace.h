@@ -534,19 +534,23 @@ VRT_DEV void hit_voxel(const FrameParams& fp, const SceneData& sc, f3 eye, f3 d,
     }
 }
 
-// pathtracer.py:218-244 (floor plane 173-190, voxel grid 192-216).
+// pathtracer.py:218-244 (floor plane 173-190, voxel grid 192-216).  `tr`: what the walk returned (vrt_cast.h reports its cell).
 template <bool SHADOW, class PyrT>
-VRT_DEV void next_hit(const FrameParams& fp, const SceneData& sc, const PyrT& P, f3 pos, f3 d, Hit& h, TraceStats& ts) {
+VRT_DEV void next_hit(const FrameParams& fp, const SceneData& sc, const PyrT& P, f3 pos, f3 d, Hit& h, TraceStats& ts, TraceOut& tr) {
     hit_init(h);
     const float ft = floor_probe(fp, pos, d);
     if (ft < DM_INF) hit_floor(fp, d, ft, h);
     const f3 eye = world_to_voxel<PyrT::G>(pos);
-    TraceOut tr;
     int nq;
     raytrace<PyrT, PyrT::flat_descend && !(SHADOW && shadow_branchy_of<PyrT>::value)>(P, eye, d, tr, nq, sc.cull);
     ts.rays += 1u; ts.iters += (unsigned)tr.iters; ts.queries += (unsigned)nq;
     VRT_REGION(SHADOW ? 3 : 9);  // ray set-up + result (one entry per ray)
     hit_voxel<SHADOW, PyrT::G>(fp, sc, eye, d, tr, h, ts);
+}
+template <bool SHADOW, class PyrT>
+VRT_DEV void next_hit(const FrameParams& fp, const SceneData& sc, const PyrT& P, f3 pos, f3 d, Hit& h, TraceStats& ts) {
+    TraceOut tr;
+    next_hit<SHADOW>(fp, sc, P, pos, d, h, ts, tr);
 }
 
 }  // namespace vrt

@@ -243,6 +243,60 @@ class Renderer(VoxelStore):
         if reset:
             self.reset_framebuffer()
 
+    # -- asking the scene (include/vrt_api.h, vrt_cast_rays / vrt_fetch_voxels; no counterpart in the reference) -----------------
+    def cast_rays(self, origins, dirs, t_max=np.inf, any_hit=False):
+        """The reference's next_hit for caller-supplied rays in world units, on the scene as prepare_data() / update_voxels() left it:
+        an array of _abi.HIT (t, kind, cell, normal, albedo, mat_id), one record a ray.  origins, dirs: (n, 3) or (3,); t_max and
+        any_hit: scalars or one value a ray.  Directions are not normalised: t counts lengths of `dirs`.  `cell` is an array index --
+        what voxel_material / voxel_color take, and set_voxel after subtracting voxel_grid_res // 2."""
+        if not getattr(self, "_prepared", False):
+            raise NativeError("cast_rays asks a prepared scene: call prepare_data() first")
+        self._push()
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        rays = np.zeros(len(o), _abi.RAY)
+        rays["origin"], rays["dir"], rays["t_max"] = o, np.asarray(dirs, np.float32).reshape(-1, 3), t_max
+        rays["flags"] = np.where(np.asarray(any_hit, bool), _abi.RAY_ANY_HIT, 0)
+        return self._s.cast_rays(rays)
+
+    def pick_ray(self, u, v):
+        """(origin, direction) of the ray through the centre of pixel (u, v), v = 0 at the bottom: get_cast_dir (pathtracer.py:293-312)
+        without the TAA jitter, statement by statement in float32, from the matrices and the position the renderer was last given."""
+        self._push()
+        f = np.float32
+        view_inv, proj_inv = cam_mod.inverse_f32(self._view), cam_mod.inverse_f32(self._proj)
+        W, H = self.image_res
+        scale = f(self._render_scale)
+        tx = (f(u) + f(0.5)) * f(1.0 / W) / scale
+        ty = (f(v) + f(0.5)) * f(1.0 / H) / scale
+        pos = (tx * f(2.0) - f(1.0), ty * f(2.0) - f(1.0), f(1.0) * f(2.0) - f(1.0), f(1.0))            # screen_to_view, depth 1
+
+        def mul(M, p):
+            return [M[i, 0] * p[0] + M[i, 1] * p[1] + M[i, 2] * p[2] + M[i, 3] * p[3] for i in range(4)]
+        q = mul(proj_inv, pos)
+        d = [q[0] / q[3], q[1] / q[3], q[2] / q[3]]
+        inv = f(1.0) / np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])                                 # Vector.normalized()
+        d = [inv * d[0], inv * d[1], inv * d[2]]
+        w = mul(view_inv, (d[0], d[1], d[2], f(0.0)))                                                   # view_to_world, a direction
+        return np.array(self._pos, np.float32), np.array(w[:3], np.float32)
+
+    def pick(self, u, v, t_max=np.inf):
+        """The hit record under pixel (u, v): cast_rays(*pick_ray(u, v))[0]."""
+        o, d = self.pick_ray(u, v)
+        return self.cast_rays(o, d, t_max)[0]
+
+    def sync_voxels_from_device(self, lo=None, hi=None):
+        """Refresh voxel_material / voxel_color (what get_voxel reads) in the box [lo, hi) of array indices -- by default the whole
+        grid -- from the device, after edits the host never saw (NativeSession.update_voxels with device memory).  The voxels
+        are not marked dirty: they are what the device holds.  Voxels written with set_voxel since the last upload and not yet sent
+        are overwritten inside the box."""
+        if not getattr(self, "_prepared", False):
+            raise NativeError("sync_voxels_from_device reads a prepared scene: call prepare_data() first")
+        g = self.voxel_grid_res
+        (x0, y0, z0), (x1, y1, z1) = (lo if lo is not None else (0, 0, 0)), (hi if hi is not None else (g, g, g))
+        mat, rgb = self._s.fetch_voxels((x0, y0, z0), (x1, y1, z1))
+        self.voxel_material[x0:x1, y0:y1, z0:z1] = mat
+        self.voxel_color[x0:x1, y0:y1, z0:z1] = rgb
+
     def accumulate_clouds(self, max_samples):
         self._push()
         self._s.sky_accumulate_clouds(max_samples)
