@@ -176,6 +176,35 @@ typedef struct vrt_ray_hit { float t; int32_t kind; int32_t cell[3]; float norma
 enum { VRT_HIT_MISS = 0, VRT_HIT_FLOOR = 1, VRT_HIT_VOXEL = 2 };
 enum { VRT_RAY_ANY_HIT = 1 };
 int vrt_cast_rays(vrt_ctx* ctx, int64_t n, const vrt_ray* rays, vrt_ray_hit* hits, int on_device);
+/* How much light arrives along a ray: n caller-supplied rays, in WORLD units, each path-traced n_samples times on a PREPARED scene, and
+ * the mean of the samples in out[k].  Sample s (0 <= s < n_samples) of ray k is one run of the reference's render body
+ * (pathtracer.py:355-632) with ReSTIR off and a static camera, started at `origin` along `dir` instead of the camera's position and
+ * get_cast_dir, on random stream (cfg.seed, first_frame + s, ray.stream, 0) -- a pixel's stream is (seed, frame, v * W + u, 0) -- and on
+ * the context's current grid, floor, materials, scene parameters, sky tables and max_depth, in the mode vrt_set_reference_indexing
+ * selected.  The estimator is the one without ReSTIR whatever cfg.use_restir says, and the camera's camera_is_moving is ignored: no
+ * albedo demodulation.  The sample's value is diffuse + specular as the render forms them for its two colour buffers, each of the two
+ * first replaced by zero where the temporal prepass would scrub it (pathtracer.py:1069-1075: a NaN, infinite or negative component).
+ *   rgb   binary32, in this order: sum = 0; sum += value_s for s = 0 .. n_samples - 1, per component; then sum / (float)n_samples.  How
+ *         the work is scheduled or cut into chunks does not change a bit of it;
+ *   t     the distance of the ray's first hit: vrt_cast_rays' t for t_max = +inf, +inf for a ray that leaves into the sky.
+ * Directions are NOT normalised (normalising a unit vector again can move a bit, and the camera's rays are taken as they are): the
+ * estimator ASSUMES a unit dir -- the BSDF, the sun's cone and the sky lookup all read it as one.  `reserved` must be 0.
+ * INVALID rays -- a non-finite origin or direction component, a direction of all zeros -- are not traced and get rgb = 0, t = +inf.
+ * Every other ray ends: a path has at most max_depth segments, each a walk of at most 512 steps.
+ * on_device = 0: host arrays, borrowed for the call, staged in chunks; the call returns when `out` is filled.  on_device = 1: both are
+ * device memory; the work is only queued on the context's stream, no host synchronisation -- the caller keeps both unchanged until
+ * work queued on that stream behind the call has run (`out` also carries the running sums between chunks).  Ordered like
+ * vrt_update_voxels: a query queued after an edit sees the new grid, one queued before it the old.
+ * The query READS scene data and nothing else: no g-buffer, reservoir, history, counter, frame number or statistic is touched, the
+ * pending accumulation (vrt_accumulate) is not forced, and frames rendered around it are bit for bit the frames rendered without it.
+ * VRT_E_INVALID: NULL arguments, n < 0, n_samples < 1 or > VRT_RADIANCE_MAX_SAMPLES, on_device not 0 or 1, a ray whose `reserved` is not
+ * 0 (host path: checked before anything is traced; device path: the library does not read device memory on the host, such a ray is
+ * treated as invalid); VRT_E_STATE: before vrt_prepare, or after a vrt_upload_voxels that no vrt_prepare has followed; n = 0 returns
+ * VRT_OK.  No counterpart in the reference: its estimator can be reached through the camera only. */
+typedef struct vrt_path_ray { float origin[3]; uint32_t stream; float dir[3]; uint32_t reserved; } vrt_path_ray;   /* 32 bytes */
+typedef struct vrt_radiance { float rgb[3]; float t; } vrt_radiance;                                               /* 16 bytes */
+enum { VRT_RADIANCE_MAX_SAMPLES = 65536 };
+int vrt_trace_radiance(vrt_ctx* ctx, int64_t n, const vrt_path_ray* rays, int n_samples, uint32_t first_frame, vrt_radiance* out, int on_device);
 /* The mirror image of vrt_update_voxels: the stored materials and colours of the box [lo, hi) copied out as mat int8[hx][hy][hz] and
  * rgb uint8[hx][hy][hz][3] -- what a program reads after device-side edits, which the host never saw.  on_device = 0: host arrays, the
  * call synchronises; 1: device memory, queued on the context's stream.  Box rules and error codes are vrt_update_voxels'; the pending

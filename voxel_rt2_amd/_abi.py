@@ -15,6 +15,11 @@ RAY = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("dir", np.flo
 HIT = np.dtype([("t", np.float32), ("kind", np.int32), ("cell", np.int32, 3), ("normal", np.float32, 3), ("albedo", np.float32, 3),
                 ("mat_id", np.int32)])
 assert RAY.itemsize == 32 and HIT.itemsize == 48
+# vrt_path_ray / vrt_radiance (vrt_trace_radiance)
+PATH_RAY = np.dtype([("origin", np.float32, 3), ("stream", np.uint32), ("dir", np.float32, 3), ("reserved", np.uint32)])
+RADIANCE = np.dtype([("rgb", np.float32, 3), ("t", np.float32)])
+RADIANCE_MAX_SAMPLES = 65536
+assert PATH_RAY.itemsize == 32 and RADIANCE.itemsize == 16
 
 
 class VrtConfig(C.Structure):
@@ -77,6 +82,7 @@ def declare(lib, prefix):
     sig("prepare", C.c_int, P)
     sig("update_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
     sig("cast_rays", C.c_int, P, C.c_int64, P, P, C.c_int)
+    sig("trace_radiance", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)
     sig("fetch_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
     sig("sky_accumulate_clouds", C.c_int, P, C.c_int)
     sig("sky_compute_slice", C.c_int, P, C.c_int, C.c_int)

@@ -114,6 +114,33 @@ class NativeSession:
             self._call("cast_rays", C.c_int64(len(rays)), rays.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), 0)
         return out
 
+    def trace_radiance(self, rays, samples=1, first_frame=0, out=None, n=None):
+        """Path-traced radiance along rays (include/vrt_api.h, vrt_trace_radiance): the mean of `samples` samples a ray, sample s on
+        random stream (seed, first_frame + s, ray.stream, 0).  Host path: `rays` is an array of _abi.PATH_RAY, the result an array of
+        _abi.RADIANCE (`out` if given).  Device path: `rays` and `out` are torch tensors on the device holding the same 32- and 16-byte
+        records (any dtype; `n` rays, by default as many as `rays` holds); the work is queued on the session's stream and `out` is
+        returned, not yet filled."""
+        samples, first_frame = int(samples), int(first_frame) & 0xFFFFFFFF
+        if hasattr(rays, "data_ptr"):
+            if out is None or not hasattr(out, "data_ptr"):
+                raise ValueError("device path: `out` is a device tensor of 16 bytes a ray")
+            count = rays.numel() * rays.element_size() // _abi.PATH_RAY.itemsize if n is None else int(n)
+            if rays.numel() * rays.element_size() < count * _abi.PATH_RAY.itemsize or out.numel() * out.element_size() < count * _abi.RADIANCE.itemsize:
+                raise ValueError(f"{count} rays need {count * 32} bytes of rays and {count * 16} bytes of results")
+            if not (rays.is_contiguous() and out.is_contiguous()):
+                raise ValueError("device tensors must be contiguous")
+            self._call("trace_radiance", C.c_int64(count), C.c_void_p(rays.data_ptr()), samples, C.c_uint32(first_frame), C.c_void_p(out.data_ptr()), 1)
+            return out
+        rays = np.ascontiguousarray(rays, dtype=_abi.PATH_RAY).reshape(-1)
+        if out is None:
+            out = np.empty(len(rays), _abi.RADIANCE)
+        if out.dtype != _abi.RADIANCE or out.shape != rays.shape or not out.flags.c_contiguous:
+            raise ValueError("`out` must be a contiguous array of _abi.RADIANCE, one record a ray")
+        if len(rays):   # (an empty array's pointer may be NULL, which the library refuses whatever n is)
+            self._call("trace_radiance", C.c_int64(len(rays)), rays.ctypes.data_as(C.c_void_p), samples, C.c_uint32(first_frame),
+                       out.ctypes.data_as(C.c_void_p), 0)
+        return out
+
     def fetch_voxels(self, lo, hi, mat=None, rgb=None, on_device=False):
         """The stored voxels of the box [lo, hi) (include/vrt_api.h, vrt_fetch_voxels).  Host path: returns (mat, rgb), arrays of shape
         hi - lo and (hi - lo, 3).  Device path (on_device=True): `mat` and `rgb` are integer device pointers to int8[hx][hy][hz] and

@@ -482,6 +482,52 @@ int vrt_cast_rays(vrt_ctx* c, int64_t n, const vrt_ray* rays, vrt_ray_hit* hits,
     HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host arrays)
     return VRT_OK;
 }
+// vrt_trace_radiance reads what vrt_cast_rays reads plus the materials and the sky tables, and is ordered the same way.  Blocks of rays
+// (plan_radiance_rays), a block's samples in chunks of whole samples (plan_radiance_chunk): one trace launch and one fold launch a chunk,
+// all on the context's stream, where stream order lets every chunk reuse the scratch plane.
+static int queue_radiance_block(vrt_ctx* c, const FrameParams& fp, const SceneData& sc, long long m, const vrt_path_ray* d_rays, int n_samples,
+                                uint32_t first_frame, vrt_radiance* d_out) {
+    const int per = plan_radiance_chunk(m, n_samples);
+    const bool staged = plan_radiance_staged(m * per, c->knobs.cast_view);
+    for (int s0 = 0; s0 < n_samples; s0 += per) {
+        const int count = std::min(per, n_samples - s0);
+        HIP_TRY(launch_trace_radiance(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, fp, sc, m, s0, count, n_samples, first_frame, d_rays,
+                                      (f3*)(c->d_radiance_plane + 256), d_out, (unsigned*)c->d_radiance_plane));
+    }
+    return VRT_OK;
+}
+int vrt_trace_radiance(vrt_ctx* c, int64_t n, const vrt_path_ray* rays, int n_samples, uint32_t first_frame, vrt_radiance* out, int on_device) {
+    if (!c || !rays || !out) return fail(VRT_E_INVALID, "null argument");
+    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
+    if (n_samples < 1 || n_samples > VRT_RADIANCE_MAX_SAMPLES) return fail(VRT_E_INVALID, "n_samples must be 1 .. VRT_RADIANCE_MAX_SAMPLES");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    if (!c->prepared) return fail(VRT_E_STATE, "vrt_trace_radiance asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
+    if (n == 0) return VRT_OK;
+    if (!on_device)
+        for (int64_t k = 0; k < n; k++) if (rays[k].reserved != 0u) return fail(VRT_E_INVALID, "a ray's `reserved` field must be 0");
+    HIP_TRY(hipSetDevice(c->device));
+    const FrameParams fp = make_frame_params(c);   // (the floor, the light, the sky switch, voxel_edges, max_depth and the seed are what a query reads of it)
+    SceneData sc = make_scene_data(c);
+    sc.cull = c->d_cull + (c->cull_active && !c->ref_oob && c->knobs.cull != 0 ? 0 : 8);   // as vrt_cast_rays
+    if (!c->d_radiance_plane) HIP_TRY(dmalloc(c, &c->d_radiance_plane, 256 + (size_t)VRT_RADIANCE_ITEMS * sizeof(f3)));   // [0]: the work counter
+    const long long block = plan_radiance_rays((long long)n);
+    if (on_device) {
+        for (long long at = 0; at < (long long)n; at += block)
+            if (queue_radiance_block(c, fp, sc, std::min(block, (long long)n - at), rays + at, n_samples, first_frame, out + at) != VRT_OK) return VRT_E_DEVICE;
+        return VRT_OK;
+    }
+    if (ensure_cast_stage(c, (size_t)block * (sizeof(vrt_path_ray) + sizeof(vrt_radiance))) != VRT_OK) return VRT_E_DEVICE;
+    vrt_path_ray* d_rays = (vrt_path_ray*)c->d_cast_stage;
+    vrt_radiance* d_out = (vrt_radiance*)(c->d_cast_stage + (size_t)block * sizeof(vrt_path_ray));
+    for (long long at = 0; at < (long long)n; at += block) {   // (stream order lets block k + 1 reuse what block k's copy back has read)
+        const long long m = std::min(block, (long long)n - at);
+        HIP_TRY(hipMemcpyAsync(d_rays, rays + at, (size_t)m * sizeof(vrt_path_ray), hipMemcpyHostToDevice, c->stream));
+        if (queue_radiance_block(c, fp, sc, m, d_rays, n_samples, first_frame, d_out) != VRT_OK) return VRT_E_DEVICE;
+        HIP_TRY(hipMemcpyAsync(out + at, d_out, (size_t)m * sizeof(vrt_radiance), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host arrays)
+    return VRT_OK;
+}
 int vrt_fetch_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], void* mat, void* rgb, int on_device) {
     if (!c || !lo || !hi || !mat || !rgb) return fail(VRT_E_INVALID, "null argument");
     if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");

@@ -15,6 +15,7 @@
 //   k_temporal_group                                      the passes of several consecutive launches in one (static camera)
 //   k_tonemap                                             LDR presentation
 //   k_cast_rays / k_fetch_voxels                          vrt_cast_rays: caller-supplied rays through next_hit; vrt_fetch_voxels
+//   k_trace_radiance / k_fold_radiance                    vrt_trace_radiance: caller-supplied rays through the path state machine; the ordered sum
 //
 // k_render is a persistent-thread kernel: the grid is sized to the device's residency, each wave
 // keeps 64 path records in registers and pulls pixels (8x8 tiles, tile-major order) from a global
@@ -26,6 +27,7 @@
 // and no lane holds a path.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <atomic>
 #include "vrt_kernels.h"
 #include "vrt_probe.h"
 #include "vrt_shade_probe.h"
@@ -1042,6 +1044,105 @@ __global__ void k_fetch_voxels(EditBox box, int G, const int8_t* __restrict__ ma
     if (i < edit_box_voxels(box)) fetch_box_voxel(box, G, i, mat, rgb, box_mat, box_rgb);
 }
 
+// ---- vrt_trace_radiance: caller-supplied rays through the path state machine (vrt_radiance.h holds the per-item body) --------------
+// The work item is (ray, sample): item i of a launch is ray i % n_rays, sample s0 + i / n_rays of the block -- a sample's rays side by
+// side, so neighbouring lanes start on neighbouring rays, and one ray with 4096 samples fills the chip as 4096 rays with one do.
+// A persistent grid (plan_radiance_blocks), one Path<false> per lane, k_render's refill: between segments a lane whose path ended
+// stores the item's value to plane[i] (every item has exactly one writer: no atomics on results) and takes the next item; a wave
+// reserves 64 items at a time from the launch's head word and hands them to its lanes itself.  Lanes at different depths run side by
+// side.  STAGED / OOB: k_cast_rays' views of the pyramid, with the material table staged beside the coarse levels as k_render has it.
+// The item of a ray's sample 0 (of the call, not of the chunk) also stores the first hit's distance to out[ray].t; nothing else of `out`
+// is written here (rgb carries k_fold_radiance's running sum).  An invalid ray's items are worth zero and are not traced.
+template <int G, bool STAGED, bool OOB>
+__global__ __launch_bounds__(256, 2) void k_trace_radiance(FrameParams fp, SceneData sc, unsigned n_rays, unsigned total, unsigned s0, uint32_t first_frame,
+                                                           const vrt_path_ray* __restrict__ rays, f3* __restrict__ plane, vrt_radiance* __restrict__ out,
+                                                           unsigned* head) {
+    constexpr int N1 = GridDim<G>::n1 * GridDim<G>::n1 * GridDim<G>::n1, N2 = GridDim<G>::n2 * GridDim<G>::n2 * GridDim<G>::n2;
+    __shared__ unsigned long long s_l1[STAGED ? N1 : 1];
+    __shared__ unsigned long long s_l2[STAGED ? N2 : 1];
+    __shared__ float s_mats[STAGED ? 128 * 14 : 1];
+    __shared__ float s_cull[8];
+    typename std::conditional<STAGED, LdsPyramid<G, OOB>, GlobalPyramid<G>>::type P;
+    SceneData scl = sc;
+    if constexpr (STAGED) {
+        for (int i = threadIdx.x; i < N1; i += blockDim.x) s_l1[i] = sc.pyr.l1[i];
+        if (threadIdx.x < N2) s_l2[threadIdx.x] = sc.pyr.l2[threadIdx.x];
+        if (threadIdx.x < 8) s_cull[threadIdx.x] = sc.cull[threadIdx.x];
+        for (int i = threadIdx.x; i < 128 * 14; i += blockDim.x) s_mats[i] = sc.mats[i];
+        __syncthreads();
+        P.l0 = sc.pyr.l0; P.l1 = s_l1; P.l2 = s_l2;
+        P.w3 = (G == 256) ? sc.pyr.l3[0] : 0ULL;
+        P.oob = sc.pyr.ref_oob != 0;
+        scl.mats = s_mats;
+        scl.cull = s_cull;
+    } else {
+        P.p = sc.pyr;
+    }
+    const int lane = threadIdx.x & 63;
+    Path<false> p;
+    p.depth = -1;
+    unsigned item = 0u;                        // the lane's item while p.depth >= 0
+    float t_first = DM_INF;
+    TraceStats ts;                             // a sink: a query counts nothing
+    stats_zero(ts);
+    bool exhausted = false;                    // wave-uniform
+    unsigned chunk_next = 0u, chunk_end = 0u;  // wave-uniform: items [chunk_next, chunk_end) are reserved for this wave
+    for (;;) {
+        const bool need = p.depth < 0;
+        const unsigned long long mask = __ballot(need);
+        if (mask != 0ULL && !exhausted) {
+            if (chunk_next == chunk_end) {
+                unsigned base = 0u;
+                if (lane == 0) base = atomicAdd(head, 64u);   // (total <= VRT_RADIANCE_ITEMS and a grid of a few thousand waves overshoots by 64 each: no wrap)
+                base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+                chunk_next = base < total ? base : total;
+                chunk_end = (base + 64u < total) ? base + 64u : total;
+                if (base >= total) { exhausted = true; chunk_end = chunk_next; }
+            }
+            const unsigned avail = chunk_end - chunk_next;
+            const unsigned n = (unsigned)__popcll(mask);
+            const unsigned rank = (unsigned)__popcll(mask & ((1ULL << lane) - 1ULL));
+            const unsigned my = chunk_next + rank;
+            chunk_next += (n < avail) ? n : avail;
+            if (need && rank < avail) {        // my < chunk_end <= total
+                const unsigned ray = my % n_rays, sample = s0 + my / n_rays;
+                const vrt_path_ray r = rays[ray];
+                if (radiance_ray_valid(r)) {
+                    item = my;
+                    radiance_begin(fp, p, r, first_frame + sample);
+                } else {
+                    plane[my] = mk3(0.0f);
+                    if (sample == 0u) out[ray].t = DM_INF;
+                }
+            }
+        }
+        if (__ballot(p.depth >= 0) == 0ULL) {
+            if (exhausted) break;
+            continue;
+        }
+        if (p.depth >= 0) {
+            const bool first = p.depth == 0;
+            const bool done = radiance_segment(fp, scl, P, p, ts, t_first);
+            if (first && item / n_rays + s0 == 0u) out[item % n_rays].t = t_first;
+            if (done) {
+                plane[item] = radiance_value(p);
+                p.depth = -1;
+            }
+        }
+    }
+}
+// One lane per ray of the block: the chunk's `count` values of the ray added in sample order to the sum the chunks before left in
+// out[ray].rgb (first: to zero), and with the last chunk the division by the call's number of samples (radiance_fold, radiance_mean).
+__global__ __launch_bounds__(256) void k_fold_radiance(unsigned n_rays, int count, int first, int last, int n_samples, const f3* __restrict__ plane,
+                                                       vrt_radiance* __restrict__ out) {
+    const unsigned ray = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ray >= n_rays) return;
+    f3 acc = first ? mk3(0.0f) : mk3(out[ray].rgb[0], out[ray].rgb[1], out[ray].rgb[2]);
+    acc = radiance_fold(acc, plane + ray, (long long)n_rays, count);
+    if (last) acc = radiance_mean(acc, n_samples);
+    out[ray].rgb[0] = acc.x; out[ray].rgb[1] = acc.y; out[ray].rgb[2] = acc.z;
+}
+
 // ---- host-side launchers -----------------------------------------------------------------------
 #define VRT_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
@@ -1237,6 +1338,37 @@ hipError_t launch_cast_rays(hipStream_t st, int grid_res, bool staged, bool oob,
 }
 hipError_t launch_fetch_voxels(hipStream_t st, int grid_res, const EditBox& box, const int8_t* mat, const uint8_t* rgb, int8_t* box_mat, uint8_t* box_rgb) {
     hipLaunchKernelGGL(k_fetch_voxels, dim3((edit_box_voxels(box) + 255) / 256), dim3(256), 0, st, box, grid_res, mat, rgb, box_mat, box_rgb);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+// vrt_trace_radiance: one chunk -- samples [s0, s0 + count) of n_rays rays -- traced into `plane` and folded into `out`.  n_rays * count
+// is at most VRT_RADIANCE_ITEMS (plan_radiance_chunk); `head`: the launch's work counter, zeroed here on the stream.
+typedef void (*radiance_kernel_fn)(FrameParams, SceneData, unsigned, unsigned, unsigned, uint32_t, const vrt_path_ray*, f3*, vrt_radiance*, unsigned*);
+hipError_t launch_trace_radiance(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n_rays,
+                                 int s0, int count, int n_samples, uint32_t first_frame, const vrt_path_ray* rays, f3* plane, vrt_radiance* out, unsigned* head) {
+    const long long items = n_rays * count;
+    if (n_rays < 1 || count < 1 || s0 < 0 || s0 + count > n_samples || items > VRT_RADIANCE_ITEMS) return hipErrorInvalidValue;
+    radiance_kernel_fn fn = nullptr;
+    if (staged) VRT_BY_GRID(grid_res, VRT_BY_2(oob, false, fn = (k_trace_radiance<G, true, A>)));
+    else VRT_BY_GRID(grid_res, fn = (k_trace_radiance<G, false, true>));
+    // the instantiation's residency, asked once (it depends on nothing a call can change; contexts of one process share the device kind)
+    static std::atomic<int> residency[2][3] = {};
+    std::atomic<int>& cached = residency[grid_res == 256 ? 1 : 0][staged ? (oob ? 2 : 1) : 0];
+    int per_cu = cached.load(std::memory_order_relaxed);
+    hipError_t e = hipSuccess;
+    if (per_cu == 0) {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0);
+        if (e != hipSuccess) return e;
+        cached.store(per_cu, std::memory_order_relaxed);
+    }
+    e = hipMemsetAsync(head, 0, sizeof(unsigned), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fn, dim3(plan_radiance_blocks(items, n_cu, per_cu)), dim3(256), 0, st, fp, sc, (unsigned)n_rays, (unsigned)items, (unsigned)s0, first_frame,
+                       rays, plane, out, head);
+    VRT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_fold_radiance, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, st, (unsigned)n_rays, count, s0 == 0 ? 1 : 0,
+                       s0 + count == n_samples ? 1 : 0, n_samples, (const f3*)plane, out);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -150,16 +150,14 @@ VRT_DEV f3 camera_ray_dir(const FrameParams& fp, int u, int v) {
     const f3 dv = norm3(screen_to_view(tc, 1.0f, fp.proj_inv));
     return xform(fp.view_inv, dv, 0.0f);
 }
-// generate_new_sample + get_cast_dir (pathtracer.py:293-347)
+// generate_new_sample (pathtracer.py:331-347) and the locals of render (:381-391): a fresh path at `pos` along `d` on random stream `rng`.
+// What a path is keyed by is its caller's: a pixel and a sample (path_begin_along), or a caller-supplied ray (vrt_radiance.h).
 template <bool RESTIR>
-VRT_DEV void path_begin_along(const FrameParams& fp, Path<RESTIR>& p, int u, int v, int sample, f3 d) {  // d = camera_ray_dir(fp, u, v)
-    p.pix_u = u;
-    p.pix_v = v;
-    p.sample = sample;
+VRT_DEV void path_start(Path<RESTIR>& p, f3 pos, f3 d, dm_rng rng) {
     p.primary_pos = mk3(0.0f);
-    p.rng = dm_rng_init(fp.seed, fp.frame + (uint32_t)sample, (uint32_t)(v * fp.W + u), 0u);
+    p.rng = rng;
     p.d = d;
-    p.pos = fp.camera_pos;
+    p.pos = pos;
     p.thr = mk3(1.0f);
     p.contrib = mk3(0.0f);
     p.nee_d = mk3(0.0f);
@@ -182,6 +180,14 @@ VRT_DEV void path_begin_along(const FrameParams& fp, Path<RESTIR>& p, int u, int
         p.rs.rc_lobe = 0;
     }
 }
+// generate_new_sample + get_cast_dir (pathtracer.py:293-347)
+template <bool RESTIR>
+VRT_DEV void path_begin_along(const FrameParams& fp, Path<RESTIR>& p, int u, int v, int sample, f3 d) {  // d = camera_ray_dir(fp, u, v)
+    p.pix_u = u;
+    p.pix_v = v;
+    p.sample = sample;
+    path_start(p, fp.camera_pos, d, dm_rng_init(fp.seed, fp.frame + (uint32_t)sample, (uint32_t)(v * fp.W + u), 0u));
+}
 template <bool RESTIR>
 VRT_DEV void path_begin(const FrameParams& fp, Path<RESTIR>& p, int u, int v, int sample) { path_begin_along(fp, p, u, v, sample, camera_ray_dir(fp, u, v)); }
 
@@ -194,7 +200,8 @@ enum { HIT_ANY = 0, HIT_SOMETHING = 1, HIT_NOTHING = 2 };
 // example1.py never changes.  Then nothing can use the light sample except case (b) below, and the compiler drops
 // the sun direction (a basis, a sincos, a square root), the light-sample evaluation and what feeds them from the
 // common path; the two draws of the cone sampler are still made, so every later draw keeps its place in the stream.
-template <bool RESTIR, int KIND, bool BLACK_SUN = false, class PyrT>
+// STORE = false: the primary vertex's g-buffer values are not stored and `out` is not read (vrt_radiance.h: a query writes no pixel).
+template <bool RESTIR, int KIND, bool BLACK_SUN = false, bool STORE = true, class PyrT>
 VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& P, const PixelBuffers& out, int local_idx,
                         Path<RESTIR>& p, const Hit& h, TraceStats& ts) {
     const int depth = p.depth;
@@ -209,7 +216,7 @@ VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& 
         p.primary_albedo = h.albedo;
         p.sky_primary = (h.closest == DM_INF) ? 1 : 0;
         p.primary_pos = ppos;
-        if (p.sample == 0) {  // the samples of one accumulate(n) call share camera and jitter: same primary vertex
+        if (STORE && p.sample == 0) {  // the samples of one accumulate(n) call share camera and jitter: same primary vertex
             stream_store(&out.gb_normal[local_idx], oct_encode(h.normal));
             stream_store3(&out.gb_position[local_idx], ppos);
             stream_store(&out.gb_mat[local_idx], p.primary_mat_info);
@@ -347,13 +354,20 @@ VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& 
     return true;
 }
 
-// Advance one segment: closest-hit query, then path_shade().
+// Advance one segment: closest-hit query, then path_shade().  `closest`: the distance the query found (inf: nothing).  STORE: path_shade's.
+template <bool RESTIR, bool STORE = true, class PyrT>
+VRT_DEV bool path_segment(const FrameParams& fp, const SceneData& sc, const PyrT& P, const PixelBuffers& out, int local_idx,
+                          Path<RESTIR>& p, TraceStats& ts, float& closest) {
+    Hit h;
+    next_hit<false>(fp, sc, P, p.pos, p.d, h, ts);
+    closest = h.closest;
+    return path_shade<RESTIR, HIT_ANY, false, STORE>(fp, sc, P, out, local_idx, p, h, ts);
+}
 template <bool RESTIR, class PyrT>
 VRT_DEV bool path_segment(const FrameParams& fp, const SceneData& sc, const PyrT& P, const PixelBuffers& out, int local_idx,
                           Path<RESTIR>& p, TraceStats& ts) {
-    Hit h;
-    next_hit<false>(fp, sc, P, p.pos, p.d, h, ts);
-    return path_shade<RESTIR, HIT_ANY>(fp, sc, P, out, local_idx, p, h, ts);
+    float closest;
+    return path_segment<RESTIR, true>(fp, sc, P, out, local_idx, p, ts, closest);
 }
 
 // defined in vrt_restir.h: builds the input reservoir (pathtracer.py:549-607, 620-626)
@@ -361,6 +375,14 @@ template <class PathT>
 VRT_DEV void restir_finish(const FrameParams& fp, const SceneData& sc, const PixelBuffers& out, int local_idx, PathT& p,
                            f3 primary_pos, f3& diffuse, f3& specular, TraceStats& ts);
 
+// pathtracer.py:611-619: BSDF-sampled and light-sampled estimates, split by first-bounce lobe (ReSTIR off; before the demodulation of :620)
+VRT_DEV void path_colours(const Path<false>& p, f3& diffuse, f3& specular) {
+    const f3 emission = ((p.primary_mat_info & 255u) == 2u) ? unpack_albedo(p.primary_mat_info) : mk3(0.0f);
+    diffuse = diffuse + ((p.first_lobe == LOBE_DIFFUSE) ? p.contrib * p.first_invpdf + emission : mk3(0.0f));
+    specular = specular + ((p.first_lobe == LOBE_SPEC) ? p.contrib * p.first_invpdf : mk3(0.0f));
+    diffuse = diffuse + p.nee_d;
+    specular = specular + p.nee_s;
+}
 // Everything after the bounce loop (pathtracer.py:535-632)
 template <bool RESTIR>
 VRT_DEV void path_finish(const FrameParams& fp, const SceneData& sc, const PixelBuffers& out, int local_idx, Path<RESTIR>& p,
@@ -379,12 +401,7 @@ VRT_DEV void path_finish(const FrameParams& fp, const SceneData& sc, const Pixel
 
     f3 diffuse = mk3(0.0f), specular = mk3(0.0f);
     if constexpr (!RESTIR) {
-        // 611-619: BSDF-sampled and light-sampled estimates, split by first-bounce lobe
-        const f3 emission = ((p.primary_mat_info & 255u) == 2u) ? unpack_albedo(p.primary_mat_info) : mk3(0.0f);
-        diffuse = diffuse + ((p.first_lobe == LOBE_DIFFUSE) ? p.contrib * p.first_invpdf + emission : mk3(0.0f));
-        specular = specular + ((p.first_lobe == LOBE_SPEC) ? p.contrib * p.first_invpdf : mk3(0.0f));
-        diffuse = diffuse + p.nee_d;
-        specular = specular + p.nee_s;
+        path_colours(p, diffuse, specular);
         if (fp.camera_is_moving == 1) diffuse = diffuse / max3s(p.primary_albedo, 1e-2f);
     } else {
         restir_finish(fp, sc, out, local_idx, p, primary_pos, diffuse, specular, ts);

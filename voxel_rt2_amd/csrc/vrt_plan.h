@@ -213,3 +213,23 @@ static inline int plan_cast_blocks(long long n, int n_cu, int blocks_per_cu) {
     const long long want = (n + 255) / 256, fit = (long long)n_cu * (blocks_per_cu > 0 ? blocks_per_cu : 1);
     return (int)(want < fit ? want : fit);
 }
+
+// ---- vrt_trace_radiance --------------------------------------------------------------------------------------------------------
+// The work item is (ray, sample); a finished item leaves its value in a scratch plane of 12 bytes an item, which k_fold_radiance sums
+// per ray in sample order.  The plane is bounded: a call is cut into blocks of rays, and a block's samples into chunks of WHOLE samples
+// (every ray of the block, samples [s0, s0 + count)), so that no launch has more than VRT_RADIANCE_ITEMS items -- 12 MiB of scratch,
+// whatever n and n_samples are.  The sum is carried in `out` from chunk to chunk in sample order (radiance_fold, vrt_radiance.h), so
+// the cut cannot change a bit of the result (tests/test_radiance_host.py, tests/test_gpu_radiance.py).
+#define VRT_RADIANCE_ITEMS (1 << 20)
+// Rays of a block (also what a host-path call stages at a time: 48 bytes of device memory a ray).
+static inline long long plan_radiance_rays(long long n) { return n < (1 << 18) ? n : (1 << 18); }
+// Whole samples of a chunk over a block of n_rays rays (1 <= n_rays <= plan_radiance_rays' bound), n_samples to do in all: at least 1.
+static inline int plan_radiance_chunk(long long n_rays, int n_samples) {
+    const long long fit = VRT_RADIANCE_ITEMS / (n_rays > 0 ? n_rays : 1);
+    return (int)(fit < 1 ? 1 : fit < n_samples ? fit : n_samples);
+}
+// Which view of the pyramid a launch of `items` items walks on: plan_cast_staged's rule on the number of items (a path is several walks,
+// so staging pays no later than it does for single rays).  `knob`: Knobs::cast_view.
+static inline bool plan_radiance_staged(long long items, int knob) { return plan_cast_staged(items, knob); }
+// Workgroups of a launch over `items` items, 256 a workgroup per turn: plan_cast_blocks' rule.
+static inline int plan_radiance_blocks(long long items, int n_cu, int blocks_per_cu) { return plan_cast_blocks(items, n_cu, blocks_per_cu); }

@@ -284,6 +284,82 @@ class Renderer(VoxelStore):
         o, d = self.pick_ray(u, v)
         return self.cast_rays(o, d, t_max)[0]
 
+    # -- how much light arrives along a ray (include/vrt_api.h, vrt_trace_radiance; no counterpart in the reference) ---------------
+    def trace_radiance(self, origins, dirs, samples=1, first_frame=0, streams=None, normalize=True):
+        """Path-traced radiance along caller-supplied rays in world units, on the scene as prepare_data() / update_voxels() left it: a
+        structured array (`rgb`: the mean of `samples` samples; `t`: the distance of the first hit, inf into the sky), one record a
+        ray.  origins, dirs: (n, 3) or (3,), numpy arrays or torch tensors on the device (those go through the device path: the records
+        are put together on the device and only the result comes back).  The estimator takes `dirs` for unit vectors: normalize=True
+        normalises them in float64 before the cast to float32, normalize=False passes them on bit for bit.  Sample s of ray k draws
+        from random stream (seed, first_frame + s, streams[k], 0); streams defaults to arange(n), so two calls with the same arguments
+        return the same bits and first_frame = samples continues where a call left off."""
+        if not getattr(self, "_prepared", False):
+            raise NativeError("trace_radiance asks a prepared scene: call prepare_data() first")
+        self._push()
+        if hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr"):
+            import torch
+            dev = origins.device if hasattr(origins, "data_ptr") else dirs.device
+            o = torch.as_tensor(origins, device=dev).to(torch.float32).reshape(-1, 3)
+            d = torch.as_tensor(dirs, device=dev).reshape(-1, 3)
+            if normalize:
+                d = d.to(torch.float64)
+                d = d / torch.linalg.norm(d, dim=1, keepdim=True)
+            n = max(o.shape[0], d.shape[0])
+            rec = torch.zeros((n, 8), dtype=torch.float32, device=dev)
+            rec[:, 0:3], rec[:, 4:7] = o, d.to(torch.float32)
+            st = torch.arange(n, device=dev, dtype=torch.int64) if streams is None else torch.as_tensor(streams, device=dev).to(torch.int64).reshape(-1)
+            rec.view(torch.int32)[:, 3] = (((st & 0xFFFFFFFF) + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32)   # the stream's 32 bits
+            out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            torch.cuda.synchronize(dev)               # the tensors are written on torch's stream, read on the session's
+            self._s.trace_radiance(rec, samples, first_frame, out)
+            self._s.sync()
+            return out.cpu().numpy().view(_abi.RADIANCE).reshape(-1)
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        d = np.asarray(dirs).reshape(-1, 3)
+        if normalize:
+            d = d.astype(np.float64)
+            d = d / np.linalg.norm(d, axis=1, keepdims=True)
+        rays = np.zeros(max(len(o), len(d)), _abi.PATH_RAY)
+        rays["origin"], rays["dir"] = o, d.astype(np.float32)
+        rays["stream"] = np.arange(len(rays), dtype=np.uint32) if streams is None else np.asarray(streams).astype(np.uint32)
+        return self._s.trace_radiance(rays, samples, first_frame)
+
+    @staticmethod
+    def panorama_dirs(width, height):
+        """The unit directions of an equirectangular image, float64[height][width][3]: pixel (row i, column j) looks along longitude
+        phi = 2 pi (j + 0.5) / width - pi (phi = 0 is -z, the default camera's forward; +x is to the right) and latitude
+        theta = pi / 2 - pi (i + 0.5) / height (row 0 at the top, looking up): (cos theta sin phi, sin theta, -cos theta cos phi)."""
+        phi = 2.0 * np.pi * (np.arange(width) + 0.5) / width - np.pi
+        theta = 0.5 * np.pi - np.pi * (np.arange(height) + 0.5) / height
+        ct, st = np.cos(theta)[:, None], np.sin(theta)[:, None]
+        return np.stack([ct * np.sin(phi)[None, :], np.broadcast_to(st, (height, width)), -ct * np.cos(phi)[None, :]], axis=-1)
+
+    def render_panorama(self, origin, width, height, samples):
+        """An equirectangular 360-degree image of the radiance arriving at `origin`, float32[height][width][3] (linear HDR): pixel
+        (i, j) is trace_radiance(origin, panorama_dirs(width, height)[i, j], samples) with stream i * width + j."""
+        dirs = self.panorama_dirs(width, height).reshape(-1, 3)
+        got = self.trace_radiance(np.broadcast_to(np.asarray(origin, np.float32), dirs.shape), dirs, samples=samples)
+        return got["rgb"].reshape(height, width, 3).copy()
+
+    def tone_map(self, hdr):
+        """The presentation curve of fetch_image (pathtracer.py:634-662: exposure, uchimura of math_utils.py:163-186, gamma 2.2) without its
+        vignette, in numpy, for HDR images that do not come from the camera (render_panorama): float rgba [H, W, 4] for save_image."""
+        x = np.asarray(hdr, np.float32) * np.float32(self.exposure)
+        x = np.clip(np.nan_to_num(x, nan=0.0, posinf=1e6, neginf=0.0), 0.0, 1e6).astype(np.float64)   # (black for NaN and negative light, white for unbounded)
+        P, a, m, l, c, b = 1.0, 1.0, 0.22, 0.4, 1.33, 0.0
+        l0 = ((P - m) * l) / a
+        S0, S1 = m + l0, m + a * l0
+        CP = -((a * P) / (P - S1)) / P
+        w0 = 1.0 - (lambda t: t * t * (3.0 - 2.0 * t))(np.clip(x / m, 0.0, 1.0))
+        w2 = np.where(x < m + l0, 0.0, 1.0)
+        w1 = 1.0 - w0 - w2
+        with np.errstate(invalid="ignore", over="ignore"):
+            T = m * np.power(x / m, c) + b
+            S = P - (P - S1) * np.exp(CP * (x - S0))
+        L = m + a * (x - m)
+        rgb = np.clip(np.power(np.clip(T * w0 + L * w1 + S * w2, 0.0, None), 1.0 / 2.2), 0.0, 1.0)
+        return np.concatenate([rgb, np.ones(rgb.shape[:-1] + (1,))], axis=-1).astype(np.float32)
+
     def sync_voxels_from_device(self, lo=None, hi=None):
         """Refresh voxel_material / voxel_color (what get_voxel reads) in the box [lo, hi) of array indices -- by default the whole
         grid -- from the device, after edits the host never saw (NativeSession.update_voxels with device memory).  The voxels
