@@ -205,6 +205,36 @@ typedef struct vrt_path_ray { float origin[3]; uint32_t stream; float dir[3]; ui
 typedef struct vrt_radiance { float rgb[3]; float t; } vrt_radiance;                                               /* 16 bytes */
 enum { VRT_RADIANCE_MAX_SAMPLES = 65536 };
 int vrt_trace_radiance(vrt_ctx* ctx, int64_t n, const vrt_path_ray* rays, int n_samples, uint32_t first_frame, vrt_radiance* out, int on_device);
+/* How much light falls on a surface point: n caller-supplied sensors -- a point on a surface with its unit normal, in WORLD units -- on a
+ * PREPARED scene, each sampled n_samples times, and the means in out[k].  Total irradiance is sky_rgb + sun_rgb; the caller adds them.
+ * Sample s of sensor k uses frame f = first_frame + s and is, in binary32:
+ *   1. g = the random stream (cfg.seed, f, sensor.stream, 4) -- 4: sensor directions; o = pos + normal * 1e-6 per component (a product,
+ *      then a sum: pathtracer.py:428);
+ *   2. the sun (pathtracer.py:436-468 without the BSDF and MIS factors): ldir = sample_cone_oriented(light_cos_theta_max, light_direction)
+ *      on g's first two draws, ndl = dot(ldir, normal).  If ndl > 0 and the shadow ray next_hit(o, ldir, inf, shadow_ray) returns >= inf:
+ *      vis_s = 1 and sun_s = ((T * light_weight) * light_color) * ndl, T = sample_skybox_transmittance(ldir) under use_physical_sky, else
+ *      1.  Otherwise vis_s = 0 and sun_s = 0.  The shadow ray is cast even when the sun is black: `sun` is a visibility;
+ *   3. the hemisphere: w = sample_cosine_weighted_hemisphere(normal) on g's next two draws.  L_s is what vrt_trace_radiance forms for ray
+ *      (o, w, sensor.stream) at frame f -- a fresh path on stream (seed, f, stream, 0), scrubbed diffuse + specular -- except that a ray
+ *      whose FIRST segment escapes into the sky is evaluated with hit_sun = 0: step 2 has counted the sun, the disc is not counted again.
+ *      sky_s = 1 for such a ray, else 0.  hemi_s = L_s * 3.14159274f per component;
+ *   4. four running sums over s = 0 .. n_samples - 1, in order: sky_rgb += hemi_s, sky += sky_s, sun_rgb += sun_s, sun += vis_s, each
+ *      divided by (float)n_samples at the end.  How the work is scheduled or cut into chunks does not change a bit of them.
+ * So `sky` is the share of the cosine-weighted hemisphere that is open, `sun` the share of the sun's disc that is visible.  The normal is
+ * ASSUMED unit and is NOT normalised, as vrt_trace_radiance's dir.  `reserved` must be 0.
+ * INVALID sensors -- a non-finite component, a normal of all zeros -- are not traced and get an all-zero record.  A sample of a valid
+ * sensor whose normal is so far from unit that (o, w) is not a ray vrt_trace_radiance would trace (o overflows, or w comes out zero or
+ * non-finite: a normal longer than about 1.8e19) is not walked either, and its four terms are zero.
+ * n_samples, on_device, ordering, purity and error codes are vrt_trace_radiance's, word for word: n_samples in 1 ..
+ * VRT_RADIANCE_MAX_SAMPLES; on_device = 0: host arrays, the call returns when `out` is filled; 1: device memory, queued on the context's
+ * stream, `out` carries the running sums between chunks; a gather queued after an edit sees the new grid; the call READS scene data and
+ * nothing else, does not force the pending accumulation and touches no statistic; it follows vrt_set_reference_indexing.
+ * VRT_E_INVALID: NULL arguments, n < 0, n_samples out of range, on_device not 0 or 1, a sensor whose `reserved` is not 0 (host path:
+ * checked before anything runs; device path: such a sensor is treated as invalid); VRT_E_STATE: before vrt_prepare; n = 0 returns VRT_OK.
+ * No counterpart in the reference. */
+typedef struct vrt_sensor { float pos[3]; uint32_t stream; float normal[3]; uint32_t reserved; } vrt_sensor;        /* 32 bytes */
+typedef struct vrt_irradiance { float sky_rgb[3]; float sky; float sun_rgb[3]; float sun; } vrt_irradiance;         /* 32 bytes */
+int vrt_gather_irradiance(vrt_ctx* ctx, int64_t n, const vrt_sensor* sensors, int n_samples, uint32_t first_frame, vrt_irradiance* out, int on_device);
 /* The mirror image of vrt_update_voxels: the stored materials and colours of the box [lo, hi) copied out as mat int8[hx][hy][hz] and
  * rgb uint8[hx][hy][hz][3] -- what a program reads after device-side edits, which the host never saw.  on_device = 0: host arrays, the
  * call synchronises; 1: device memory, queued on the context's stream.  Box rules and error codes are vrt_update_voxels'; the pending

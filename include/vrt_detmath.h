@@ -294,7 +294,7 @@ DM_HD uint32_t dm_pcg_hash(uint32_t v) {
     uint32_t w = ((s >> ((s >> 28u) + 4u)) ^ s) * 277803737u;
     return (w >> 22u) ^ w;
 }
-/* stream = which kernel draws (0 render, 1 spatial reuse, 2 sky precompute, 3 host jitter);
+/* stream = which kernel draws (0 render, 1 spatial reuse, 2 sky precompute, 3 host jitter, 4 sensor directions: vrt_gather_irradiance);
  * index = global pixel / texel index, so results do not depend on how rows are sharded. */
 DM_HD dm_rng dm_rng_init(uint32_t seed, uint32_t frame, uint32_t index, uint32_t stream) {
     dm_rng r;

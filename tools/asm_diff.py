@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Are the device functions of this tree's kernels the machine code another revision generates?  Compiles voxel_rt2_amd/csrc/vrt_kernels.hip
+for the device alone (hipcc -S, the library's flags) from this tree and from REV's csrc/ and include/ (git archive into a temporary
+folder), cuts both listings into functions and compares every function both have, instruction for instruction: comments dropped, block
+labels renumbered in order of appearance (a function's labels carry its number in the file, which moves when functions are added).
+
+    python tools/asm_diff.py [REV] [name-substring ...]         REV: default HEAD~1
+
+Prints one line per function that differs or that only one side has, then the counts; exit status 1 if a function both have differs."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from voxel_rt2_amd import build as B  # noqa: E402
+
+SRC = os.path.join("voxel_rt2_amd", "csrc", "vrt_kernels.hip")
+
+
+def listing(root, out):
+    flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC")]
+    subprocess.run([B._hipcc()] + flags + ["--offload-device-only", "-S", os.path.join(root, SRC), "-o", out], check=True, capture_output=True)
+    return open(out).read()
+
+
+def functions(text):
+    """{demangled name: [instruction lines]} of a device listing."""
+    out, cur, body = {}, None, None
+    for line in text.splitlines():
+        m = re.match(r"^([A-Za-z_][\w$.]*):\s*(;.*)?$", line)
+        if m and cur is None and not m.group(1).startswith("."):
+            cur, body = m.group(1), []
+            continue
+        if cur is None:
+            continue
+        if re.match(r"^\.Lfunc_end\d+:", line):
+            out[cur] = body
+            cur = None
+            continue
+        line = line.split(";")[0].strip()
+        if line and not line.startswith((".p2align", ".loc", ".file", ".cfi", ".section", ".text")):
+            body.append(line)
+    names = list(out)
+    nice = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.splitlines() if names else []
+    return {n: out[k] for k, n in zip(names, nice)}
+
+
+def normal(body):
+    seen = {}
+
+    def label(m):
+        return seen.setdefault(m.group(0), f".L{len(seen)}")
+    return [re.sub(r"\.L[A-Za-z_]*\d+(_\d+)?", label, ln) for ln in body]
+
+
+def main():
+    args = sys.argv[1:]
+    rev = args.pop(0) if args and not subprocess.run(["git", "-C", ROOT, "rev-parse", "--verify", "-q", args[0] + "^{commit}"], capture_output=True).returncode else "HEAD~1"
+    with tempfile.TemporaryDirectory() as tmp:
+        old = os.path.join(tmp, "rev")
+        os.makedirs(old)
+        tar = subprocess.run(["git", "-C", ROOT, "archive", rev, "voxel_rt2_amd/csrc", "include"], check=True, capture_output=True).stdout
+        subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)
+        a, b = functions(listing(old, os.path.join(tmp, "a.s"))), functions(listing(ROOT, os.path.join(tmp, "b.s")))
+    pick = lambda n: not args or any(s in n for s in args)
+    same = differ = 0
+    for n in sorted(set(a) | set(b)):
+        if not pick(n):
+            continue
+        if n not in a or n not in b:
+            print(f"only in {'this tree' if n in b else rev}: {n[:150]}")
+        elif normal(a[n]) == normal(b[n]):
+            same += 1
+        else:
+            differ += 1
+            print(f"DIFFERS ({len(a[n])} -> {len(b[n])} instructions): {n[:150]}")
+    print(f"{same} functions identical to {rev}'s, {differ} differ")
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -141,6 +141,34 @@ class NativeSession:
                        out.ctypes.data_as(C.c_void_p), 0)
         return out
 
+    def gather_irradiance(self, sensors, samples=1, first_frame=0, out=None, n=None):
+        """Irradiance at surface points (include/vrt_api.h, vrt_gather_irradiance): per sensor the means over `samples` samples of the
+        hemisphere's light, its open share, the sun's light and its visible share; sample s draws its directions from random stream
+        (seed, first_frame + s, sensor.stream, 4).  Host path: `sensors` is an array of _abi.SENSOR, the result an array of
+        _abi.IRRADIANCE (`out` if given).  Device path: `sensors` and `out` are torch tensors on the device holding the same 32-byte
+        records (any dtype; `n` sensors, by default as many as `sensors` holds); the work is queued on the session's stream and `out`
+        is returned, not yet filled."""
+        samples, first_frame = int(samples), int(first_frame) & 0xFFFFFFFF
+        if hasattr(sensors, "data_ptr"):
+            if out is None or not hasattr(out, "data_ptr"):
+                raise ValueError("device path: `out` is a device tensor of 32 bytes a sensor")
+            count = sensors.numel() * sensors.element_size() // _abi.SENSOR.itemsize if n is None else int(n)
+            if sensors.numel() * sensors.element_size() < count * _abi.SENSOR.itemsize or out.numel() * out.element_size() < count * _abi.IRRADIANCE.itemsize:
+                raise ValueError(f"{count} sensors need {count * 32} bytes of sensors and {count * 32} bytes of results")
+            if not (sensors.is_contiguous() and out.is_contiguous()):
+                raise ValueError("device tensors must be contiguous")
+            self._call("gather_irradiance", C.c_int64(count), C.c_void_p(sensors.data_ptr()), samples, C.c_uint32(first_frame), C.c_void_p(out.data_ptr()), 1)
+            return out
+        sensors = np.ascontiguousarray(sensors, dtype=_abi.SENSOR).reshape(-1)
+        if out is None:
+            out = np.empty(len(sensors), _abi.IRRADIANCE)
+        if out.dtype != _abi.IRRADIANCE or out.shape != sensors.shape or not out.flags.c_contiguous:
+            raise ValueError("`out` must be a contiguous array of _abi.IRRADIANCE, one record a sensor")
+        if len(sensors):   # (an empty array's pointer may be NULL, which the library refuses whatever n is)
+            self._call("gather_irradiance", C.c_int64(len(sensors)), sensors.ctypes.data_as(C.c_void_p), samples, C.c_uint32(first_frame),
+                       out.ctypes.data_as(C.c_void_p), 0)
+        return out
+
     def fetch_voxels(self, lo, hi, mat=None, rgb=None, on_device=False):
         """The stored voxels of the box [lo, hi) (include/vrt_api.h, vrt_fetch_voxels).  Host path: returns (mat, rgb), arrays of shape
         hi - lo and (hi - lo, 3).  Device path (on_device=True): `mat` and `rgb` are integer device pointers to int8[hx][hy][hz] and

@@ -482,6 +482,14 @@ int vrt_cast_rays(vrt_ctx* c, int64_t n, const vrt_ray* rays, vrt_ray_hit* hits,
     HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host arrays)
     return VRT_OK;
 }
+// The scratch plane of vrt_trace_radiance and vrt_gather_irradiance: a work counter (256 bytes) and VRT_RADIANCE_ITEMS item values of one or
+// VRT_SENSOR_ITEMS records of the other -- the same bytes; both run on the context's stream, whose order lets them share it.
+static_assert((size_t)VRT_SENSOR_ITEMS * sizeof(vrt_irradiance) <= (size_t)VRT_RADIANCE_ITEMS * sizeof(f3), "the sensor plane must fit the radiance plane");
+static_assert(sizeof(vrt_irradiance) == VRT_SENSOR_ITEM_BYTES && sizeof(vrt_sensor) == 32, "record sizes of include/vrt_api.h");
+static int ensure_query_plane(vrt_ctx* c) {
+    if (!c->d_radiance_plane) HIP_TRY(dmalloc(c, &c->d_radiance_plane, 256 + (size_t)VRT_RADIANCE_ITEMS * sizeof(f3)));   // [0]: the work counter
+    return VRT_OK;
+}
 // vrt_trace_radiance reads what vrt_cast_rays reads plus the materials and the sky tables, and is ordered the same way.  Blocks of rays
 // (plan_radiance_rays), a block's samples in chunks of whole samples (plan_radiance_chunk): one trace launch and one fold launch a chunk,
 // all on the context's stream, where stream order lets every chunk reuse the scratch plane.
@@ -509,7 +517,7 @@ int vrt_trace_radiance(vrt_ctx* c, int64_t n, const vrt_path_ray* rays, int n_sa
     const FrameParams fp = make_frame_params(c);   // (the floor, the light, the sky switch, voxel_edges, max_depth and the seed are what a query reads of it)
     SceneData sc = make_scene_data(c);
     sc.cull = c->d_cull + (c->cull_active && !c->ref_oob && c->knobs.cull != 0 ? 0 : 8);   // as vrt_cast_rays
-    if (!c->d_radiance_plane) HIP_TRY(dmalloc(c, &c->d_radiance_plane, 256 + (size_t)VRT_RADIANCE_ITEMS * sizeof(f3)));   // [0]: the work counter
+    if (ensure_query_plane(c) != VRT_OK) return VRT_E_DEVICE;
     const long long block = plan_radiance_rays((long long)n);
     if (on_device) {
         for (long long at = 0; at < (long long)n; at += block)
@@ -524,6 +532,50 @@ int vrt_trace_radiance(vrt_ctx* c, int64_t n, const vrt_path_ray* rays, int n_sa
         HIP_TRY(hipMemcpyAsync(d_rays, rays + at, (size_t)m * sizeof(vrt_path_ray), hipMemcpyHostToDevice, c->stream));
         if (queue_radiance_block(c, fp, sc, m, d_rays, n_samples, first_frame, d_out) != VRT_OK) return VRT_E_DEVICE;
         HIP_TRY(hipMemcpyAsync(out + at, d_out, (size_t)m * sizeof(vrt_radiance), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host arrays)
+    return VRT_OK;
+}
+// vrt_gather_irradiance: vrt_trace_radiance's reading, ordering and cutting (plan_sensor_rays, plan_sensor_chunk), on the shared plane.
+static int queue_sensor_block(vrt_ctx* c, const FrameParams& fp, const SceneData& sc, long long m, const vrt_sensor* d_sensors, int n_samples,
+                              uint32_t first_frame, vrt_irradiance* d_out) {
+    const int per = plan_sensor_chunk(m, n_samples);
+    for (int s0 = 0; s0 < n_samples; s0 += per) {
+        const int count = std::min(per, n_samples - s0);
+        const bool staged = plan_cast_staged(m * count, c->knobs.cast_view);   // on the items of THIS launch: a short last chunk chooses for itself
+        HIP_TRY(launch_gather_irradiance(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, fp, sc, m, s0, count, n_samples, first_frame, d_sensors,
+                                         (vrt_irradiance*)(c->d_radiance_plane + 256), d_out, (unsigned*)c->d_radiance_plane));
+    }
+    return VRT_OK;
+}
+int vrt_gather_irradiance(vrt_ctx* c, int64_t n, const vrt_sensor* sensors, int n_samples, uint32_t first_frame, vrt_irradiance* out, int on_device) {
+    if (!c || !sensors || !out) return fail(VRT_E_INVALID, "null argument");
+    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
+    if (n_samples < 1 || n_samples > VRT_RADIANCE_MAX_SAMPLES) return fail(VRT_E_INVALID, "n_samples must be 1 .. VRT_RADIANCE_MAX_SAMPLES");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    if (!c->prepared) return fail(VRT_E_STATE, "vrt_gather_irradiance asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
+    if (n == 0) return VRT_OK;
+    if (!on_device)
+        for (int64_t k = 0; k < n; k++) if (sensors[k].reserved != 0u) return fail(VRT_E_INVALID, "a sensor's `reserved` field must be 0");
+    HIP_TRY(hipSetDevice(c->device));
+    const FrameParams fp = make_frame_params(c);   // (what vrt_trace_radiance reads of it)
+    SceneData sc = make_scene_data(c);
+    sc.cull = c->d_cull + (c->cull_active && !c->ref_oob && c->knobs.cull != 0 ? 0 : 8);   // as vrt_cast_rays
+    if (ensure_query_plane(c) != VRT_OK) return VRT_E_DEVICE;
+    const long long block = plan_sensor_rays((long long)n);
+    if (on_device) {
+        for (long long at = 0; at < (long long)n; at += block)
+            if (queue_sensor_block(c, fp, sc, std::min(block, (long long)n - at), sensors + at, n_samples, first_frame, out + at) != VRT_OK) return VRT_E_DEVICE;
+        return VRT_OK;
+    }
+    if (ensure_cast_stage(c, (size_t)block * (sizeof(vrt_sensor) + sizeof(vrt_irradiance))) != VRT_OK) return VRT_E_DEVICE;
+    vrt_sensor* d_sensors = (vrt_sensor*)c->d_cast_stage;
+    vrt_irradiance* d_out = (vrt_irradiance*)(c->d_cast_stage + (size_t)block * sizeof(vrt_sensor));
+    for (long long at = 0; at < (long long)n; at += block) {   // (stream order lets block k + 1 reuse what block k's copy back has read)
+        const long long m = std::min(block, (long long)n - at);
+        HIP_TRY(hipMemcpyAsync(d_sensors, sensors + at, (size_t)m * sizeof(vrt_sensor), hipMemcpyHostToDevice, c->stream));
+        if (queue_sensor_block(c, fp, sc, m, d_sensors, n_samples, first_frame, d_out) != VRT_OK) return VRT_E_DEVICE;
+        HIP_TRY(hipMemcpyAsync(out + at, d_out, (size_t)m * sizeof(vrt_irradiance), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host arrays)
     return VRT_OK;

@@ -15,6 +15,7 @@
 #include "vrt_edit.h"
 #include "vrt_cast.h"
 #include "vrt_radiance.h"
+#include "vrt_sensor.h"
 
 #define VRT_RENDER_THREADS 256
 #ifndef VRT_RENDER_MIN_WAVES
@@ -60,6 +61,11 @@ hipError_t launch_fetch_voxels(hipStream_t st, int grid_res, const EditBox& box,
 // head: one word of device memory, the launch's work counter.
 hipError_t launch_trace_radiance(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n_rays,
                                  int s0, int count, int n_samples, uint32_t first_frame, const vrt_path_ray* rays, f3* plane, vrt_radiance* out, unsigned* head);
+// vrt_gather_irradiance: samples [s0, s0 + count) of n_sensors sensors (device memory) gathered into plane[n_sensors * count] and folded into
+// out[n_sensors] (vrt_sensor.h; k_gather_irradiance, k_fold_irradiance).  n_sensors * count <= VRT_SENSOR_ITEMS; the rest as launch_trace_radiance.
+hipError_t launch_gather_irradiance(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n_sensors,
+                                    int s0, int count, int n_samples, uint32_t first_frame, const vrt_sensor* sensors, vrt_irradiance* plane, vrt_irradiance* out,
+                                    unsigned* head);
 hipError_t query_render_residency(int grid_res, bool restir, bool instr, int* blocks_per_cu);
 hipError_t launch_render(hipStream_t st, int grid_res, bool restir, bool instr, int n_blocks, const FrameParams& fp, const SceneData& sc,
                          const PixelBuffers& out, unsigned* work_counters, unsigned launch_seq, int n_samples, int chunk_override);

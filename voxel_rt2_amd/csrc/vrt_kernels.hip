@@ -16,6 +16,7 @@
 //   k_tonemap                                             LDR presentation
 //   k_cast_rays / k_fetch_voxels                          vrt_cast_rays: caller-supplied rays through next_hit; vrt_fetch_voxels
 //   k_trace_radiance / k_fold_radiance                    vrt_trace_radiance: caller-supplied rays through the path state machine; the ordered sum
+//   k_gather_irradiance / k_fold_irradiance               vrt_gather_irradiance: a sun sample and a hemisphere path per (sensor, sample); the ordered sums
 //
 // k_render is a persistent-thread kernel: the grid is sized to the device's residency, each wave
 // keeps 64 path records in registers and pulls pixels (8x8 tiles, tile-major order) from a global
@@ -1143,6 +1144,123 @@ __global__ __launch_bounds__(256) void k_fold_radiance(unsigned n_rays, int coun
     out[ray].rgb[0] = acc.x; out[ray].rgb[1] = acc.y; out[ray].rgb[2] = acc.z;
 }
 
+// ---- vrt_gather_irradiance: caller-supplied surface points; sun sample and hemisphere path per (sensor, sample) (vrt_sensor.h) ----
+// The work item is (sensor, sample): item i of a launch is sensor i % n_sensors, sample s0 + i / n_sensors of the block.  The schedule is
+// k_trace_radiance's: a persistent grid, one Path<false> per lane, a wave reserves 64 items at a time from the launch's head word and
+// refills the lanes whose item ended.  A fresh item has made its four draws (sensor_begin) and waits for its shadow ray; the shadow
+// rays of waiting items are walked TOGETHER (sensor_sun) once VRT_SENSOR_SUN_BATCH lanes wait, or when no lane has a path to step, or
+// when the launch has no items left -- a refill finds a lane or two a turn, and a walk for them alone would cost the whole wave a
+// walk's time.  Waiting lanes sit out the segment step.  The order of walks cannot change a result: an item owns its two random streams.
+// Every item has one writer per field of its plane record: the sun terms are stored behind the shadow ray, sky_s at the path's first
+// segment, hemi_s at its end; no atomics on results.  An invalid sensor's items, and an item whose derived ray sensor_begin refuses, are
+// all zeros and are not traced.
+#ifndef VRT_SENSOR_SUN_BATCH
+#define VRT_SENSOR_SUN_BATCH 16   // (tools/build_variant.sh NAME -DVRT_SENSOR_SUN_BATCH=1: a shadow walk at every refill; DESIGN.md section 4 says what is known of the choice)
+#endif
+template <int G, bool STAGED, bool OOB>
+__global__ __launch_bounds__(256, 2) void k_gather_irradiance(FrameParams fp, SceneData sc, unsigned n_sensors, unsigned total, unsigned s0, uint32_t first_frame,
+                                                              const vrt_sensor* __restrict__ sensors, vrt_irradiance* __restrict__ plane, unsigned* head) {
+    constexpr int N1 = GridDim<G>::n1 * GridDim<G>::n1 * GridDim<G>::n1, N2 = GridDim<G>::n2 * GridDim<G>::n2 * GridDim<G>::n2;
+    __shared__ unsigned long long s_l1[STAGED ? N1 : 1];
+    __shared__ unsigned long long s_l2[STAGED ? N2 : 1];
+    __shared__ float s_mats[STAGED ? 128 * 14 : 1];
+    __shared__ float s_cull[8];
+    typename std::conditional<STAGED, LdsPyramid<G, OOB>, GlobalPyramid<G>>::type P;
+    SceneData scl = sc;
+    if constexpr (STAGED) {
+        for (int i = threadIdx.x; i < N1; i += blockDim.x) s_l1[i] = sc.pyr.l1[i];
+        if (threadIdx.x < N2) s_l2[threadIdx.x] = sc.pyr.l2[threadIdx.x];
+        if (threadIdx.x < 8) s_cull[threadIdx.x] = sc.cull[threadIdx.x];
+        for (int i = threadIdx.x; i < 128 * 14; i += blockDim.x) s_mats[i] = sc.mats[i];
+        __syncthreads();
+        P.l0 = sc.pyr.l0; P.l1 = s_l1; P.l2 = s_l2;
+        P.w3 = (G == 256) ? sc.pyr.l3[0] : 0ULL;
+        P.oob = sc.pyr.ref_oob != 0;
+        scl.mats = s_mats;
+        scl.cull = s_cull;
+    } else {
+        P.p = sc.pyr;
+    }
+    const int lane = threadIdx.x & 63;
+    Path<false> p;
+    p.depth = -1;
+    unsigned item = 0u;                        // the lane's item while p.depth >= 0
+    bool sun_pending = false;                  // the item's shadow ray is still to be walked (then p.depth == 0)
+    f3 ldir = mk3(0.0f);                       // ... along ldir, with ndl = dot(ldir, normal)
+    float ndl = 0.0f;
+    TraceStats ts;                             // a sink: a query counts nothing
+    stats_zero(ts);
+    bool exhausted = false;                    // wave-uniform
+    unsigned chunk_next = 0u, chunk_end = 0u;  // wave-uniform: items [chunk_next, chunk_end) are reserved for this wave
+    for (;;) {
+        const bool need = p.depth < 0;
+        const unsigned long long mask = __ballot(need);
+        if (mask != 0ULL && !exhausted) {
+            if (chunk_next == chunk_end) {
+                unsigned base = 0u;
+                if (lane == 0) base = atomicAdd(head, 64u);   // (total <= VRT_SENSOR_ITEMS and a grid of a few thousand waves overshoots by 64 each: no wrap)
+                base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+                chunk_next = base < total ? base : total;
+                chunk_end = (base + 64u < total) ? base + 64u : total;
+                if (base >= total) { exhausted = true; chunk_end = chunk_next; }
+            }
+            const unsigned avail = chunk_end - chunk_next;
+            const unsigned n = (unsigned)__popcll(mask);
+            const unsigned rank = (unsigned)__popcll(mask & ((1ULL << lane) - 1ULL));
+            const unsigned my = chunk_next + rank;
+            chunk_next += (n < avail) ? n : avail;
+            if (need && rank < avail) {        // my < chunk_end <= total
+                const unsigned sensor = my % n_sensors, sample = s0 + my / n_sensors;
+                const vrt_sensor s = sensors[sensor];
+                if (sensor_valid(s) && sensor_begin(fp, p, s, first_frame + sample, ldir, ndl)) {
+                    item = my;
+                    sun_pending = true;
+                } else {
+                    plane[my] = sensor_zero();
+                }
+            }
+        }
+        const unsigned long long live = __ballot(p.depth >= 0);
+        if (live == 0ULL) {
+            if (exhausted) break;
+            continue;
+        }
+        const unsigned long long waiting = __ballot(sun_pending);   // a subset of `live`
+        if (waiting != 0ULL && (__popcll(waiting) >= VRT_SENSOR_SUN_BATCH || waiting == live || exhausted)) {
+            if (sun_pending) {
+                float vis;
+                const f3 sun = sensor_sun(fp, scl, P, p.pos, ldir, ndl, ts, vis);
+                vrt_irradiance* rec = plane + item;
+                rec->sun_rgb[0] = sun.x; rec->sun_rgb[1] = sun.y; rec->sun_rgb[2] = sun.z; rec->sun = vis;
+                sun_pending = false;
+            }
+        }
+        if (p.depth >= 0 && !sun_pending) {
+            const bool first = p.depth == 0;
+            float sky = 0.0f;
+            const bool done = sensor_segment(fp, scl, P, p, ts, sky);
+            vrt_irradiance* rec = plane + item;
+            if (first) rec->sky = sky;
+            if (done) {
+                const f3 hemi = sensor_value(p);
+                rec->sky_rgb[0] = hemi.x; rec->sky_rgb[1] = hemi.y; rec->sky_rgb[2] = hemi.z;
+                p.depth = -1;
+            }
+        }
+    }
+}
+// One lane per sensor of the block: the chunk's `count` records of the sensor added in sample order to the sums the chunks before left
+// in out[sensor] (first: to zero), and with the last chunk the division by the call's number of samples (sensor_fold, sensor_mean).
+__global__ __launch_bounds__(256) void k_fold_irradiance(unsigned n_sensors, int count, int first, int last, int n_samples, const vrt_irradiance* __restrict__ plane,
+                                                         vrt_irradiance* __restrict__ out) {
+    const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_sensors) return;
+    vrt_irradiance acc = first ? sensor_zero() : out[k];
+    acc = sensor_fold(acc, plane + k, (long long)n_sensors, count);
+    if (last) acc = sensor_mean(acc, n_samples);
+    out[k] = acc;
+}
+
 // ---- host-side launchers -----------------------------------------------------------------------
 #define VRT_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
@@ -1369,6 +1487,38 @@ hipError_t launch_trace_radiance(hipStream_t st, int grid_res, bool staged, bool
     VRT_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_fold_radiance, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, st, (unsigned)n_rays, count, s0 == 0 ? 1 : 0,
                        s0 + count == n_samples ? 1 : 0, n_samples, (const f3*)plane, out);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+// vrt_gather_irradiance: one chunk -- samples [s0, s0 + count) of n_sensors sensors -- gathered into `plane` and folded into `out`.
+// n_sensors * count is at most VRT_SENSOR_ITEMS (plan_sensor_chunk); `head`: the launch's work counter, zeroed here on the stream.
+typedef void (*sensor_kernel_fn)(FrameParams, SceneData, unsigned, unsigned, unsigned, uint32_t, const vrt_sensor*, vrt_irradiance*, unsigned*);
+hipError_t launch_gather_irradiance(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n_sensors,
+                                    int s0, int count, int n_samples, uint32_t first_frame, const vrt_sensor* sensors, vrt_irradiance* plane, vrt_irradiance* out,
+                                    unsigned* head) {
+    const long long items = n_sensors * count;
+    if (n_sensors < 1 || count < 1 || s0 < 0 || s0 + count > n_samples || items > VRT_SENSOR_ITEMS) return hipErrorInvalidValue;
+    sensor_kernel_fn fn = nullptr;
+    if (staged) VRT_BY_GRID(grid_res, VRT_BY_2(oob, false, fn = (k_gather_irradiance<G, true, A>)));
+    else VRT_BY_GRID(grid_res, fn = (k_gather_irradiance<G, false, true>));
+    // the instantiation's residency, asked once (launch_trace_radiance)
+    static std::atomic<int> residency[2][3] = {};
+    std::atomic<int>& cached = residency[grid_res == 256 ? 1 : 0][staged ? (oob ? 2 : 1) : 0];
+    int per_cu = cached.load(std::memory_order_relaxed);
+    hipError_t e = hipSuccess;
+    if (per_cu == 0) {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0);
+        if (e != hipSuccess) return e;
+        cached.store(per_cu, std::memory_order_relaxed);
+    }
+    e = hipMemsetAsync(head, 0, sizeof(unsigned), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fn, dim3(plan_radiance_blocks(items, n_cu, per_cu)), dim3(256), 0, st, fp, sc, (unsigned)n_sensors, (unsigned)items, (unsigned)s0, first_frame,
+                       sensors, plane, head);
+    VRT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_fold_irradiance, dim3((unsigned)((n_sensors + 255) / 256)), dim3(256), 0, st, (unsigned)n_sensors, count, s0 == 0 ? 1 : 0,
+                       s0 + count == n_samples ? 1 : 0, n_samples, (const vrt_irradiance*)plane, out);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

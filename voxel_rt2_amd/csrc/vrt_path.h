@@ -201,7 +201,9 @@ enum { HIT_ANY = 0, HIT_SOMETHING = 1, HIT_NOTHING = 2 };
 // the sun direction (a basis, a sincos, a square root), the light-sample evaluation and what feeds them from the
 // common path; the two draws of the cone sampler are still made, so every later draw keeps its place in the stream.
 // STORE = false: the primary vertex's g-buffer values are not stored and `out` is not read (vrt_radiance.h: a query writes no pixel).
-template <bool RESTIR, int KIND, bool BLACK_SUN = false, bool STORE = true, class PyrT>
+// DISC0 = false: a path whose FIRST segment escapes does not see the sun's disc (hit_sun = 0 at depth 0; vrt_sensor.h: the caller has
+// counted the sun at the path's origin already).  Later segments see it as ever.
+template <bool RESTIR, int KIND, bool BLACK_SUN = false, bool STORE = true, bool DISC0 = true, class PyrT>
 VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& P, const PixelBuffers& out, int local_idx,
                         Path<RESTIR>& p, const Hit& h, TraceStats& ts) {
     const int depth = p.depth;
@@ -337,7 +339,7 @@ VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& 
     if (KIND != HIT_SOMETHING && h.closest == DM_INF) {
         VRT_REGION(5);
         // escaped: background colour or skybox, plus the sun disc (pathtracer.py:500-517)
-        const float hit_sun = (dot3(fp.light_dir, p.d) >= fp.light_cos_max) ? 1.0f : 0.0f;
+        const float hit_sun = ((DISC0 || depth > 0) && dot3(fp.light_dir, p.d) >= fp.light_cos_max) ? 1.0f : 0.0f;
         f3 scat = fp.background, trans = mk3(1.0f);
         if (fp.use_sky == 1) { sky_lookup(sc.sky, p.d, p.rng, scat, trans); ts.sky_lookups += 2u; }
         const f3 emission = firefly(scat + trans * fp.light_weight * fp.light_color * hit_sun);
@@ -354,14 +356,14 @@ VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& 
     return true;
 }
 
-// Advance one segment: closest-hit query, then path_shade().  `closest`: the distance the query found (inf: nothing).  STORE: path_shade's.
-template <bool RESTIR, bool STORE = true, class PyrT>
+// Advance one segment: closest-hit query, then path_shade().  `closest`: the distance the query found (inf: nothing).  STORE, DISC0: path_shade's.
+template <bool RESTIR, bool STORE = true, bool DISC0 = true, class PyrT>
 VRT_DEV bool path_segment(const FrameParams& fp, const SceneData& sc, const PyrT& P, const PixelBuffers& out, int local_idx,
                           Path<RESTIR>& p, TraceStats& ts, float& closest) {
     Hit h;
     next_hit<false>(fp, sc, P, p.pos, p.d, h, ts);
     closest = h.closest;
-    return path_shade<RESTIR, HIT_ANY, false, STORE>(fp, sc, P, out, local_idx, p, h, ts);
+    return path_shade<RESTIR, HIT_ANY, false, STORE, DISC0>(fp, sc, P, out, local_idx, p, h, ts);
 }
 template <bool RESTIR, class PyrT>
 VRT_DEV bool path_segment(const FrameParams& fp, const SceneData& sc, const PyrT& P, const PixelBuffers& out, int local_idx,

@@ -233,3 +233,20 @@ static inline int plan_radiance_chunk(long long n_rays, int n_samples) {
 static inline bool plan_radiance_staged(long long items, int knob) { return plan_cast_staged(items, knob); }
 // Workgroups of a launch over `items` items, 256 a workgroup per turn: plan_cast_blocks' rule.
 static inline int plan_radiance_blocks(long long items, int n_cu, int blocks_per_cu) { return plan_cast_blocks(items, n_cu, blocks_per_cu); }
+
+// ---- vrt_gather_irradiance -----------------------------------------------------------------------------------------------------
+// The work item is (sensor, sample); a finished item leaves its four terms in a scratch plane of 32 bytes an item (a vrt_irradiance
+// record), which k_fold_irradiance sums per sensor in sample order.  The plane is bounded by BYTES, the same 12 MiB as
+// VRT_RADIANCE_ITEMS' (the two queries run on one stream and share the allocation): VRT_SENSOR_ITEMS = 12 MiB / 32 = 393 216 items a
+// launch.  A call is cut into blocks of sensors, and a block's samples into chunks of WHOLE samples, as vrt_trace_radiance's; the sums
+// are carried in `out` from chunk to chunk in sample order (sensor_fold, vrt_sensor.h), so the cut cannot change a bit of the result
+// (tests/test_sensor_host.py, tests/test_gpu_sensor.py).
+#define VRT_SENSOR_ITEM_BYTES 32
+#define VRT_SENSOR_ITEMS ((VRT_RADIANCE_ITEMS * 12) / VRT_SENSOR_ITEM_BYTES)
+// Sensors of a block (also what a host-path call stages at a time: 64 bytes of device memory a sensor): one sample of a block fits the plane.
+static inline long long plan_sensor_rays(long long n) { return n < (1 << 18) ? n : (1 << 18); }
+// Whole samples of a chunk over a block of n_sensors sensors (1 <= n_sensors <= plan_sensor_rays' bound), n_samples to do in all: at least 1.
+static inline int plan_sensor_chunk(long long n_sensors, int n_samples) {
+    const long long fit = VRT_SENSOR_ITEMS / (n_sensors > 0 ? n_sensors : 1);
+    return (int)(fit < 1 ? 1 : fit < n_samples ? fit : n_samples);
+}

@@ -33,12 +33,12 @@ VRT_DEV void radiance_begin(const FrameParams& fp, Path<false>& p, const vrt_pat
 }
 // One segment: path_segment (vrt_path.h) without its stores.  Returns true when the path is over.  t_first: at the path's first segment,
 // the distance of that hit -- vrt_cast_rays' t for t_max = inf (the same next_hit on the same ray), +inf into the sky.  A query counts
-// nothing: the caller's `ts` is a sink.
-template <class PyrT>
+// nothing: the caller's `ts` is a sink.  DISC0: path_shade's (false: vrt_sensor.h's paths).
+template <bool DISC0 = true, class PyrT>
 VRT_DEV bool radiance_segment(const FrameParams& fp, const SceneData& sc, const PyrT& P, Path<false>& p, TraceStats& ts, float& t_first) {
     const bool first = p.depth == 0;
     float closest;
-    const bool done = path_segment<false, false>(fp, sc, P, PixelBuffers{}, 0, p, ts, closest);   // (the buffers are never read: STORE = false)
+    const bool done = path_segment<false, false, DISC0>(fp, sc, P, PixelBuffers{}, 0, p, ts, closest);   // (the buffers are never read: STORE = false)
     if (first) t_first = closest;
     return done;
 }

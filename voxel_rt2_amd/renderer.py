@@ -112,6 +112,36 @@ class VoxelStore:
         self._voxels_dirty = False
         self._dirty_lo, self._dirty_hi = [0, 0, 0], [0, 0, 0]
 
+    # face k of a voxel: 0..5 = -x, +x, -y, +y, -z, +z
+    FACE_NORMALS = np.array([(-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1)], np.float32)
+
+    def surface_faces(self, lo=None, hi=None):
+        """The exposed faces of the solid voxels (material > 0) in the box [lo, hi) of array indices -- by default the whole grid: every
+        face whose neighbour cell is empty or lies outside the grid.  Host numpy on voxel_material (after device-side edits run
+        sync_voxels_from_device first).  Returns (cell int32[m, 3] array indices, face int8[m] 0..5 = -x, +x, -y, +y, -z, +z,
+        centre float32[m, 3] the face's centre in world units, normal float32[m, 3]), faces in the order of `face`, then of the cells."""
+        g = self.voxel_grid_res
+        lo = np.clip(np.array((0, 0, 0) if lo is None else lo, np.int64), 0, g)
+        hi = np.clip(np.array((g, g, g) if hi is None else hi, np.int64), 0, g)
+        hi = np.maximum(hi, lo)
+        pad = np.zeros((g + 2,) * 3, bool)
+        pad[1:-1, 1:-1, 1:-1] = self.voxel_material > 0
+        box = tuple(slice(int(a) + 1, int(b) + 1) for a, b in zip(lo, hi))
+        solid = pad[box]
+        cells, faces = [], []
+        for k in range(6):                                      # six shifted comparisons
+            axis, step = k >> 1, (k & 1) * 2 - 1
+            there = tuple(slice(sl.start + step, sl.stop + step) if a == axis else sl for a, sl in enumerate(box))
+            idx = np.argwhere(solid & ~pad[there])
+            cells.append(idx + lo)
+            faces.append(np.full(len(idx), k, np.int8))
+        cell = np.concatenate(cells).astype(np.int32).reshape(-1, 3)
+        face = np.concatenate(faces)
+        normal = self.FACE_NORMALS[face]
+        dx = 2.0 / g                                            # a cell spans [(i - g / 2) dx, (i + 1 - g / 2) dx]: exact in binary32
+        centre = ((cell.astype(np.float64) + 0.5 - g / 2) * dx + normal.astype(np.float64) * (0.5 * dx)).astype(np.float32)
+        return cell, face, centre, normal
+
 
 class Renderer(VoxelStore):
     def __init__(self, dx, image_res, up, voxel_edges, exposure=3, *, max_depth=None, use_restir=None, seed=None, sky_res=None,
@@ -323,6 +353,45 @@ class Renderer(VoxelStore):
         rays["origin"], rays["dir"] = o, d.astype(np.float32)
         rays["stream"] = np.arange(len(rays), dtype=np.uint32) if streams is None else np.asarray(streams).astype(np.uint32)
         return self._s.trace_radiance(rays, samples, first_frame)
+
+    # -- how much light falls on a surface point (include/vrt_api.h, vrt_gather_irradiance; no counterpart in the reference) ---------
+    def gather_irradiance(self, points, normals, samples=64, first_frame=0, streams=None):
+        """Irradiance at caller-supplied surface points in world units, on the scene as prepare_data() / update_voxels() left it: a
+        structured array of _abi.IRRADIANCE, one record a point -- sky_rgb (the hemisphere's light, sky and bounced), sky (the open share
+        of the cosine-weighted hemisphere), sun_rgb (the sun's direct light), sun (the visible share of its disc), each the mean of
+        `samples` samples; the total is sky_rgb + sun_rgb.  points, normals: (n, 3) or (3,), numpy arrays or torch tensors on the device
+        (those go through the device path).  Normals are taken for unit vectors and passed on bit for bit.  Sample s of point k draws
+        from random streams (seed, first_frame + s, streams[k], 4) and (.., 0); streams defaults to arange(n)."""
+        if not getattr(self, "_prepared", False):
+            raise NativeError("gather_irradiance asks a prepared scene: call prepare_data() first")
+        self._push()
+        if hasattr(points, "data_ptr") or hasattr(normals, "data_ptr"):
+            import torch
+            dev = points.device if hasattr(points, "data_ptr") else normals.device
+            o = torch.as_tensor(points, device=dev).to(torch.float32).reshape(-1, 3)
+            d = torch.as_tensor(normals, device=dev).to(torch.float32).reshape(-1, 3)
+            n = max(o.shape[0], d.shape[0])
+            rec = torch.zeros((n, 8), dtype=torch.float32, device=dev)
+            rec[:, 0:3], rec[:, 4:7] = o, d
+            st = torch.arange(n, device=dev, dtype=torch.int64) if streams is None else torch.as_tensor(streams, device=dev).to(torch.int64).reshape(-1)
+            rec.view(torch.int32)[:, 3] = (((st & 0xFFFFFFFF) + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32)   # the stream's 32 bits
+            out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+            torch.cuda.synchronize(dev)               # the tensors are written on torch's stream, read on the session's
+            self._s.gather_irradiance(rec, samples, first_frame, out)
+            self._s.sync()
+            return out.cpu().numpy().view(_abi.IRRADIANCE).reshape(-1)
+        o = np.asarray(points, np.float32).reshape(-1, 3)
+        d = np.asarray(normals, np.float32).reshape(-1, 3)
+        sensors = np.zeros(max(len(o), len(d)), _abi.SENSOR)
+        sensors["pos"], sensors["normal"] = o, d
+        sensors["stream"] = np.arange(len(sensors), dtype=np.uint32) if streams is None else np.asarray(streams).astype(np.uint32)
+        return self._s.gather_irradiance(sensors, samples, first_frame)
+
+    def bake_faces(self, lo=None, hi=None, samples=64):
+        """surface_faces(lo, hi) followed by gather_irradiance at the faces' centres: (cell, face, irradiance records), stream k for
+        face k of the list."""
+        cell, face, centre, normal = self.surface_faces(lo, hi)
+        return cell, face, self.gather_irradiance(centre, normal, samples=samples)
 
     @staticmethod
     def panorama_dirs(width, height):
