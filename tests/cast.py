@@ -446,8 +446,8 @@ def lib():
     if _lib is None:
         src = os.path.join(HERE, "emul", "cast_emul.cpp")
         csrc = os.path.join(ROOT, "voxel_rt2_amd", "csrc")
-        deps = [src, os.path.join(ROOT, "include", "vrt_api.h"), os.path.join(ROOT, "include", "vrt_detmath.h")]
-        deps += [os.path.join(csrc, f) for f in ("vrt_cast.h", "vrt_edit.h", "vrt_trace.h", "vrt_types.h", "vrt_plan.h")]
+        deps = [src, os.path.join(HERE, "emul", "query_emul.h"), os.path.join(ROOT, "include", "vrt_api.h"), os.path.join(ROOT, "include", "vrt_detmath.h")]
+        deps += [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]   # (query_emul.h reads the sampled queries' headers too)
         if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
             subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-shared", "-Wall", "-Werror",
                             "-Wno-unused-function", "-Wno-unknown-pragmas", "-o", _SO, src], check=True, capture_output=True)

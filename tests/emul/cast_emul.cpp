@@ -1,33 +1,8 @@
 // cast_emul.cpp -- TEST TOOLING: the loop of k_cast_rays (voxel_rt2_amd/csrc/vrt_kernels.hip) run on the host over cast_row of
 // voxel_rt2_amd/csrc/vrt_cast.h, ray by ray, on a pyramid and texel grid the test hands over (tests/edit.py builds them in numpy);
-// the loop of k_fetch_voxels; and the plain decisions of vrt_cast_rays (vrt_plan.h).  tests/cast.py compiles this with g++ and calls
-// it through ctypes.
-#include <cstring>
-#include "../../voxel_rt2_amd/csrc/vrt_cast.h"
-#include "../../voxel_rt2_amd/csrc/vrt_plan.h"
-
-using namespace vrt;
-
-// The staged view of the kernel (LdsPyramid, vrt_kernels.hip: device only) restated for the host: the same members and reads, the coarse
-// levels in copies of their own where the kernel has them in LDS.  OOB as there: whether the type carries the reference's reading
-// of cells outside the grid.
-template <int G_, bool OOB_>
-struct StagedPyramid {
-    static constexpr int G = G_;
-    static constexpr bool flat_descend = false;
-    static constexpr bool cull = true;
-    static constexpr bool oob_capable = OOB_;
-    bool oob;
-    bool oob_ref() const { return oob; }
-    const unsigned long long* l0;
-    unsigned long long l1[GridDim<G_>::n1 * GridDim<G_>::n1 * GridDim<G_>::n1];
-    unsigned long long l2[GridDim<G_>::n2 * GridDim<G_>::n2 * GridDim<G_>::n2];
-    unsigned long long w3;
-    unsigned long long load_l0(int i) const { return l0[i]; }
-    unsigned long long load_l1(int i) const { return l1[i]; }
-    unsigned long long load_l2(int i) const { return l2[i]; }
-    unsigned long long load_l3() const { return w3; }
-};
+// the loop of k_fetch_voxels; and the plain decisions of vrt_cast_rays (vrt_plan.h).  The views of the pyramid and the scene record's
+// conversion are tests/emul/query_emul.h's.  tests/cast.py compiles this with g++ and calls it through ctypes.
+#include "query_emul.h"
 
 struct CastScene {   // what tests/cast.py fills (ctypes mirror there)
     int32_t grid_res, ref_oob, floor_material, pad;
@@ -47,44 +22,16 @@ static void rows(const FrameParams& fp, const SceneData& sc, const PyrT& P, int 
         else { cast_row<false>(fp, sc, P, rays[i], hits[i]); if (any) cast_strip_surface(hits[i]); }
     }
 }
-template <int G>
-static void cast_g(const CastScene& s, int staged, int mode, long long n, const vrt_ray* rays, vrt_ray_hit* hits) {
-    FrameParams fp;
-    memset(&fp, 0, sizeof(fp));
-    fp.floor_height = s.floor_height;
-    fp.floor_color = mk3(s.floor_color[0], s.floor_color[1], s.floor_color[2]);
-    fp.floor_material = s.floor_material;
-    fp.voxel_edges = s.voxel_edges;
-    SceneData sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.pyr.l0 = s.l0; sc.pyr.l1 = s.l1; sc.pyr.l2 = s.l2; sc.pyr.l3 = s.l3;
-    sc.pyr.ref_oob = s.ref_oob;
-    sc.grid = s.grid;
-    sc.cull = s.cull;
-    if (!staged) {
-        GlobalPyramid<G> P;
-        P.p = sc.pyr;
-        rows(fp, sc, P, mode, n, rays, hits);
-        return;
-    }
-    auto stage = [&](auto& P) {
-        P.l0 = s.l0;
-        memcpy(P.l1, s.l1, sizeof(P.l1));
-        memcpy(P.l2, s.l2, sizeof(P.l2));
-        P.w3 = G == 256 ? s.l3[0] : 0ULL;
-        P.oob = s.ref_oob != 0;
-        rows(fp, sc, P, mode, n, rays, hits);
-    };
-    if (s.ref_oob) { static StagedPyramid<G, true> P; stage(P); }
-    else { static StagedPyramid<G, false> P; stage(P); }
-}
-
 extern "C" {
 
 int cast_emul_rays(const CastScene* s, int staged, int mode, long long n, const vrt_ray* rays, vrt_ray_hit* hits) {
     if (!s || n < 0 || (s->grid_res != 128 && s->grid_res != 256)) return -1;
-    if (s->grid_res == 256) cast_g<256>(*s, staged, mode, n, rays, hits);
-    else cast_g<128>(*s, staged, mode, n, rays, hits);
+    FrameParams fp;
+    SceneData sc;
+    scene_common(*s, fp, sc);
+    auto run = [&](const auto& P) { rows(fp, sc, P, mode, n, rays, hits); };
+    if (s->grid_res == 256) with_view<256>(sc, staged, run);
+    else with_view<128>(sc, staged, run);
     return 0;
 }
 int cast_emul_valid(const vrt_ray* r) { return cast_ray_valid(*r) ? 1 : 0; }

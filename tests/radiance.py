@@ -235,8 +235,8 @@ class RadScene(C.Structure):
 
 def lib():
     if "emul" not in _libs:
-        so = _build(_EMUL, os.path.join(HERE, "emul", "radiance_emul.cpp"), [os.path.join(ROOT, "voxel_rt2_amd", "csrc"), os.path.join(ROOT, "include")],
-                    ["-Werror"])
+        so = _build(_EMUL, os.path.join(HERE, "emul", "radiance_emul.cpp"), [os.path.join(ROOT, "voxel_rt2_amd", "csrc"), os.path.join(ROOT, "include"),
+                                                                                os.path.join(HERE, "emul")], ["-Werror"])
         lib = C.CDLL(so)
         lib.radiance_emul_trace.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_void_p]
         lib.radiance_emul_valid.argtypes = [C.c_void_p]
@@ -250,7 +250,7 @@ def lib():
 
 
 def chunks(n_rays, n_samples):
-    """[(s0, count)] as queue_radiance_block (vrt_api.hip) cuts a block's samples: plan_radiance_chunk whole samples at a time."""
+    """[(s0, count)] as sampled_query (vrt_api.hip) cuts a block's samples: plan_query_chunk whole samples at a time."""
     per = lib().radiance_emul_chunk(n_rays, n_samples)
     return [(s0, min(per, n_samples - s0)) for s0 in range(0, n_samples, max(per, 1))]
 

@@ -3,6 +3,7 @@ is compared by its bits, any NaN equal to any NaN):
   - every case == the oracle's render body: pose by pose on the host path (small launches: the pyramid in global memory) and all poses
     in one batch on the device path, tiled until the launch walks on the staged pyramid;
   - 2 048 rays x 600 samples take more than one chunk: 64 of the rays against the oracle, all of them against the same rays reversed;
+  - 1, 63, 64, 65 and 257 rays x 3 samples == the host build: a wave's reservation, its short last one, a second workgroup;
   - one ray x 4 096 samples == the ordered sum of 4 096 one-sample calls;
   - a query queued before / after an edit sees the old / new grid; frames rendered with queries interleaved == frames rendered without,
     a pending deferred accumulation included; vrt_get_stats does not notice queries;
@@ -61,7 +62,7 @@ def test_device_equals_oracle(case):
 
 def test_more_than_one_chunk():
     case, Wd, Hd, spp = "one_voxel_d2", 64, 32, 600
-    assert len(X.chunks(Wd * Hd, spp)) > 1                                             # at the committed budget (plan_radiance_chunk)
+    assert len(X.chunks(Wd * Hd, spp)) > 1                                             # at the committed budget (plan_query_chunk)
     o = X.start(X.ShimOracle(X.config(case, Wd, Hd)), case)
     o.set_camera(X.camera("default", 0, Wd, Hd))
     uv = np.array([(u, v) for v in range(Hd) for u in range(Wd)], np.int32)
@@ -77,6 +78,32 @@ def test_more_than_one_chunk():
         assert got["rgb"][pick].tobytes() == rgb.tobytes(), f"{(got['rgb'][pick] != rgb).any(axis=1).sum()} of 64 rays differ from the oracle"
         assert s.trace_radiance(rays[pick], spp, X.FIRST_FRAME).tobytes() == got[pick].tobytes()   # one chunk on the host path
         assert (got["rgb"] > 0).any() and np.isinf(got["t"]).any() and np.isfinite(got["t"]).any()
+    finally:
+        s.close()
+
+
+@pytest.fixture(scope="module")
+def one_voxel_rays():
+    """The 64 x 32 camera rays of the one_voxel case's default pose, and the case's scene for the host build."""
+    case, Wd, Hd = "one_voxel_d2", 64, 32
+    o = X.start(X.ShimOracle(X.config(case, Wd, Hd)), case)
+    o.set_camera(X.camera("default", 0, Wd, Hd))
+    rays = X.camera_rays(o, "default", np.array([(u, v) for v in range(Hd) for u in range(Wd)], np.int32), Wd)
+    o.close()
+    return rays, X.HostScene(case)
+
+
+@pytest.mark.parametrize("n_rays", [1, 63, 64, 65, 257])
+def test_batch_sizes_around_a_waves_reservation(one_voxel_rays, n_rays):
+    """A wave's take of 64 items, its short last take and a second workgroup (WaveItems, vrt_kernels.hip): 3 samples of n_rays rays on
+    the device path against the host build of the same functions, byte for byte."""
+    rays, host_scene = one_voxel_rays
+    rays = rays[(np.arange(n_rays) * 5) % len(rays)]
+    want = host_scene.trace(rays, 3)
+    s = session("one_voxel_d2")
+    try:
+        got = device_trace(s, rays, 3)
+        assert got.tobytes() == want.tobytes(), f"{X.mismatches(got, want).size} of {n_rays} records differ from the host build's"
     finally:
         s.close()
 

@@ -99,6 +99,30 @@ def test_fold_over_chunks_equals_fold_over_one(host_scene):
     assert (whole["rgb"] > 0).any()
 
 
+def test_query_chunk_equals_the_two_former_plans():
+    """plan_query_chunk(cap, n, s) under the radiance cap and under the sensor cap (radiance_emul_chunk, sensor_emul_chunk) against the
+    formula the two former plan functions held, written out here."""
+    import sensor as S
+    assert X.lib().radiance_emul_items() == 1 << 20 and S.lib().sensor_emul_items() == (1 << 20) * 12 // 32 == 393216
+    for chunk, cap in ((X.lib().radiance_emul_chunk, 1 << 20), (S.lib().sensor_emul_chunk, 393216)):
+        for n in (1, 2, 255, 4096, 1 << 18):
+            for spp in (1, 2, 257, 4096):
+                fit = cap // n
+                assert chunk(n, spp) == (1 if fit < 1 else fit if fit < spp else spp), (cap, n, spp)
+
+
+def test_views_and_chunkings_agree_on_96_rays_of_5_samples(host_scene):
+    """The plan's chunk, chunks of one sample and chunks of two, on both views of the pyramid: the same bytes."""
+    h = host_scene("sunlit_d5")
+    rays = np.concatenate([X.expected("sunlit_d5")[p][0] for p in ("default", "gap", "street")])[:96]
+    assert len(rays) == 96
+    whole = h.trace(rays, 5, staged=0, per=0)
+    assert (whole["rgb"] > 0).any() and np.isfinite(whole["t"]).any()
+    for staged in (0, 1):
+        for per in (0, 1, 2):
+            assert h.trace(rays, 5, staged=staged, per=per).tobytes() == whole.tobytes(), (staged, per)
+
+
 def ray(o=(0.0, 0.5, 0.0), d=(0.0, -1.0, 0.0), stream=3, reserved=0):
     r = np.zeros(1, X.PATH_RAY)
     with np.errstate(invalid="ignore"):

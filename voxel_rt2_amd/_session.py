@@ -90,29 +90,36 @@ class NativeSession:
             pm, pr = mat.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p)
         self._call("update_voxels", (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), pm, pr, int(bool(on_device)))
 
+    def _query(self, entry, records, out, n, in_name, out_name, extra, noun, what):
+        """The three scene queries' handling of their arrays: `records` of dtype _abi.<in_name> in, `out` of _abi.<out_name> back,
+        `extra` arguments between them.  noun, what: the messages' words for an input record and for the results."""
+        in_dtype, out_dtype = getattr(_abi, in_name), getattr(_abi, out_name)
+        i, o = in_dtype.itemsize, out_dtype.itemsize
+        if hasattr(records, "data_ptr"):
+            if out is None or not hasattr(out, "data_ptr"):
+                raise ValueError(f"device path: `out` is a device tensor of {o} bytes a {noun}")
+            count = records.numel() * records.element_size() // i if n is None else int(n)
+            if records.numel() * records.element_size() < count * i or out.numel() * out.element_size() < count * o:
+                raise ValueError(f"{count} {noun}s need {count * i} bytes of {noun}s and {count * o} bytes of {what}")
+            if not (records.is_contiguous() and out.is_contiguous()):
+                raise ValueError("device tensors must be contiguous")
+            self._call(entry, C.c_int64(count), C.c_void_p(records.data_ptr()), *extra, C.c_void_p(out.data_ptr()), 1)
+            return out
+        records = np.ascontiguousarray(records, dtype=in_dtype).reshape(-1)
+        if out is None:
+            out = np.empty(len(records), out_dtype)
+        if out.dtype != out_dtype or out.shape != records.shape or not out.flags.c_contiguous:
+            raise ValueError(f"`out` must be a contiguous array of _abi.{out_name}, one record a {noun}")
+        if len(records):   # (an empty array's pointer may be NULL, which the library refuses whatever n is)
+            self._call(entry, C.c_int64(len(records)), records.ctypes.data_as(C.c_void_p), *extra, out.ctypes.data_as(C.c_void_p), 0)
+        return out
+
     def cast_rays(self, rays, out=None, n=None):
         """Rays against the prepared scene (include/vrt_api.h, vrt_cast_rays).  Host path: `rays` is an array of _abi.RAY, the result
         an array of _abi.HIT (`out` if given).  Device path: `rays` and `out` are torch tensors on the device holding the same 32-
         and 48-byte records (any dtype; `n` rays, by default as many as `rays` holds); the work is queued on the session's stream and
         `out` is returned, not yet filled."""
-        if hasattr(rays, "data_ptr"):
-            if out is None or not hasattr(out, "data_ptr"):
-                raise ValueError("device path: `out` is a device tensor of 48 bytes a ray")
-            count = rays.numel() * rays.element_size() // _abi.RAY.itemsize if n is None else int(n)
-            if rays.numel() * rays.element_size() < count * _abi.RAY.itemsize or out.numel() * out.element_size() < count * _abi.HIT.itemsize:
-                raise ValueError(f"{count} rays need {count * 32} bytes of rays and {count * 48} bytes of records")
-            if not (rays.is_contiguous() and out.is_contiguous()):
-                raise ValueError("device tensors must be contiguous")
-            self._call("cast_rays", C.c_int64(count), C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr()), 1)
-            return out
-        rays = np.ascontiguousarray(rays, dtype=_abi.RAY).reshape(-1)
-        if out is None:
-            out = np.empty(len(rays), _abi.HIT)
-        if out.dtype != _abi.HIT or out.shape != rays.shape or not out.flags.c_contiguous:
-            raise ValueError("`out` must be a contiguous array of _abi.HIT, one record a ray")
-        if len(rays):   # (an empty array's pointer may be NULL, which the library refuses whatever n is)
-            self._call("cast_rays", C.c_int64(len(rays)), rays.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), 0)
-        return out
+        return self._query("cast_rays", rays, out, n, "RAY", "HIT", (), "ray", "records")
 
     def trace_radiance(self, rays, samples=1, first_frame=0, out=None, n=None):
         """Path-traced radiance along rays (include/vrt_api.h, vrt_trace_radiance): the mean of `samples` samples a ray, sample s on
@@ -120,26 +127,8 @@ class NativeSession:
         _abi.RADIANCE (`out` if given).  Device path: `rays` and `out` are torch tensors on the device holding the same 32- and 16-byte
         records (any dtype; `n` rays, by default as many as `rays` holds); the work is queued on the session's stream and `out` is
         returned, not yet filled."""
-        samples, first_frame = int(samples), int(first_frame) & 0xFFFFFFFF
-        if hasattr(rays, "data_ptr"):
-            if out is None or not hasattr(out, "data_ptr"):
-                raise ValueError("device path: `out` is a device tensor of 16 bytes a ray")
-            count = rays.numel() * rays.element_size() // _abi.PATH_RAY.itemsize if n is None else int(n)
-            if rays.numel() * rays.element_size() < count * _abi.PATH_RAY.itemsize or out.numel() * out.element_size() < count * _abi.RADIANCE.itemsize:
-                raise ValueError(f"{count} rays need {count * 32} bytes of rays and {count * 16} bytes of results")
-            if not (rays.is_contiguous() and out.is_contiguous()):
-                raise ValueError("device tensors must be contiguous")
-            self._call("trace_radiance", C.c_int64(count), C.c_void_p(rays.data_ptr()), samples, C.c_uint32(first_frame), C.c_void_p(out.data_ptr()), 1)
-            return out
-        rays = np.ascontiguousarray(rays, dtype=_abi.PATH_RAY).reshape(-1)
-        if out is None:
-            out = np.empty(len(rays), _abi.RADIANCE)
-        if out.dtype != _abi.RADIANCE or out.shape != rays.shape or not out.flags.c_contiguous:
-            raise ValueError("`out` must be a contiguous array of _abi.RADIANCE, one record a ray")
-        if len(rays):   # (an empty array's pointer may be NULL, which the library refuses whatever n is)
-            self._call("trace_radiance", C.c_int64(len(rays)), rays.ctypes.data_as(C.c_void_p), samples, C.c_uint32(first_frame),
-                       out.ctypes.data_as(C.c_void_p), 0)
-        return out
+        extra = (int(samples), C.c_uint32(int(first_frame) & 0xFFFFFFFF))
+        return self._query("trace_radiance", rays, out, n, "PATH_RAY", "RADIANCE", extra, "ray", "results")
 
     def gather_irradiance(self, sensors, samples=1, first_frame=0, out=None, n=None):
         """Irradiance at surface points (include/vrt_api.h, vrt_gather_irradiance): per sensor the means over `samples` samples of the
@@ -148,26 +137,8 @@ class NativeSession:
         _abi.IRRADIANCE (`out` if given).  Device path: `sensors` and `out` are torch tensors on the device holding the same 32-byte
         records (any dtype; `n` sensors, by default as many as `sensors` holds); the work is queued on the session's stream and `out`
         is returned, not yet filled."""
-        samples, first_frame = int(samples), int(first_frame) & 0xFFFFFFFF
-        if hasattr(sensors, "data_ptr"):
-            if out is None or not hasattr(out, "data_ptr"):
-                raise ValueError("device path: `out` is a device tensor of 32 bytes a sensor")
-            count = sensors.numel() * sensors.element_size() // _abi.SENSOR.itemsize if n is None else int(n)
-            if sensors.numel() * sensors.element_size() < count * _abi.SENSOR.itemsize or out.numel() * out.element_size() < count * _abi.IRRADIANCE.itemsize:
-                raise ValueError(f"{count} sensors need {count * 32} bytes of sensors and {count * 32} bytes of results")
-            if not (sensors.is_contiguous() and out.is_contiguous()):
-                raise ValueError("device tensors must be contiguous")
-            self._call("gather_irradiance", C.c_int64(count), C.c_void_p(sensors.data_ptr()), samples, C.c_uint32(first_frame), C.c_void_p(out.data_ptr()), 1)
-            return out
-        sensors = np.ascontiguousarray(sensors, dtype=_abi.SENSOR).reshape(-1)
-        if out is None:
-            out = np.empty(len(sensors), _abi.IRRADIANCE)
-        if out.dtype != _abi.IRRADIANCE or out.shape != sensors.shape or not out.flags.c_contiguous:
-            raise ValueError("`out` must be a contiguous array of _abi.IRRADIANCE, one record a sensor")
-        if len(sensors):   # (an empty array's pointer may be NULL, which the library refuses whatever n is)
-            self._call("gather_irradiance", C.c_int64(len(sensors)), sensors.ctypes.data_as(C.c_void_p), samples, C.c_uint32(first_frame),
-                       out.ctypes.data_as(C.c_void_p), 0)
-        return out
+        extra = (int(samples), C.c_uint32(int(first_frame) & 0xFFFFFFFF))
+        return self._query("gather_irradiance", sensors, out, n, "SENSOR", "IRRADIANCE", extra, "sensor", "results")
 
     def fetch_voxels(self, lo, hi, mat=None, rgb=None, on_device=False):
         """The stored voxels of the box [lo, hi) (include/vrt_api.h, vrt_fetch_voxels).  Host path: returns (mat, rgb), arrays of shape

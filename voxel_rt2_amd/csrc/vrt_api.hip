@@ -440,8 +440,8 @@ int vrt_update_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], cons
                         c->d_l0c, c->d_l0c_base, c->d_cull));
     return read_cull_record(c);   // (the wait also ends the loan of the host arrays)
 }
-// ---- asking the scene: vrt_cast_rays, vrt_fetch_voxels -------------------------------------------------------------------------
-// Both READ scene data (pyramid, texels, stored voxels), on the context's stream: behind every edit queued so far, ahead of every
+// ---- asking the scene: vrt_cast_rays, vrt_trace_radiance, vrt_gather_irradiance, vrt_fetch_voxels ------------------------------
+// All READ scene data (pyramid, texels, stored voxels), on the context's stream: behind every edit queued so far, ahead of every
 // later one.  Render launches read the same data on their own streams and nothing here writes what they or their passes touch, so
 // neither main_dirty nor the pending accumulation is concerned: no enter(), no flush.
 static int ensure_cast_stage(vrt_ctx* c, size_t need) {
@@ -452,32 +452,29 @@ static int ensure_cast_stage(vrt_ctx* c, size_t need) {
     c->cast_stage_bytes = need;
     return VRT_OK;
 }
-int vrt_cast_rays(vrt_ctx* c, int64_t n, const vrt_ray* rays, vrt_ray_hit* hits, int on_device) {
-    if (!c || !rays || !hits) return fail(VRT_E_INVALID, "null argument");
-    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
-    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
-    if (!c->prepared) return fail(VRT_E_STATE, "vrt_cast_rays asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
-    if (n == 0) return VRT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    const FrameParams fp = make_frame_params(c);   // (the floor and voxel_edges are what a query reads of it)
-    SceneData sc = make_scene_data(c);
+extern "C++" {   // (templates below)
+// What every query reads.  Of the frame parameters: the floor and voxel_edges; the sampled queries also the light, the sky switch,
+// max_depth and the seed.  Of the scene: the pyramid and the texels; the sampled queries also the materials and the sky tables.
+struct QueryInputs { FrameParams fp; SceneData sc; };
+static QueryInputs query_inputs(vrt_ctx* c) {
+    QueryInputs q{make_frame_params(c), make_scene_data(c)};
     // the scene's box, whatever the render launches count: culled rays are misses either way (cast_row); not with the reference's
     // indexing, where a ray clear of every solid voxel can still "hit" outside the grid (plan_render_variant)
-    sc.cull = c->d_cull + (c->cull_active && !c->ref_oob && c->knobs.cull != 0 ? 0 : 8);
-    const bool staged = plan_cast_staged((long long)n, c->knobs.cast_view);
-    if (on_device) {
-        HIP_TRY(launch_cast_rays(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, fp, sc, (long long)n, rays, hits));
-        return VRT_OK;
-    }
-    const size_t chunk = (size_t)std::min<long long>(plan_cast_chunk(), (long long)n);
-    if (ensure_cast_stage(c, chunk * (sizeof(vrt_ray) + sizeof(vrt_ray_hit))) != VRT_OK) return VRT_E_DEVICE;
-    vrt_ray* d_rays = (vrt_ray*)c->d_cast_stage;
-    vrt_ray_hit* d_hits = (vrt_ray_hit*)(c->d_cast_stage + chunk * sizeof(vrt_ray));
-    for (size_t at = 0; at < (size_t)n; at += chunk) {   // (stream order lets chunk k + 1 reuse what chunk k's copy back has read)
-        const size_t m = std::min(chunk, (size_t)n - at);
-        HIP_TRY(hipMemcpyAsync(d_rays, rays + at, m * sizeof(vrt_ray), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(launch_cast_rays(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, fp, sc, (long long)m, d_rays, d_hits));
-        HIP_TRY(hipMemcpyAsync(hits + at, d_hits, m * sizeof(vrt_ray_hit), hipMemcpyDeviceToHost, c->stream));
+    q.sc.cull = c->d_cull + (c->cull_active && !c->ref_oob && c->knobs.cull != 0 ? 0 : 8);
+    return q;
+}
+// A query's host path: the caller's n records, `block` at a time, copied to the staging buffer, worked on by queue(m, d_in, d_out) --
+// which queues on the context's stream -- and copied back; then the wait.
+template <class In, class Out, class Queue>
+static int staged_query(vrt_ctx* c, long long n, long long block, const In* in, Out* out, Queue queue) {
+    if (ensure_cast_stage(c, (size_t)block * (sizeof(In) + sizeof(Out))) != VRT_OK) return VRT_E_DEVICE;
+    In* d_in = (In*)c->d_cast_stage;
+    Out* d_out = (Out*)(c->d_cast_stage + (size_t)block * sizeof(In));
+    for (long long at = 0; at < n; at += block) {   // (stream order lets block k + 1 reuse what block k's copy back has read)
+        const long long m = std::min(block, n - at);
+        HIP_TRY(hipMemcpyAsync(d_in, in + at, (size_t)m * sizeof(In), hipMemcpyHostToDevice, c->stream));
+        if (queue(m, (const In*)d_in, d_out) != VRT_OK) return VRT_E_DEVICE;
+        HIP_TRY(hipMemcpyAsync(out + at, d_out, (size_t)m * sizeof(Out), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host arrays)
     return VRT_OK;
@@ -486,99 +483,62 @@ int vrt_cast_rays(vrt_ctx* c, int64_t n, const vrt_ray* rays, vrt_ray_hit* hits,
 // VRT_SENSOR_ITEMS records of the other -- the same bytes; both run on the context's stream, whose order lets them share it.
 static_assert((size_t)VRT_SENSOR_ITEMS * sizeof(vrt_irradiance) <= (size_t)VRT_RADIANCE_ITEMS * sizeof(f3), "the sensor plane must fit the radiance plane");
 static_assert(sizeof(vrt_irradiance) == VRT_SENSOR_ITEM_BYTES && sizeof(vrt_sensor) == 32, "record sizes of include/vrt_api.h");
-static int ensure_query_plane(vrt_ctx* c) {
+// A sampled query (vrt_query.h) reads what vrt_cast_rays reads plus the materials and the sky tables, and is ordered the same way.
+// Blocks of records (plan_query_rays), a block's samples in chunks of whole samples (plan_query_chunk): one item launch and one fold
+// launch a chunk, all on the context's stream, where stream order lets every chunk reuse the scratch plane.  name, noun: the entry
+// point's, for its messages.
+template <class Q>
+static int sampled_query(vrt_ctx* c, const char* name, const char* noun, int64_t n, const typename Q::In* in, int n_samples, uint32_t first_frame,
+                         typename Q::Out* out, int on_device) {
+    if (!c || !in || !out) return fail(VRT_E_INVALID, "null argument");
+    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
+    if (n_samples < 1 || n_samples > VRT_RADIANCE_MAX_SAMPLES) return fail(VRT_E_INVALID, "n_samples must be 1 .. VRT_RADIANCE_MAX_SAMPLES");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    if (!c->prepared) return fail(VRT_E_STATE, std::string(name) + " asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
+    if (n == 0) return VRT_OK;
+    if (!on_device)
+        for (int64_t k = 0; k < n; k++) if (in[k].reserved != 0u) return fail(VRT_E_INVALID, std::string("a ") + noun + "'s `reserved` field must be 0");
+    HIP_TRY(hipSetDevice(c->device));
+    const QueryInputs q = query_inputs(c);
     if (!c->d_radiance_plane) HIP_TRY(dmalloc(c, &c->d_radiance_plane, 256 + (size_t)VRT_RADIANCE_ITEMS * sizeof(f3)));   // [0]: the work counter
+    auto queue = [&](long long m, const typename Q::In* d_in, typename Q::Out* d_out) -> int {
+        const int per = plan_query_chunk(Q::max_items, m, n_samples);
+        for (int s0 = 0; s0 < n_samples; s0 += per) {
+            const int count = std::min(per, n_samples - s0);
+            const bool staged = plan_cast_staged(m * count, c->knobs.cast_view);   // on the items of THIS launch: a short last chunk chooses for itself
+            HIP_TRY(launch_sampled_query<Q>(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, q.fp, q.sc, m, s0, count, n_samples, first_frame, d_in,
+                                            (typename Q::Item*)(c->d_radiance_plane + 256), d_out, (unsigned*)c->d_radiance_plane));
+        }
+        return VRT_OK;
+    };
+    const long long block = plan_query_rays((long long)n);
+    if (!on_device) return staged_query(c, (long long)n, block, in, out, queue);
+    for (long long at = 0; at < (long long)n; at += block)
+        if (queue(std::min(block, (long long)n - at), in + at, out + at) != VRT_OK) return VRT_E_DEVICE;
     return VRT_OK;
 }
-// vrt_trace_radiance reads what vrt_cast_rays reads plus the materials and the sky tables, and is ordered the same way.  Blocks of rays
-// (plan_radiance_rays), a block's samples in chunks of whole samples (plan_radiance_chunk): one trace launch and one fold launch a chunk,
-// all on the context's stream, where stream order lets every chunk reuse the scratch plane.
-static int queue_radiance_block(vrt_ctx* c, const FrameParams& fp, const SceneData& sc, long long m, const vrt_path_ray* d_rays, int n_samples,
-                                uint32_t first_frame, vrt_radiance* d_out) {
-    const int per = plan_radiance_chunk(m, n_samples);
-    const bool staged = plan_radiance_staged(m * per, c->knobs.cast_view);
-    for (int s0 = 0; s0 < n_samples; s0 += per) {
-        const int count = std::min(per, n_samples - s0);
-        HIP_TRY(launch_trace_radiance(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, fp, sc, m, s0, count, n_samples, first_frame, d_rays,
-                                      (f3*)(c->d_radiance_plane + 256), d_out, (unsigned*)c->d_radiance_plane));
-    }
-    return VRT_OK;
+}  // extern "C++"
+int vrt_cast_rays(vrt_ctx* c, int64_t n, const vrt_ray* rays, vrt_ray_hit* hits, int on_device) {
+    if (!c || !rays || !hits) return fail(VRT_E_INVALID, "null argument");
+    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    if (!c->prepared) return fail(VRT_E_STATE, "vrt_cast_rays asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
+    if (n == 0) return VRT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const QueryInputs q = query_inputs(c);
+    const bool staged = plan_cast_staged((long long)n, c->knobs.cast_view);   // on the whole batch, however the host path cuts it
+    auto queue = [&](long long m, const vrt_ray* d_rays, vrt_ray_hit* d_hits) -> int {
+        HIP_TRY(launch_cast_rays(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, q.fp, q.sc, m, d_rays, d_hits));
+        return VRT_OK;
+    };
+    if (on_device) return queue((long long)n, rays, hits);
+    return staged_query(c, (long long)n, std::min<long long>(plan_cast_chunk(), (long long)n), rays, hits, queue);
 }
 int vrt_trace_radiance(vrt_ctx* c, int64_t n, const vrt_path_ray* rays, int n_samples, uint32_t first_frame, vrt_radiance* out, int on_device) {
-    if (!c || !rays || !out) return fail(VRT_E_INVALID, "null argument");
-    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
-    if (n_samples < 1 || n_samples > VRT_RADIANCE_MAX_SAMPLES) return fail(VRT_E_INVALID, "n_samples must be 1 .. VRT_RADIANCE_MAX_SAMPLES");
-    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
-    if (!c->prepared) return fail(VRT_E_STATE, "vrt_trace_radiance asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
-    if (n == 0) return VRT_OK;
-    if (!on_device)
-        for (int64_t k = 0; k < n; k++) if (rays[k].reserved != 0u) return fail(VRT_E_INVALID, "a ray's `reserved` field must be 0");
-    HIP_TRY(hipSetDevice(c->device));
-    const FrameParams fp = make_frame_params(c);   // (the floor, the light, the sky switch, voxel_edges, max_depth and the seed are what a query reads of it)
-    SceneData sc = make_scene_data(c);
-    sc.cull = c->d_cull + (c->cull_active && !c->ref_oob && c->knobs.cull != 0 ? 0 : 8);   // as vrt_cast_rays
-    if (ensure_query_plane(c) != VRT_OK) return VRT_E_DEVICE;
-    const long long block = plan_radiance_rays((long long)n);
-    if (on_device) {
-        for (long long at = 0; at < (long long)n; at += block)
-            if (queue_radiance_block(c, fp, sc, std::min(block, (long long)n - at), rays + at, n_samples, first_frame, out + at) != VRT_OK) return VRT_E_DEVICE;
-        return VRT_OK;
-    }
-    if (ensure_cast_stage(c, (size_t)block * (sizeof(vrt_path_ray) + sizeof(vrt_radiance))) != VRT_OK) return VRT_E_DEVICE;
-    vrt_path_ray* d_rays = (vrt_path_ray*)c->d_cast_stage;
-    vrt_radiance* d_out = (vrt_radiance*)(c->d_cast_stage + (size_t)block * sizeof(vrt_path_ray));
-    for (long long at = 0; at < (long long)n; at += block) {   // (stream order lets block k + 1 reuse what block k's copy back has read)
-        const long long m = std::min(block, (long long)n - at);
-        HIP_TRY(hipMemcpyAsync(d_rays, rays + at, (size_t)m * sizeof(vrt_path_ray), hipMemcpyHostToDevice, c->stream));
-        if (queue_radiance_block(c, fp, sc, m, d_rays, n_samples, first_frame, d_out) != VRT_OK) return VRT_E_DEVICE;
-        HIP_TRY(hipMemcpyAsync(out + at, d_out, (size_t)m * sizeof(vrt_radiance), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host arrays)
-    return VRT_OK;
-}
-// vrt_gather_irradiance: vrt_trace_radiance's reading, ordering and cutting (plan_sensor_rays, plan_sensor_chunk), on the shared plane.
-static int queue_sensor_block(vrt_ctx* c, const FrameParams& fp, const SceneData& sc, long long m, const vrt_sensor* d_sensors, int n_samples,
-                              uint32_t first_frame, vrt_irradiance* d_out) {
-    const int per = plan_sensor_chunk(m, n_samples);
-    for (int s0 = 0; s0 < n_samples; s0 += per) {
-        const int count = std::min(per, n_samples - s0);
-        const bool staged = plan_cast_staged(m * count, c->knobs.cast_view);   // on the items of THIS launch: a short last chunk chooses for itself
-        HIP_TRY(launch_gather_irradiance(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, fp, sc, m, s0, count, n_samples, first_frame, d_sensors,
-                                         (vrt_irradiance*)(c->d_radiance_plane + 256), d_out, (unsigned*)c->d_radiance_plane));
-    }
-    return VRT_OK;
+    return sampled_query<RadianceQuery>(c, "vrt_trace_radiance", "ray", n, rays, n_samples, first_frame, out, on_device);
 }
 int vrt_gather_irradiance(vrt_ctx* c, int64_t n, const vrt_sensor* sensors, int n_samples, uint32_t first_frame, vrt_irradiance* out, int on_device) {
-    if (!c || !sensors || !out) return fail(VRT_E_INVALID, "null argument");
-    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
-    if (n_samples < 1 || n_samples > VRT_RADIANCE_MAX_SAMPLES) return fail(VRT_E_INVALID, "n_samples must be 1 .. VRT_RADIANCE_MAX_SAMPLES");
-    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
-    if (!c->prepared) return fail(VRT_E_STATE, "vrt_gather_irradiance asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
-    if (n == 0) return VRT_OK;
-    if (!on_device)
-        for (int64_t k = 0; k < n; k++) if (sensors[k].reserved != 0u) return fail(VRT_E_INVALID, "a sensor's `reserved` field must be 0");
-    HIP_TRY(hipSetDevice(c->device));
-    const FrameParams fp = make_frame_params(c);   // (what vrt_trace_radiance reads of it)
-    SceneData sc = make_scene_data(c);
-    sc.cull = c->d_cull + (c->cull_active && !c->ref_oob && c->knobs.cull != 0 ? 0 : 8);   // as vrt_cast_rays
-    if (ensure_query_plane(c) != VRT_OK) return VRT_E_DEVICE;
-    const long long block = plan_sensor_rays((long long)n);
-    if (on_device) {
-        for (long long at = 0; at < (long long)n; at += block)
-            if (queue_sensor_block(c, fp, sc, std::min(block, (long long)n - at), sensors + at, n_samples, first_frame, out + at) != VRT_OK) return VRT_E_DEVICE;
-        return VRT_OK;
-    }
-    if (ensure_cast_stage(c, (size_t)block * (sizeof(vrt_sensor) + sizeof(vrt_irradiance))) != VRT_OK) return VRT_E_DEVICE;
-    vrt_sensor* d_sensors = (vrt_sensor*)c->d_cast_stage;
-    vrt_irradiance* d_out = (vrt_irradiance*)(c->d_cast_stage + (size_t)block * sizeof(vrt_sensor));
-    for (long long at = 0; at < (long long)n; at += block) {   // (stream order lets block k + 1 reuse what block k's copy back has read)
-        const long long m = std::min(block, (long long)n - at);
-        HIP_TRY(hipMemcpyAsync(d_sensors, sensors + at, (size_t)m * sizeof(vrt_sensor), hipMemcpyHostToDevice, c->stream));
-        if (queue_sensor_block(c, fp, sc, m, d_sensors, n_samples, first_frame, d_out) != VRT_OK) return VRT_E_DEVICE;
-        HIP_TRY(hipMemcpyAsync(out + at, d_out, (size_t)m * sizeof(vrt_irradiance), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host arrays)
-    return VRT_OK;
+    return sampled_query<SensorQuery>(c, "vrt_gather_irradiance", "sensor", n, sensors, n_samples, first_frame, out, on_device);
 }
 int vrt_fetch_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], void* mat, void* rgb, int on_device) {
     if (!c || !lo || !hi || !mat || !rgb) return fail(VRT_E_INVALID, "null argument");

@@ -14,8 +14,7 @@
 #include "vrt_plan.h"
 #include "vrt_edit.h"
 #include "vrt_cast.h"
-#include "vrt_radiance.h"
-#include "vrt_sensor.h"
+#include "vrt_query.h"
 
 #define VRT_RENDER_THREADS 256
 #ifndef VRT_RENDER_MIN_WAVES
@@ -56,16 +55,13 @@ hipError_t launch_cast_rays(hipStream_t st, int grid_res, bool staged, bool oob,
                             const vrt_ray* rays, vrt_ray_hit* hits);
 // vrt_fetch_voxels: the stored voxels of `box` (valid, not empty) gathered into box_mat / box_rgb (device memory)
 hipError_t launch_fetch_voxels(hipStream_t st, int grid_res, const EditBox& box, const int8_t* mat, const uint8_t* rgb, int8_t* box_mat, uint8_t* box_rgb);
-// vrt_trace_radiance: samples [s0, s0 + count) of n_rays rays (device memory) traced into plane[n_rays * count] and folded into out[n_rays]
-// (vrt_radiance.h; k_trace_radiance, k_fold_radiance).  n_rays * count <= VRT_RADIANCE_ITEMS; staged / oob as for launch_cast_rays;
-// head: one word of device memory, the launch's work counter.
-hipError_t launch_trace_radiance(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n_rays,
-                                 int s0, int count, int n_samples, uint32_t first_frame, const vrt_path_ray* rays, f3* plane, vrt_radiance* out, unsigned* head);
-// vrt_gather_irradiance: samples [s0, s0 + count) of n_sensors sensors (device memory) gathered into plane[n_sensors * count] and folded into
-// out[n_sensors] (vrt_sensor.h; k_gather_irradiance, k_fold_irradiance).  n_sensors * count <= VRT_SENSOR_ITEMS; the rest as launch_trace_radiance.
-hipError_t launch_gather_irradiance(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n_sensors,
-                                    int s0, int count, int n_samples, uint32_t first_frame, const vrt_sensor* sensors, vrt_irradiance* plane, vrt_irradiance* out,
-                                    unsigned* head);
+// A sampled query Q (vrt_query.h: RadianceQuery, SensorQuery): samples [s0, s0 + count) of n records (device memory) worked into
+// plane[n * count] by the query's item kernel (k_trace_radiance, k_gather_irradiance) and folded into out[n] (k_fold_query).
+// n * count <= Q::max_items; staged / oob as for launch_cast_rays; head: one word of device memory, the launch's work counter.
+template <class Q>
+hipError_t launch_sampled_query(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n, int s0,
+                                int count, int n_samples, uint32_t first_frame, const typename Q::In* in, typename Q::Item* plane, typename Q::Out* out,
+                                unsigned* head);
 hipError_t query_render_residency(int grid_res, bool restir, bool instr, int* blocks_per_cu);
 hipError_t launch_render(hipStream_t st, int grid_res, bool restir, bool instr, int n_blocks, const FrameParams& fp, const SceneData& sc,
                          const PixelBuffers& out, unsigned* work_counters, unsigned launch_seq, int n_samples, int chunk_override);

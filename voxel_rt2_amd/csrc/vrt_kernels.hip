@@ -15,8 +15,9 @@
 //   k_temporal_group                                      the passes of several consecutive launches in one (static camera)
 //   k_tonemap                                             LDR presentation
 //   k_cast_rays / k_fetch_voxels                          vrt_cast_rays: caller-supplied rays through next_hit; vrt_fetch_voxels
-//   k_trace_radiance / k_fold_radiance                    vrt_trace_radiance: caller-supplied rays through the path state machine; the ordered sum
-//   k_gather_irradiance / k_fold_irradiance               vrt_gather_irradiance: a sun sample and a hemisphere path per (sensor, sample); the ordered sums
+//   k_trace_radiance                                      vrt_trace_radiance: caller-supplied rays through the path state machine
+//   k_gather_irradiance                                   vrt_gather_irradiance: a sun sample and a hemisphere path per (sensor, sample)
+//   k_fold_query<Q>                                       the ordered sums of either (vrt_query.h)
 //
 // k_render is a persistent-thread kernel: the grid is sized to the device's residency, each wave
 // keeps 64 path records in registers and pulls pixels (8x8 tiles, tile-major order) from a global
@@ -996,34 +997,78 @@ __global__ __launch_bounds__(64) void k_shade_probe(FrameParams fp, SceneData sc
                     lane_tables ? lane_tables + (size_t)i * VRT_SHADE_LANE_TABLE : nullptr);
 }
 
+// ---- the scene queries: what k_cast_rays, k_trace_radiance and k_gather_irradiance share -------------------------------------------
+// A query kernel's view of the pyramid.  STAGED: the coarse levels in LDS exactly as k_render keeps them for LdsPyramid (at 256^3 the
+// 32 KiB l1 level), the fine level through L2, and with MATS the material table beside them as k_render has it; else the launch is small
+// and everything is read from global memory.  OOB (STAGED only; GlobalPyramid always can): the instantiation carries the reference's
+// reading of cells outside the grid.
+template <int G, bool STAGED, bool OOB>
+using QueryView = typename std::conditional<STAGED, LdsPyramid<G, OOB>, GlobalPyramid<G>>::type;
+// The sizes of the staged levels; the kernel declares the arrays (__shared__ unsigned long long s_l1[STAGED ? N1 : 1] ...: separate
+// arrays, not one struct -- as a struct the same bytes cost the 128^3 sampled kernels five registers) and stage_query fills them.
+template <int G> struct QueryLds { static constexpr int N1 = GridDim<G>::n1 * GridDim<G>::n1 * GridDim<G>::n1, N2 = GridDim<G>::n2 * GridDim<G>::n2 * GridDim<G>::n2; };
+// Called by every thread of the workgroup (it holds the barrier).  Fills the view P, and points scl, the kernel's copy of sc, at what was
+// staged.  MATS: the material table too (a cast reads none and hands over a one-element array).  sc by value: through a reference to the
+// kernel's argument the unstaged instantiations no longer come out as the code they were with the staging written in the kernel.
+template <int G, bool STAGED, bool OOB, bool MATS, int N1, int N2, int NM>
+__device__ __forceinline__ void stage_query(const SceneData sc, unsigned long long (&s_l1)[N1], unsigned long long (&s_l2)[N2], float (&s_mats)[NM], float (&s_cull)[8],
+                                            QueryView<G, STAGED, OOB>& P, SceneData& scl) {
+    if constexpr (STAGED) {
+        for (int i = threadIdx.x; i < N1; i += blockDim.x) s_l1[i] = sc.pyr.l1[i];
+        if (threadIdx.x < N2) s_l2[threadIdx.x] = sc.pyr.l2[threadIdx.x];
+        if (threadIdx.x < 8) s_cull[threadIdx.x] = sc.cull[threadIdx.x];
+        if constexpr (MATS) for (int i = threadIdx.x; i < 128 * 14; i += blockDim.x) s_mats[i] = sc.mats[i];
+        __syncthreads();
+        P.l0 = sc.pyr.l0; P.l1 = s_l1; P.l2 = s_l2;
+        P.w3 = (G == 256) ? sc.pyr.l3[0] : 0ULL;
+        P.oob = sc.pyr.ref_oob != 0;
+        if constexpr (MATS) scl.mats = s_mats;
+        scl.cull = s_cull;
+    } else {
+        P.p = sc.pyr;
+    }
+}
+// A wave's reservation of a sampled query's items, k_render's refill: a wave reserves 64 items at a time from the launch's head word (one
+// returning atomic a wave, not one a lane) and hands them to its lanes itself, in lane order.  All three members are wave-uniform.
+struct WaveItems {
+    bool exhausted = false;         // the launch has no items left
+    unsigned next = 0u, end = 0u;   // items [next, end) are reserved for this wave
+    // mask: the ballot of the lanes that want an item (need: this lane's bit), not 0, and the launch not exhausted -- the caller tests
+    // both (`mask != 0ULL && !items.exhausted && items.take(...)`: with the wave-uniform test in here the compiler lays the loop out
+    // differently and k_trace_radiance<256, true, false> takes two more registers).  True on the lanes that got an item: `my` (< total).
+    __device__ __forceinline__ bool take(unsigned long long mask, bool need, int lane, unsigned* head, unsigned total, unsigned& my) {
+        if (next == end) {
+            unsigned base = 0u;
+            if (lane == 0) base = atomicAdd(head, 64u);   // (total <= the query's cap of 2^20 items and a grid of a few thousand waves overshoots by 64 each: no wrap)
+            base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+            next = base < total ? base : total;
+            end = (base + 64u < total) ? base + 64u : total;
+            if (base >= total) { exhausted = true; end = next; }
+        }
+        const unsigned avail = end - next;
+        const unsigned n = (unsigned)__popcll(mask);
+        const unsigned rank = (unsigned)__popcll(mask & ((1ULL << lane) - 1ULL));
+        my = next + rank;
+        next += (n < avail) ? n : avail;
+        return need && rank < avail;                      // my < end <= total
+    }
+};
+
 // ---- vrt_cast_rays: caller-supplied rays through next_hit (vrt_cast.h holds the per-ray body) ----------------------------------
 // One ray per lane, a grid-stride loop over the batch; the grid is what fits on the chip (plan_cast_blocks), so a workgroup stages
-// the pyramid once however many rays it walks.  STAGED: the coarse levels in LDS exactly as k_render keeps them for LdsPyramid (at
-// 256^3 the 32 KiB l1 level), the fine level through L2; else the batch is small and everything is read from global memory.
-// OOB (STAGED only; GlobalPyramid always can): the instantiation carries the reference's reading of cells outside the grid.
+// the pyramid once however many rays it walks (stage_query, without the material table: a cast reads none).
 // VRT_RAY_ANY_HIT is a property of a ray, the surface lookup it saves one of the instantiation: a wave whose rays all carry the
 // flag runs cast_row<true>; a mixed wave runs cast_row<false> once for all of them and drops the lookup's result on the flagged
 // lanes, which is the same record (the walk does not depend on the flag), so no wave walks twice.
 template <int G, bool STAGED, bool OOB>
 __global__ __launch_bounds__(256) void k_cast_rays(FrameParams fp, SceneData sc, long long n, const vrt_ray* __restrict__ rays, vrt_ray_hit* __restrict__ hits) {
-    constexpr int N1 = GridDim<G>::n1 * GridDim<G>::n1 * GridDim<G>::n1, N2 = GridDim<G>::n2 * GridDim<G>::n2 * GridDim<G>::n2;
-    __shared__ unsigned long long s_l1[STAGED ? N1 : 1];
-    __shared__ unsigned long long s_l2[STAGED ? N2 : 1];
+    __shared__ unsigned long long s_l1[STAGED ? QueryLds<G>::N1 : 1];
+    __shared__ unsigned long long s_l2[STAGED ? QueryLds<G>::N2 : 1];
+    __shared__ float s_mats[1];
     __shared__ float s_cull[8];
-    typename std::conditional<STAGED, LdsPyramid<G, OOB>, GlobalPyramid<G>>::type P;
+    QueryView<G, STAGED, OOB> P;
     SceneData scl = sc;
-    if constexpr (STAGED) {
-        for (int i = threadIdx.x; i < N1; i += blockDim.x) s_l1[i] = sc.pyr.l1[i];
-        if (threadIdx.x < N2) s_l2[threadIdx.x] = sc.pyr.l2[threadIdx.x];
-        if (threadIdx.x < 8) s_cull[threadIdx.x] = sc.cull[threadIdx.x];
-        __syncthreads();
-        P.l0 = sc.pyr.l0; P.l1 = s_l1; P.l2 = s_l2;
-        P.w3 = (G == 256) ? sc.pyr.l3[0] : 0ULL;
-        P.oob = sc.pyr.ref_oob != 0;
-        scl.cull = s_cull;
-    } else {
-        P.p = sc.pyr;
-    }
+    stage_query<G, STAGED, OOB, false>(sc, s_l1, s_l2, s_mats, s_cull, P, scl);
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const vrt_ray r = rays[i];
@@ -1048,37 +1093,22 @@ __global__ void k_fetch_voxels(EditBox box, int G, const int8_t* __restrict__ ma
 // ---- vrt_trace_radiance: caller-supplied rays through the path state machine (vrt_radiance.h holds the per-item body) --------------
 // The work item is (ray, sample): item i of a launch is ray i % n_rays, sample s0 + i / n_rays of the block -- a sample's rays side by
 // side, so neighbouring lanes start on neighbouring rays, and one ray with 4096 samples fills the chip as 4096 rays with one do.
-// A persistent grid (plan_radiance_blocks), one Path<false> per lane, k_render's refill: between segments a lane whose path ended
-// stores the item's value to plane[i] (every item has exactly one writer: no atomics on results) and takes the next item; a wave
-// reserves 64 items at a time from the launch's head word and hands them to its lanes itself.  Lanes at different depths run side by
-// side.  STAGED / OOB: k_cast_rays' views of the pyramid, with the material table staged beside the coarse levels as k_render has it.
+// A persistent grid (plan_cast_blocks over the items), one Path<false> per lane, k_render's refill (WaveItems): between segments a lane
+// whose path ended stores the item's value to plane[i] (every item has exactly one writer: no atomics on results) and takes the next
+// item.  Lanes at different depths run side by side.  STAGED / OOB: stage_query's views, with the material table.
 // The item of a ray's sample 0 (of the call, not of the chunk) also stores the first hit's distance to out[ray].t; nothing else of `out`
-// is written here (rgb carries k_fold_radiance's running sum).  An invalid ray's items are worth zero and are not traced.
+// is written here (rgb carries k_fold_query's running sum).  An invalid ray's items are worth zero and are not traced.
 template <int G, bool STAGED, bool OOB>
 __global__ __launch_bounds__(256, 2) void k_trace_radiance(FrameParams fp, SceneData sc, unsigned n_rays, unsigned total, unsigned s0, uint32_t first_frame,
                                                            const vrt_path_ray* __restrict__ rays, f3* __restrict__ plane, vrt_radiance* __restrict__ out,
                                                            unsigned* head) {
-    constexpr int N1 = GridDim<G>::n1 * GridDim<G>::n1 * GridDim<G>::n1, N2 = GridDim<G>::n2 * GridDim<G>::n2 * GridDim<G>::n2;
-    __shared__ unsigned long long s_l1[STAGED ? N1 : 1];
-    __shared__ unsigned long long s_l2[STAGED ? N2 : 1];
+    __shared__ unsigned long long s_l1[STAGED ? QueryLds<G>::N1 : 1];
+    __shared__ unsigned long long s_l2[STAGED ? QueryLds<G>::N2 : 1];
     __shared__ float s_mats[STAGED ? 128 * 14 : 1];
     __shared__ float s_cull[8];
-    typename std::conditional<STAGED, LdsPyramid<G, OOB>, GlobalPyramid<G>>::type P;
+    QueryView<G, STAGED, OOB> P;
     SceneData scl = sc;
-    if constexpr (STAGED) {
-        for (int i = threadIdx.x; i < N1; i += blockDim.x) s_l1[i] = sc.pyr.l1[i];
-        if (threadIdx.x < N2) s_l2[threadIdx.x] = sc.pyr.l2[threadIdx.x];
-        if (threadIdx.x < 8) s_cull[threadIdx.x] = sc.cull[threadIdx.x];
-        for (int i = threadIdx.x; i < 128 * 14; i += blockDim.x) s_mats[i] = sc.mats[i];
-        __syncthreads();
-        P.l0 = sc.pyr.l0; P.l1 = s_l1; P.l2 = s_l2;
-        P.w3 = (G == 256) ? sc.pyr.l3[0] : 0ULL;
-        P.oob = sc.pyr.ref_oob != 0;
-        scl.mats = s_mats;
-        scl.cull = s_cull;
-    } else {
-        P.p = sc.pyr;
-    }
+    stage_query<G, STAGED, OOB, true>(sc, s_l1, s_l2, s_mats, s_cull, P, scl);
     const int lane = threadIdx.x & 63;
     Path<false> p;
     p.depth = -1;
@@ -1086,39 +1116,24 @@ __global__ __launch_bounds__(256, 2) void k_trace_radiance(FrameParams fp, Scene
     float t_first = DM_INF;
     TraceStats ts;                             // a sink: a query counts nothing
     stats_zero(ts);
-    bool exhausted = false;                    // wave-uniform
-    unsigned chunk_next = 0u, chunk_end = 0u;  // wave-uniform: items [chunk_next, chunk_end) are reserved for this wave
+    WaveItems items;
     for (;;) {
         const bool need = p.depth < 0;
         const unsigned long long mask = __ballot(need);
-        if (mask != 0ULL && !exhausted) {
-            if (chunk_next == chunk_end) {
-                unsigned base = 0u;
-                if (lane == 0) base = atomicAdd(head, 64u);   // (total <= VRT_RADIANCE_ITEMS and a grid of a few thousand waves overshoots by 64 each: no wrap)
-                base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-                chunk_next = base < total ? base : total;
-                chunk_end = (base + 64u < total) ? base + 64u : total;
-                if (base >= total) { exhausted = true; chunk_end = chunk_next; }
-            }
-            const unsigned avail = chunk_end - chunk_next;
-            const unsigned n = (unsigned)__popcll(mask);
-            const unsigned rank = (unsigned)__popcll(mask & ((1ULL << lane) - 1ULL));
-            const unsigned my = chunk_next + rank;
-            chunk_next += (n < avail) ? n : avail;
-            if (need && rank < avail) {        // my < chunk_end <= total
-                const unsigned ray = my % n_rays, sample = s0 + my / n_rays;
-                const vrt_path_ray r = rays[ray];
-                if (radiance_ray_valid(r)) {
-                    item = my;
-                    radiance_begin(fp, p, r, first_frame + sample);
-                } else {
-                    plane[my] = mk3(0.0f);
-                    if (sample == 0u) out[ray].t = DM_INF;
-                }
+        unsigned my = 0u;
+        if (mask != 0ULL && !items.exhausted && items.take(mask, need, lane, head, total, my)) {
+            const unsigned ray = my % n_rays, sample = s0 + my / n_rays;
+            const vrt_path_ray r = rays[ray];
+            if (radiance_ray_valid(r)) {
+                item = my;
+                radiance_begin(fp, p, r, first_frame + sample);
+            } else {
+                plane[my] = RadianceQuery::zero();
+                if (sample == 0u) out[ray].t = DM_INF;
             }
         }
         if (__ballot(p.depth >= 0) == 0ULL) {
-            if (exhausted) break;
+            if (items.exhausted) break;
             continue;
         }
         if (p.depth >= 0) {
@@ -1132,22 +1147,10 @@ __global__ __launch_bounds__(256, 2) void k_trace_radiance(FrameParams fp, Scene
         }
     }
 }
-// One lane per ray of the block: the chunk's `count` values of the ray added in sample order to the sum the chunks before left in
-// out[ray].rgb (first: to zero), and with the last chunk the division by the call's number of samples (radiance_fold, radiance_mean).
-__global__ __launch_bounds__(256) void k_fold_radiance(unsigned n_rays, int count, int first, int last, int n_samples, const f3* __restrict__ plane,
-                                                       vrt_radiance* __restrict__ out) {
-    const unsigned ray = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ray >= n_rays) return;
-    f3 acc = first ? mk3(0.0f) : mk3(out[ray].rgb[0], out[ray].rgb[1], out[ray].rgb[2]);
-    acc = radiance_fold(acc, plane + ray, (long long)n_rays, count);
-    if (last) acc = radiance_mean(acc, n_samples);
-    out[ray].rgb[0] = acc.x; out[ray].rgb[1] = acc.y; out[ray].rgb[2] = acc.z;
-}
 
 // ---- vrt_gather_irradiance: caller-supplied surface points; sun sample and hemisphere path per (sensor, sample) (vrt_sensor.h) ----
 // The work item is (sensor, sample): item i of a launch is sensor i % n_sensors, sample s0 + i / n_sensors of the block.  The schedule is
-// k_trace_radiance's: a persistent grid, one Path<false> per lane, a wave reserves 64 items at a time from the launch's head word and
-// refills the lanes whose item ended.  A fresh item has made its four draws (sensor_begin) and waits for its shadow ray; the shadow
+// k_trace_radiance's.  A fresh item has made its four draws (sensor_begin) and waits for its shadow ray; the shadow
 // rays of waiting items are walked TOGETHER (sensor_sun) once VRT_SENSOR_SUN_BATCH lanes wait, or when no lane has a path to step, or
 // when the launch has no items left -- a refill finds a lane or two a turn, and a walk for them alone would cost the whole wave a
 // walk's time.  Waiting lanes sit out the segment step.  The order of walks cannot change a result: an item owns its two random streams.
@@ -1160,27 +1163,13 @@ __global__ __launch_bounds__(256) void k_fold_radiance(unsigned n_rays, int coun
 template <int G, bool STAGED, bool OOB>
 __global__ __launch_bounds__(256, 2) void k_gather_irradiance(FrameParams fp, SceneData sc, unsigned n_sensors, unsigned total, unsigned s0, uint32_t first_frame,
                                                               const vrt_sensor* __restrict__ sensors, vrt_irradiance* __restrict__ plane, unsigned* head) {
-    constexpr int N1 = GridDim<G>::n1 * GridDim<G>::n1 * GridDim<G>::n1, N2 = GridDim<G>::n2 * GridDim<G>::n2 * GridDim<G>::n2;
-    __shared__ unsigned long long s_l1[STAGED ? N1 : 1];
-    __shared__ unsigned long long s_l2[STAGED ? N2 : 1];
+    __shared__ unsigned long long s_l1[STAGED ? QueryLds<G>::N1 : 1];
+    __shared__ unsigned long long s_l2[STAGED ? QueryLds<G>::N2 : 1];
     __shared__ float s_mats[STAGED ? 128 * 14 : 1];
     __shared__ float s_cull[8];
-    typename std::conditional<STAGED, LdsPyramid<G, OOB>, GlobalPyramid<G>>::type P;
+    QueryView<G, STAGED, OOB> P;
     SceneData scl = sc;
-    if constexpr (STAGED) {
-        for (int i = threadIdx.x; i < N1; i += blockDim.x) s_l1[i] = sc.pyr.l1[i];
-        if (threadIdx.x < N2) s_l2[threadIdx.x] = sc.pyr.l2[threadIdx.x];
-        if (threadIdx.x < 8) s_cull[threadIdx.x] = sc.cull[threadIdx.x];
-        for (int i = threadIdx.x; i < 128 * 14; i += blockDim.x) s_mats[i] = sc.mats[i];
-        __syncthreads();
-        P.l0 = sc.pyr.l0; P.l1 = s_l1; P.l2 = s_l2;
-        P.w3 = (G == 256) ? sc.pyr.l3[0] : 0ULL;
-        P.oob = sc.pyr.ref_oob != 0;
-        scl.mats = s_mats;
-        scl.cull = s_cull;
-    } else {
-        P.p = sc.pyr;
-    }
+    stage_query<G, STAGED, OOB, true>(sc, s_l1, s_l2, s_mats, s_cull, P, scl);
     const int lane = threadIdx.x & 63;
     Path<false> p;
     p.depth = -1;
@@ -1190,43 +1179,28 @@ __global__ __launch_bounds__(256, 2) void k_gather_irradiance(FrameParams fp, Sc
     float ndl = 0.0f;
     TraceStats ts;                             // a sink: a query counts nothing
     stats_zero(ts);
-    bool exhausted = false;                    // wave-uniform
-    unsigned chunk_next = 0u, chunk_end = 0u;  // wave-uniform: items [chunk_next, chunk_end) are reserved for this wave
+    WaveItems items;
     for (;;) {
         const bool need = p.depth < 0;
         const unsigned long long mask = __ballot(need);
-        if (mask != 0ULL && !exhausted) {
-            if (chunk_next == chunk_end) {
-                unsigned base = 0u;
-                if (lane == 0) base = atomicAdd(head, 64u);   // (total <= VRT_SENSOR_ITEMS and a grid of a few thousand waves overshoots by 64 each: no wrap)
-                base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-                chunk_next = base < total ? base : total;
-                chunk_end = (base + 64u < total) ? base + 64u : total;
-                if (base >= total) { exhausted = true; chunk_end = chunk_next; }
-            }
-            const unsigned avail = chunk_end - chunk_next;
-            const unsigned n = (unsigned)__popcll(mask);
-            const unsigned rank = (unsigned)__popcll(mask & ((1ULL << lane) - 1ULL));
-            const unsigned my = chunk_next + rank;
-            chunk_next += (n < avail) ? n : avail;
-            if (need && rank < avail) {        // my < chunk_end <= total
-                const unsigned sensor = my % n_sensors, sample = s0 + my / n_sensors;
-                const vrt_sensor s = sensors[sensor];
-                if (sensor_valid(s) && sensor_begin(fp, p, s, first_frame + sample, ldir, ndl)) {
-                    item = my;
-                    sun_pending = true;
-                } else {
-                    plane[my] = sensor_zero();
-                }
+        unsigned my = 0u;
+        if (mask != 0ULL && !items.exhausted && items.take(mask, need, lane, head, total, my)) {
+            const unsigned sensor = my % n_sensors, sample = s0 + my / n_sensors;
+            const vrt_sensor s = sensors[sensor];
+            if (sensor_valid(s) && sensor_begin(fp, p, s, first_frame + sample, ldir, ndl)) {
+                item = my;
+                sun_pending = true;
+            } else {
+                plane[my] = SensorQuery::zero();
             }
         }
         const unsigned long long live = __ballot(p.depth >= 0);
         if (live == 0ULL) {
-            if (exhausted) break;
+            if (items.exhausted) break;
             continue;
         }
         const unsigned long long waiting = __ballot(sun_pending);   // a subset of `live`
-        if (waiting != 0ULL && (__popcll(waiting) >= VRT_SENSOR_SUN_BATCH || waiting == live || exhausted)) {
+        if (waiting != 0ULL && (__popcll(waiting) >= VRT_SENSOR_SUN_BATCH || waiting == live || items.exhausted)) {
             if (sun_pending) {
                 float vis;
                 const f3 sun = sensor_sun(fp, scl, P, p.pos, ldir, ndl, ts, vis);
@@ -1249,16 +1223,15 @@ __global__ __launch_bounds__(256, 2) void k_gather_irradiance(FrameParams fp, Sc
         }
     }
 }
-// One lane per sensor of the block: the chunk's `count` records of the sensor added in sample order to the sums the chunks before left
-// in out[sensor] (first: to zero), and with the last chunk the division by the call's number of samples (sensor_fold, sensor_mean).
-__global__ __launch_bounds__(256) void k_fold_irradiance(unsigned n_sensors, int count, int first, int last, int n_samples, const vrt_irradiance* __restrict__ plane,
-                                                         vrt_irradiance* __restrict__ out) {
+
+// ---- the sampled queries' fold (query_fold, vrt_query.h) -------------------------------------------------------------------------
+// One lane per record of the block: the chunk's `count` plane values of the record added in sample order to the sum the chunks before
+// left in out[k] (first: to zero), and with the last chunk the division by the call's number of samples.
+template <class Q>
+__global__ __launch_bounds__(256) void k_fold_query(unsigned n, int count, int first, int last, int n_samples, const typename Q::Item* __restrict__ plane,
+                                                    typename Q::Out* __restrict__ out) {
     const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_sensors) return;
-    vrt_irradiance acc = first ? sensor_zero() : out[k];
-    acc = sensor_fold(acc, plane + k, (long long)n_sensors, count);
-    if (last) acc = sensor_mean(acc, n_samples);
-    out[k] = acc;
+    if (k < n) query_fold<Q>(out[k], plane + k, (long long)n, count, first != 0, last != 0, n_samples);
 }
 
 // ---- host-side launchers -----------------------------------------------------------------------
@@ -1441,14 +1414,41 @@ hipError_t launch_trace_probe(hipStream_t st, int grid_res, int walk, const Pyra
     return hipSuccess;
 }
 
-typedef void (*cast_kernel_fn)(FrameParams, SceneData, long long, const vrt_ray*, vrt_ray_hit*);
+// The ONE place a query launch's (grid_res, staged, oob) becomes an instantiation of its kernel K (CastKernel, ItemKernel<Q>) -- and
+// that instantiation's residency, asked once: it depends on nothing a call can change (contexts of one process share the device kind).
+template <class K>
+static hipError_t query_kernel(int grid_res, bool staged, bool oob, typename K::fn_t* fn, int* per_cu) {
+    if (staged) VRT_BY_GRID(grid_res, VRT_BY_2(oob, false, *fn = (K::template get<G, true, A>())));
+    else VRT_BY_GRID(grid_res, *fn = (K::template get<G, false, true>()));
+    static std::atomic<int> residency[2][3] = {};   // (one table per K)
+    std::atomic<int>& cached = residency[grid_res == 256 ? 1 : 0][staged ? (oob ? 2 : 1) : 0];
+    *per_cu = cached.load(std::memory_order_relaxed);
+    if (*per_cu == 0) {
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, *fn, 256, 0);
+        if (e != hipSuccess) return e;
+        cached.store(*per_cu, std::memory_order_relaxed);
+    }
+    return hipSuccess;
+}
+struct CastKernel {
+    typedef void (*fn_t)(FrameParams, SceneData, long long, const vrt_ray*, vrt_ray_hit*);
+    template <int G, bool STAGED, bool OOB> static fn_t get() { return k_cast_rays<G, STAGED, OOB>; }
+};
+template <class Q> struct ItemKernel;   // the kernel that steps Q's items
+template <> struct ItemKernel<RadianceQuery> {
+    typedef void (*fn_t)(FrameParams, SceneData, unsigned, unsigned, unsigned, uint32_t, const vrt_path_ray*, f3*, vrt_radiance*, unsigned*);
+    template <int G, bool STAGED, bool OOB> static fn_t get() { return k_trace_radiance<G, STAGED, OOB>; }
+};
+template <> struct ItemKernel<SensorQuery> {
+    typedef void (*fn_t)(FrameParams, SceneData, unsigned, unsigned, unsigned, uint32_t, const vrt_sensor*, vrt_irradiance*, unsigned*);
+    template <int G, bool STAGED, bool OOB> static fn_t get() { return k_gather_irradiance<G, STAGED, OOB>; }
+};
+
 hipError_t launch_cast_rays(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n,
                             const vrt_ray* rays, vrt_ray_hit* hits) {
-    cast_kernel_fn fn = nullptr;
-    if (staged) VRT_BY_GRID(grid_res, VRT_BY_2(oob, false, fn = (k_cast_rays<G, true, A>)));
-    else VRT_BY_GRID(grid_res, fn = (k_cast_rays<G, false, true>));
+    CastKernel::fn_t fn = nullptr;
     int per_cu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0);
+    hipError_t e = query_kernel<CastKernel>(grid_res, staged, oob, &fn, &per_cu);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(fn, dim3(plan_cast_blocks(n, n_cu, per_cu)), dim3(256), 0, st, fp, sc, n, rays, hits);
     VRT_LAUNCH_CHECK();
@@ -1460,67 +1460,34 @@ hipError_t launch_fetch_voxels(hipStream_t st, int grid_res, const EditBox& box,
     return hipSuccess;
 }
 
-// vrt_trace_radiance: one chunk -- samples [s0, s0 + count) of n_rays rays -- traced into `plane` and folded into `out`.  n_rays * count
-// is at most VRT_RADIANCE_ITEMS (plan_radiance_chunk); `head`: the launch's work counter, zeroed here on the stream.
-typedef void (*radiance_kernel_fn)(FrameParams, SceneData, unsigned, unsigned, unsigned, uint32_t, const vrt_path_ray*, f3*, vrt_radiance*, unsigned*);
-hipError_t launch_trace_radiance(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n_rays,
-                                 int s0, int count, int n_samples, uint32_t first_frame, const vrt_path_ray* rays, f3* plane, vrt_radiance* out, unsigned* head) {
-    const long long items = n_rays * count;
-    if (n_rays < 1 || count < 1 || s0 < 0 || s0 + count > n_samples || items > VRT_RADIANCE_ITEMS) return hipErrorInvalidValue;
-    radiance_kernel_fn fn = nullptr;
-    if (staged) VRT_BY_GRID(grid_res, VRT_BY_2(oob, false, fn = (k_trace_radiance<G, true, A>)));
-    else VRT_BY_GRID(grid_res, fn = (k_trace_radiance<G, false, true>));
-    // the instantiation's residency, asked once (it depends on nothing a call can change; contexts of one process share the device kind)
-    static std::atomic<int> residency[2][3] = {};
-    std::atomic<int>& cached = residency[grid_res == 256 ? 1 : 0][staged ? (oob ? 2 : 1) : 0];
-    int per_cu = cached.load(std::memory_order_relaxed);
-    hipError_t e = hipSuccess;
-    if (per_cu == 0) {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0);
-        if (e != hipSuccess) return e;
-        cached.store(per_cu, std::memory_order_relaxed);
-    }
+// A sampled query's chunk -- samples [s0, s0 + count) of n records -- worked into `plane` by the query's item kernel and folded into `out`.
+// n * count is at most Q::max_items (plan_query_chunk); `head`: the launch's work counter, zeroed here on the stream.
+template <class Q>
+hipError_t launch_sampled_query(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n, int s0,
+                                int count, int n_samples, uint32_t first_frame, const typename Q::In* in, typename Q::Item* plane, typename Q::Out* out,
+                                unsigned* head) {
+    const long long items = n * count;
+    if (n < 1 || count < 1 || s0 < 0 || s0 + count > n_samples || items > Q::max_items) return hipErrorInvalidValue;
+    typename ItemKernel<Q>::fn_t fn = nullptr;
+    int per_cu = 0;
+    hipError_t e = query_kernel<ItemKernel<Q>>(grid_res, staged, oob, &fn, &per_cu);
+    if (e != hipSuccess) return e;
     e = hipMemsetAsync(head, 0, sizeof(unsigned), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fn, dim3(plan_radiance_blocks(items, n_cu, per_cu)), dim3(256), 0, st, fp, sc, (unsigned)n_rays, (unsigned)items, (unsigned)s0, first_frame,
-                       rays, plane, out, head);
+    const dim3 grid(plan_cast_blocks(items, n_cu, per_cu));
+    if constexpr (std::is_same<Q, RadianceQuery>::value)   // (k_trace_radiance stores the first hit's distance to out[ray].t itself)
+        hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, fp, sc, (unsigned)n, (unsigned)items, (unsigned)s0, first_frame, in, plane, out, head);
+    else
+        hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, fp, sc, (unsigned)n, (unsigned)items, (unsigned)s0, first_frame, in, plane, head);
     VRT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_fold_radiance, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, st, (unsigned)n_rays, count, s0 == 0 ? 1 : 0,
-                       s0 + count == n_samples ? 1 : 0, n_samples, (const f3*)plane, out);
+    hipLaunchKernelGGL(k_fold_query<Q>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (unsigned)n, count, s0 == 0 ? 1 : 0,
+                       s0 + count == n_samples ? 1 : 0, n_samples, (const typename Q::Item*)plane, out);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }
-
-// vrt_gather_irradiance: one chunk -- samples [s0, s0 + count) of n_sensors sensors -- gathered into `plane` and folded into `out`.
-// n_sensors * count is at most VRT_SENSOR_ITEMS (plan_sensor_chunk); `head`: the launch's work counter, zeroed here on the stream.
-typedef void (*sensor_kernel_fn)(FrameParams, SceneData, unsigned, unsigned, unsigned, uint32_t, const vrt_sensor*, vrt_irradiance*, unsigned*);
-hipError_t launch_gather_irradiance(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n_sensors,
-                                    int s0, int count, int n_samples, uint32_t first_frame, const vrt_sensor* sensors, vrt_irradiance* plane, vrt_irradiance* out,
-                                    unsigned* head) {
-    const long long items = n_sensors * count;
-    if (n_sensors < 1 || count < 1 || s0 < 0 || s0 + count > n_samples || items > VRT_SENSOR_ITEMS) return hipErrorInvalidValue;
-    sensor_kernel_fn fn = nullptr;
-    if (staged) VRT_BY_GRID(grid_res, VRT_BY_2(oob, false, fn = (k_gather_irradiance<G, true, A>)));
-    else VRT_BY_GRID(grid_res, fn = (k_gather_irradiance<G, false, true>));
-    // the instantiation's residency, asked once (launch_trace_radiance)
-    static std::atomic<int> residency[2][3] = {};
-    std::atomic<int>& cached = residency[grid_res == 256 ? 1 : 0][staged ? (oob ? 2 : 1) : 0];
-    int per_cu = cached.load(std::memory_order_relaxed);
-    hipError_t e = hipSuccess;
-    if (per_cu == 0) {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0);
-        if (e != hipSuccess) return e;
-        cached.store(per_cu, std::memory_order_relaxed);
-    }
-    e = hipMemsetAsync(head, 0, sizeof(unsigned), st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fn, dim3(plan_radiance_blocks(items, n_cu, per_cu)), dim3(256), 0, st, fp, sc, (unsigned)n_sensors, (unsigned)items, (unsigned)s0, first_frame,
-                       sensors, plane, head);
-    VRT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_fold_irradiance, dim3((unsigned)((n_sensors + 255) / 256)), dim3(256), 0, st, (unsigned)n_sensors, count, s0 == 0 ? 1 : 0,
-                       s0 + count == n_samples ? 1 : 0, n_samples, (const vrt_irradiance*)plane, out);
-    VRT_LAUNCH_CHECK();
-    return hipSuccess;
-}
+template hipError_t launch_sampled_query<RadianceQuery>(hipStream_t, int, bool, bool, int, const FrameParams&, const SceneData&, long long, int, int, int, uint32_t,
+                                                        const vrt_path_ray*, f3*, vrt_radiance*, unsigned*);
+template hipError_t launch_sampled_query<SensorQuery>(hipStream_t, int, bool, bool, int, const FrameParams&, const SceneData&, long long, int, int, int, uint32_t,
+                                                      const vrt_sensor*, vrt_irradiance*, vrt_irradiance*, unsigned*);
 
 }  // namespace vrt

@@ -195,7 +195,7 @@ static inline int plan_partial_blocks(int all_blocks, int grid_div) { return (al
 static inline int plan_set_of(unsigned pipe_seq, int n_sets) { return (int)(pipe_seq % (unsigned)n_sets); }
 static inline int plan_lane_of(unsigned pipe_seq, int n_streams) { return (int)(pipe_seq % (unsigned)n_streams); }
 
-// ---- vrt_cast_rays -----------------------------------------------------------------------------------------------------------
+// ---- vrt_cast_rays (its two rules of thumb also serve the sampled queries, below) ------------------------------------------------
 // Which view of the pyramid a batch of n rays is walked on: the coarse levels staged in LDS once per workgroup (k_render's
 // LdsPyramid), or everything through global memory.  Staging is 4 KiB + 64 B a workgroup at 128^3 and 32.5 KiB at 256^3: a cost per
 // WORKGROUP, which a grid sized from the CU count pays a bounded number of times, but which a pick of one ray or a fan of a few
@@ -214,39 +214,32 @@ static inline int plan_cast_blocks(long long n, int n_cu, int blocks_per_cu) {
     return (int)(want < fit ? want : fit);
 }
 
-// ---- vrt_trace_radiance --------------------------------------------------------------------------------------------------------
-// The work item is (ray, sample); a finished item leaves its value in a scratch plane of 12 bytes an item, which k_fold_radiance sums
-// per ray in sample order.  The plane is bounded: a call is cut into blocks of rays, and a block's samples into chunks of WHOLE samples
-// (every ray of the block, samples [s0, s0 + count)), so that no launch has more than VRT_RADIANCE_ITEMS items -- 12 MiB of scratch,
-// whatever n and n_samples are.  The sum is carried in `out` from chunk to chunk in sample order (radiance_fold, vrt_radiance.h), so
-// the cut cannot change a bit of the result (tests/test_radiance_host.py, tests/test_gpu_radiance.py).
+// ---- the sampled queries: vrt_trace_radiance, vrt_gather_irradiance (vrt_query.h) ----------------------------------------------------
+// The work item is (record, sample) -- (ray, sample) or (sensor, sample); a finished item leaves its value in a scratch plane -- 12 bytes
+// an item for a radiance, a 32-byte vrt_irradiance record of four terms for a sensor -- which k_fold_query sums per record in sample
+// order.  The plane is bounded: a call is cut into blocks of records, and a block's samples into chunks of WHOLE samples (every record of
+// the block, samples [s0, s0 + count)), so that no launch has more items than the query's cap -- 12 MiB of scratch, whatever n and
+// n_samples are.  The sums are carried in `out` from chunk to chunk in sample order (query_fold, vrt_query.h), so the cut cannot change a
+// bit of the result (tests/test_radiance_host.py, tests/test_sensor_host.py and their GPU twins).  The sensors' cap is the same BYTES as
+// the radiances' (the two queries run on one stream and share the allocation): 12 MiB / 32 = 393 216 items a launch.
+// Which view of the pyramid a launch of `items` items walks on is plan_cast_staged's rule on the number of items (a path is several
+// walks, so staging pays no later than it does for single rays); its workgroups are plan_cast_blocks' over the items.
 #define VRT_RADIANCE_ITEMS (1 << 20)
-// Rays of a block (also what a host-path call stages at a time: 48 bytes of device memory a ray).
-static inline long long plan_radiance_rays(long long n) { return n < (1 << 18) ? n : (1 << 18); }
-// Whole samples of a chunk over a block of n_rays rays (1 <= n_rays <= plan_radiance_rays' bound), n_samples to do in all: at least 1.
-static inline int plan_radiance_chunk(long long n_rays, int n_samples) {
-    const long long fit = VRT_RADIANCE_ITEMS / (n_rays > 0 ? n_rays : 1);
-    return (int)(fit < 1 ? 1 : fit < n_samples ? fit : n_samples);
-}
-// Which view of the pyramid a launch of `items` items walks on: plan_cast_staged's rule on the number of items (a path is several walks,
-// so staging pays no later than it does for single rays).  `knob`: Knobs::cast_view.
-static inline bool plan_radiance_staged(long long items, int knob) { return plan_cast_staged(items, knob); }
-// Workgroups of a launch over `items` items, 256 a workgroup per turn: plan_cast_blocks' rule.
-static inline int plan_radiance_blocks(long long items, int n_cu, int blocks_per_cu) { return plan_cast_blocks(items, n_cu, blocks_per_cu); }
-
-// ---- vrt_gather_irradiance -----------------------------------------------------------------------------------------------------
-// The work item is (sensor, sample); a finished item leaves its four terms in a scratch plane of 32 bytes an item (a vrt_irradiance
-// record), which k_fold_irradiance sums per sensor in sample order.  The plane is bounded by BYTES, the same 12 MiB as
-// VRT_RADIANCE_ITEMS' (the two queries run on one stream and share the allocation): VRT_SENSOR_ITEMS = 12 MiB / 32 = 393 216 items a
-// launch.  A call is cut into blocks of sensors, and a block's samples into chunks of WHOLE samples, as vrt_trace_radiance's; the sums
-// are carried in `out` from chunk to chunk in sample order (sensor_fold, vrt_sensor.h), so the cut cannot change a bit of the result
-// (tests/test_sensor_host.py, tests/test_gpu_sensor.py).
 #define VRT_SENSOR_ITEM_BYTES 32
 #define VRT_SENSOR_ITEMS ((VRT_RADIANCE_ITEMS * 12) / VRT_SENSOR_ITEM_BYTES)
-// Sensors of a block (also what a host-path call stages at a time: 64 bytes of device memory a sensor): one sample of a block fits the plane.
-static inline long long plan_sensor_rays(long long n) { return n < (1 << 18) ? n : (1 << 18); }
-// Whole samples of a chunk over a block of n_sensors sensors (1 <= n_sensors <= plan_sensor_rays' bound), n_samples to do in all: at least 1.
-static inline int plan_sensor_chunk(long long n_sensors, int n_samples) {
-    const long long fit = VRT_SENSOR_ITEMS / (n_sensors > 0 ? n_sensors : 1);
+// Records of a block (also what a host-path call stages at a time: 48 bytes of device memory a ray, 64 a sensor): one sample of a block
+// fits either plane.
+static inline long long plan_query_rays(long long n) { return n < (1 << 18) ? n : (1 << 18); }
+// Whole samples of a chunk over a block of n records (1 <= n <= plan_query_rays' bound) under a cap of `cap` items a launch, n_samples to
+// do in all: at least 1.
+static inline int plan_query_chunk(long long cap, long long n, int n_samples) {
+    const long long fit = cap / (n > 0 ? n : 1);
     return (int)(fit < 1 ? 1 : fit < n_samples ? fit : n_samples);
 }
+// The two queries' own names for the rules above, as the host emulations' exported entry points are defined (radiance_emul_chunk,
+// sensor_emul_rays and the like: tests/emul/).
+static inline long long plan_radiance_rays(long long n) { return plan_query_rays(n); }
+static inline int plan_radiance_chunk(long long n_rays, int n_samples) { return plan_query_chunk(VRT_RADIANCE_ITEMS, n_rays, n_samples); }
+static inline bool plan_radiance_staged(long long items, int knob) { return plan_cast_staged(items, knob); }
+static inline long long plan_sensor_rays(long long n) { return plan_query_rays(n); }
+static inline int plan_sensor_chunk(long long n_sensors, int n_samples) { return plan_query_chunk(VRT_SENSOR_ITEMS, n_sensors, n_samples); }
