@@ -13,6 +13,7 @@ and both of its tests are strict `t < closest`, the floor's first -- (1) whateve
 and voxel is accepted iff it is below t_max, a tie going to the floor with either start; (2) a floor at f >= t_max that it skips cannot
 hide a voxel at v < t_max from the run with inf, since v < f there too.
 Invalid rays (include/vrt_api.h) are never shown to the oracle: their record is the miss record."""
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -458,7 +459,30 @@ def lib():
         _lib.cast_emul_chunk.restype = C.c_longlong
         _lib.cast_emul_blocks.argtypes = [C.c_longlong, C.c_int, C.c_int]
         _lib.cast_emul_fetch.argtypes = [C.c_int] + [C.c_void_p] * 6
+        _lib.cast_emul_poison.argtypes = [C.c_int]
+        _lib.cast_emul_probe.argtypes = [C.c_void_p] * 3
+        _lib.cast_emul_probe.restype = None
     return _lib
+
+
+@contextlib.contextmanager
+def poisoned(emul=None):
+    """The emulator hands the device functions frame parameters whose unread fields are poisoned (tests/emul/query_emul.h) while this is
+    open.  emul: the emulator's library and the prefix of its exports (this module's by default)."""
+    so, prefix = emul or (lib(), "cast")
+    was = getattr(so, prefix + "_emul_poison")(1)
+    try:
+        yield
+    finally:
+        getattr(so, prefix + "_emul_poison")(was)
+
+
+def probe(scene_record, emul=None):
+    """(float32[8], int32[4]) of frame_params_probe (tests/emul/query_emul.h) on the frame parameters of the emulator's current mode."""
+    so, prefix = emul or (lib(), "cast")
+    out, ints = np.zeros(8, np.float32), np.zeros(4, np.int32)
+    getattr(so, prefix + "_emul_probe")(C.byref(scene_record), orc.fptr(out), orc.fptr(ints))
+    return out, ints
 
 
 def switch_over():

@@ -47,4 +47,14 @@ int cast_emul_fetch(int G, const int* lo, const int* hi, const int8_t* mat, cons
     return 0;
 }
 
+// the mode of the frame parameters every later call hands the device functions (query_emul.h): 0 plain, 1 poisoned; returns the mode before
+int cast_emul_poison(int on) { const int was = g_query_poison; g_query_poison = on ? 1 : 0; return was; }
+// frame_params_probe on the record a call on scene `s` would hand over in the current mode: float out[8], int32 ints[4]
+void cast_emul_probe(const CastScene* s, float* out, int32_t* ints) {
+    FrameParams fp;
+    SceneData sc;
+    scene_common(*s, fp, sc);
+    frame_params_probe(fp, out, ints);
+}
+
 }  // extern "C"

@@ -50,10 +50,29 @@ static void with_view(const SceneData& sc, int staged, Fn fn) {
     else { static StagedPyramid<G, false> P; stage(P); }
 }
 
-// What every query reads of a scene record (CastScene of cast_emul.cpp, RadScene): the floor, the pyramid, the texels, the culling box.
+// The frame parameters a query is handed have two modes.  Plain (0): every field a query is not meant to read is zero.  Poisoned (1,
+// query_emul_poison): every such field holds a hostile value -- every 32-bit word of the record a quiet NaN's bits (so a field added to
+// FrameParams later is poisoned by default), the integer fields the largest int or -1, `frame` all ones, camera_is_moving the value the
+// plain mode does not hold.  A query's answer must not tell the modes apart (tests/test_*_host.py: the same bytes).
+static int g_query_poison = 0;
+static void frame_params_base(FrameParams& fp) {
+    memset(&fp, 0, sizeof(fp));
+    if (!g_query_poison) return;
+    static_assert(sizeof(FrameParams) % 4 == 0, "FrameParams is a record of 32-bit fields");
+    const uint32_t qnan = 0x7fc00000u;
+    for (size_t k = 0; k < sizeof(fp); k += 4) memcpy((char*)&fp + k, &qnan, 4);
+    fp.W = fp.H = 0x7fffffff;
+    fp.row0 = -1; fp.row1 = 0x7fffffff;
+    fp.stripe_rows = -1; fp.stripe_period = 0x7fffffff; fp.stripe_first = -1; fp.stripe_tile_rows = 0x7fffffff;
+    fp.frame = 0xffffffffu;
+    fp.camera_is_moving = 1;   // (plain: 0; scene_sampled takes the other value in either mode)
+}
+
+// What every query reads of a scene record (CastScene of cast_emul.cpp, RadScene) -- of the frame parameters the floor (height, colour,
+// material) and voxel_edges, as query_inputs (vrt_api.hip) lists them; of the scene the pyramid, the texels, the culling box.
 template <class Scene>
 static void scene_common(const Scene& s, FrameParams& fp, SceneData& sc) {
-    memset(&fp, 0, sizeof(fp));
+    frame_params_base(fp);
     fp.floor_height = s.floor_height;
     fp.floor_color = mk3(s.floor_color[0], s.floor_color[1], s.floor_color[2]);
     fp.floor_material = s.floor_material;
@@ -63,6 +82,16 @@ static void scene_common(const Scene& s, FrameParams& fp, SceneData& sc) {
     sc.pyr.ref_oob = s.ref_oob;
     sc.grid = s.grid;
     sc.cull = s.cull;
+}
+// The liveness check of the poisoned mode: functions that DO read fields no query reads, on the record `fp` -- camera_ray_dir(3, 2)
+// (the matrices, inv_res, render_scale, the jitter) into out[0..2], pixel_texcoord(3, 2) into out[3..4]; launch_tile_rows (row0, row1,
+// the stripe fields) into tile_rows; and the three plain integers.
+static void frame_params_probe(const FrameParams& fp, float* out, int32_t* ints) {
+    const f3 d = camera_ray_dir(fp, 3, 2);
+    const f2 tc = pixel_texcoord(fp, 3.0f, 2.0f);
+    out[0] = d.x; out[1] = d.y; out[2] = d.z; out[3] = tc.x; out[4] = tc.y;
+    out[5] = fp.exposure; out[6] = fp.max_accum_frames; out[7] = fp.camera_pos.y;
+    ints[0] = launch_tile_rows(fp); ints[1] = fp.W; ints[2] = (int32_t)fp.frame; ints[3] = fp.camera_is_moving;
 }
 struct RadScene {   // what tests/radiance.py fills (ctypes mirror there); tests/sensor.py fills the same record
     int32_t grid_res, ref_oob, floor_material, use_sky, max_depth, sky_res;
@@ -74,7 +103,8 @@ struct RadScene {   // what tests/radiance.py fills (ctypes mirror there); tests
     const unsigned long long *l0, *l1, *l2, *l3;
     const float *mats, *sky_scat, *sky_trans;
 };
-// ... and what a sampled query reads on top: the light, the sky, the path's depth and seed, the materials.
+// ... and what a sampled query reads on top: the background, the light (direction, colour, cone, weight), the sky switch, max_depth and
+// the seed; the materials and the sky tables.
 static void scene_sampled(const RadScene& s, FrameParams& fp, SceneData& sc) {
     scene_common(s, fp, sc);
     fp.background = mk3(s.background[0], s.background[1], s.background[2]);
@@ -85,7 +115,7 @@ static void scene_sampled(const RadScene& s, FrameParams& fp, SceneData& sc) {
     fp.use_sky = s.use_sky;
     fp.max_depth = s.max_depth;
     fp.seed = s.seed;
-    fp.camera_is_moving = 1;   // (ignored by a query: were it read, the demodulation would show)
+    fp.camera_is_moving = g_query_poison ? 0 : 1;   // (ignored by a query: were it read, the demodulation would show)
     sc.mats = s.mats;
     sc.sky.scattering = s.sky_scat; sc.sky.transmittance = s.sky_trans;
     sc.sky.res = s.sky_res; sc.sky.fres = s.sky_res > 0 ? (float)(1.0 / (double)s.sky_res) : 0.0f;

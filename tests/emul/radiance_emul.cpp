@@ -24,11 +24,21 @@ long long radiance_emul_rays(long long n) { return plan_radiance_rays(n); }
 long long radiance_emul_items(void) { return VRT_RADIANCE_ITEMS; }
 int radiance_emul_staged(long long items, int knob) { return plan_radiance_staged(items, knob) ? 1 : 0; }
 
+// the mode of the frame parameters every later call hands the device functions (query_emul.h): 0 plain, 1 poisoned; returns the mode before
+int radiance_emul_poison(int on) { const int was = g_query_poison; g_query_poison = on ? 1 : 0; return was; }
+// frame_params_probe on the record a call on scene `s` would hand over in the current mode: float out[8], int32 ints[4]
+void radiance_emul_probe(const RadScene* s, float* out, int32_t* ints) {
+    FrameParams fp;
+    SceneData sc;
+    scene_sampled(*s, fp, sc);
+    frame_params_probe(fp, out, ints);
+}
+
 }  // extern "C"
 
 #ifdef RADIANCE_EMUL_MAIN
 // SmallScene without the roof; 96 rays (a fan from above, some from inside a block, some invalid) x 5 samples at depth 6 on both views,
-// in one chunk and in chunks of 2 samples.
+// in one chunk and in chunks of 2 samples; then once more with the poisoned frame parameters.
 int main() {
     SmallScene scene(false, 6);
     const int n = 96, spp = 5;
@@ -45,9 +55,13 @@ int main() {
         if (k % 16 == 9) r.dir[0] = r.dir[1] = r.dir[2] = 0.0f;
         if (k % 16 == 11) r.origin[1] = DM_INF;
     }
-    std::vector<vrt_radiance> a(n), b(n), c(n);
+    std::vector<vrt_radiance> a(n), b(n), c(n), d(n);
     if (radiance_emul_trace(&scene.s, 0, n, rays.data(), spp, 3u, 0, a.data()) || radiance_emul_trace(&scene.s, 1, n, rays.data(), spp, 3u, 0, b.data()) ||
         radiance_emul_trace(&scene.s, 0, n, rays.data(), spp, 3u, 2, c.data())) return 2;
+    radiance_emul_poison(1);   // the frame parameters no query reads, poisoned (query_emul.h): the same bytes
+    if (radiance_emul_trace(&scene.s, 1, n, rays.data(), spp, 3u, 2, d.data())) return 2;
+    radiance_emul_poison(0);
+    if (memcmp(a.data(), d.data(), n * sizeof(vrt_radiance))) { printf("the poisoned frame parameters changed a ray\n"); return 1; }
     double sum = 0.0;
     int lit = 0, hits = 0;
     for (int k = 0; k < n; k++) {
@@ -56,7 +70,7 @@ int main() {
         lit += a[k].rgb[1] > 0.0f;
         hits += a[k].t < DM_INF;
     }
-    printf("radiance_emul: %d rays x %d samples, %d lit, %d hit something, sum %.6f: views and chunkings agree\n", n, spp, lit, hits, sum);
+    printf("radiance_emul: %d rays x %d samples, %d lit, %d hit something, sum %.6f: views and chunkings agree, poisoned frame parameters change nothing\n", n, spp, lit, hits, sum);
     return lit > n / 2 && hits > n / 4 ? 0 : 1;
 }
 #endif

@@ -26,11 +26,21 @@ void sensor_emul_fold(vrt_irradiance* acc, const vrt_irradiance* values, long lo
     if (mean_over > 0) *acc = sensor_mean(*acc, mean_over);
 }
 
+// the mode of the frame parameters every later call hands the device functions (query_emul.h): 0 plain, 1 poisoned; returns the mode before
+int sensor_emul_poison(int on) { const int was = g_query_poison; g_query_poison = on ? 1 : 0; return was; }
+// frame_params_probe on the record a call on scene `s` would hand over in the current mode: float out[8], int32 ints[4]
+void sensor_emul_probe(const RadScene* s, float* out, int32_t* ints) {
+    FrameParams fp;
+    SceneData sc;
+    scene_sampled(*s, fp, sc);
+    frame_params_probe(fp, out, ints);
+}
+
 }  // extern "C"
 
 #ifdef SENSOR_EMUL_MAIN
 // SmallScene with the roof; 80 sensors (floor points, block tops, points under the roof, some invalid) x 5 samples at depth 5 on both
-// views, in one chunk and in chunks of 2 samples.
+// views, in one chunk and in chunks of 2 samples; then once more with the poisoned frame parameters.
 int main() {
     SmallScene scene(true, 5);
     const int n = 80, spp = 5;
@@ -47,9 +57,13 @@ int main() {
         if (k % 16 == 11) r.pos[2] = DM_INF;
         if (k % 16 == 15) r.reserved = 1u;
     }
-    std::vector<vrt_irradiance> a(n), b(n), c(n);
+    std::vector<vrt_irradiance> a(n), b(n), c(n), d(n);
     if (sensor_emul_gather(&scene.s, 0, n, sensors.data(), spp, 3u, 0, a.data()) || sensor_emul_gather(&scene.s, 1, n, sensors.data(), spp, 3u, 0, b.data()) ||
         sensor_emul_gather(&scene.s, 0, n, sensors.data(), spp, 3u, 2, c.data())) return 2;
+    sensor_emul_poison(1);   // the frame parameters no query reads, poisoned (query_emul.h): the same bytes
+    if (sensor_emul_gather(&scene.s, 1, n, sensors.data(), spp, 3u, 2, d.data())) return 2;
+    sensor_emul_poison(0);
+    if (memcmp(a.data(), d.data(), n * sizeof(vrt_irradiance))) { printf("the poisoned frame parameters changed a sensor\n"); return 1; }
     double sum = 0.0;
     int lit = 0, open = 0, sunny = 0;
     for (int k = 0; k < n; k++) {
@@ -59,7 +73,7 @@ int main() {
         open += a[k].sky > 0.0f;
         sunny += a[k].sun > 0.0f;
     }
-    printf("sensor_emul: %d sensors x %d samples, %d lit, %d see sky, %d see the sun, sum %.6f: views and chunkings agree\n", n, spp, lit, open, sunny, sum);
+    printf("sensor_emul: %d sensors x %d samples, %d lit, %d see sky, %d see the sun, sum %.6f: views and chunkings agree, poisoned frame parameters change nothing\n", n, spp, lit, open, sunny, sum);
     return lit > n / 2 && open > n / 4 && sunny > n / 8 ? 0 : 1;
 }
 #endif

@@ -38,8 +38,12 @@ POSES.update({
 ALL = tuple(POSES)
 SIX = P.SIX + ("street",)
 # name: (scene, max_depth, scene-parameter overrides, reference indexing, poses)
+# `sunlit_d2_relit`: sunlit_d2 under another light (direction, colour, cone), background and floor height -- what vrt_set_scene can change
+# behind a prepared scene without a new vrt_prepare (tests/test_gpu_query_states.py); the floor one voxel lower, the blocks hover above it
+RELIT = dict(light_direction=(0.4, 1.0, -0.7), light_color=(0.9, 0.7, 0.4), light_cone=0.3, background_color=(0.5, 0.2, 0.1), floor_height=-11.0 * V)
 CASES = {f"sunlit_d{d}": ("sunlit", d, {}, False, ALL) for d in (1, 2, 5, 8)}
 CASES.update({
+    "sunlit_d2_relit": ("sunlit", 2, RELIT, False, ALL),
     "s1_black_sun": ("s1", 8, dict(light_color=(0.0, 0.0, 0.0)), False, ALL),
     "dense": ("dense", 4, {}, False, ALL),
     "dense_ref": ("dense", 4, {}, True, ALL),
@@ -245,8 +249,20 @@ def lib():
         lib.radiance_emul_rays.restype = C.c_longlong
         lib.radiance_emul_items.restype = C.c_longlong
         lib.radiance_emul_staged.argtypes = [C.c_longlong, C.c_int]
+        lib.radiance_emul_poison.argtypes = [C.c_int]
+        lib.radiance_emul_probe.argtypes = [C.c_void_p] * 3
+        lib.radiance_emul_probe.restype = None
         _libs["emul"] = lib
     return _libs["emul"]
+
+
+def poisoned():
+    """tests/cast.py's poisoned() on this module's emulator."""
+    return K.poisoned((lib(), "radiance"))
+
+
+def probe(scene_record):
+    return K.probe(scene_record, (lib(), "radiance"))
 
 
 def chunks(n_rays, n_samples):

@@ -39,9 +39,11 @@ SAMPLES = (1, 3)
 CASES = {f"sunlit_d{d}": ("sunlit", d, {}, False) for d in (1, 2, 5, 8)}
 CASES.update({
     "sky": ("sunlit", 4, dict(use_physical_sky=1, use_clouds=0), False),
+    "dense": ("dense", 4, {}, False),                              # dense_ref's other mode: vrt_set_reference_indexing toggled on a live context
     "dense_ref": ("dense", 4, {}, True),
     "s1_256": ("s1_256", 4, {}, False),
     "cone": ("sunlit", 2, dict(light_cone=0.8), False),          # example5.py's wide sun
+    "sunlit_d2_relit": ("sunlit", 2, X.RELIT, False),            # tests/radiance.py: what vrt_set_scene can change behind a prepared scene
 })
 SUNLIT = tuple(c for c in CASES if CASES[c][0] == "sunlit")
 # the fixtures, in array indices (the sun-lit scene's blocks lie in x 37..87, y 54..65, z 46..78)
@@ -336,8 +338,20 @@ def lib():
         lib.sensor_emul_item_bytes.restype = C.c_longlong
         lib.sensor_emul_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int]
         lib.sensor_emul_fold.restype = None
+        lib.sensor_emul_poison.argtypes = [C.c_int]
+        lib.sensor_emul_probe.argtypes = [C.c_void_p] * 3
+        lib.sensor_emul_probe.restype = None
         _libs["emul"] = lib
     return _libs["emul"]
+
+
+def poisoned():
+    """tests/cast.py's poisoned() on this module's emulator."""
+    return K.poisoned((lib(), "sensor"))
+
+
+def probe(scene_record):
+    return K.probe(scene_record, (lib(), "sensor"))
 
 
 def blocks(n):

@@ -1,6 +1,7 @@
 """vrt_cast_rays on the host: the row function of voxel_rt2_amd/csrc/vrt_cast.h compiled with g++ (tests/emul/cast_emul.cpp runs the
 loop of k_cast_rays) against the oracle's next_hit -- every ray family on every scene of tests/cast.py, both views of the pyramid,
-any-hit rays as a wave of like rays and as part of a mixed wave, the reference's indexing off and on.  Then the validity gate on literal
+any-hit rays as a wave of like rays and as part of a mixed wave, the reference's indexing off and on; and all of it again with every
+frame parameter a cast does not read poisoned: the same bytes.  Then the validity gate on literal
 rays, the switch-over and grid-size functions, the boundary (exports, bindings, record sizes, NULL-context codes) and the box
 arithmetic of vrt_fetch_voxels against numpy slices."""
 import ctypes as C
@@ -56,6 +57,52 @@ def test_row_function_with_reference_indexing(host_scene, scene):
     print(f"reference indexing {scene}: {K.mismatches(want, plain).size} of {len(rays)} records differ from the default mode's, {int(outside.sum())} hits outside the grid")
     for staged in (0, 1):
         K.check(host_scene(scene, True).cast(rays, staged), rays, want, f"{scene} reference indexing staged={staged}")
+
+
+def check_probe_is_live(plain, poisoned, moving):
+    """frame_params_probe (tests/emul/query_emul.h) in the two modes: functions that read what no query reads tell them apart.
+    camera_ray_dir, pixel_texcoord and the three plain floats are NaN on the poisoned record; launch_tile_rows reads the stripe fields'
+    poison where the plain record gives 0 rows; W, frame and camera_is_moving hold their poison.  moving: (plain, poisoned) values of
+    camera_is_moving for this emulator's conversion."""
+    (pf, pi), (qf, qi) = plain, poisoned
+    assert np.isnan(qf).all(), qf
+    assert pi.tolist() == [0, 0, 0, moving[0]] and qi.tolist() == [0x7FFFFFFF, 0x7FFFFFFF, -1, moving[1]], (pi, qi)
+    assert (pf[5:] == 0).all()                                              # exposure, max_accum_frames, camera_pos.y of the plain record
+
+
+def test_poison_is_live(host_scene):
+    h = host_scene("sunlit")
+    plain = K.probe(h.s)
+    with K.poisoned():
+        poisoned = K.probe(h.s)
+    check_probe_is_live(plain, poisoned, (0, 1))
+    assert K.lib().cast_emul_poison(0) == 0                                 # and the mode is back to plain
+
+
+@pytest.mark.parametrize("scene,fam", K.cases())
+def test_poisoned_frame_parameters_change_no_byte(host_scene, scene, fam):
+    """Every field of FrameParams a cast is not meant to read (the camera, the pixel grid, the launch's rows and stripes, the frame
+    counter, the light, the sky switch, ...) poisoned: the same bytes as with those fields zero, for every family, both views of the
+    pyramid and both ways a wave treats any-hit rays.  (The plain mode is what test_row_function_equals_oracle pins to the oracle.)"""
+    rays, _, _ = K.family(scene, fam)
+    h = host_scene(scene)
+    for staged in (0, 1):
+        for mode in (0, 1):
+            plain = h.cast(rays, staged, mode)
+            with K.poisoned():
+                got = h.cast(rays, staged, mode)
+            assert got.tobytes() == plain.tobytes(), f"{scene}/{fam} staged={staged} mode={mode}: {K.mismatches(got, plain).size} of {len(rays)} records differ"
+
+
+@pytest.mark.parametrize("scene", ["sunlit", "dense", "s1_256"])
+def test_poisoned_frame_parameters_change_no_byte_with_reference_indexing(host_scene, scene):
+    rays = np.concatenate([K.family(scene, f)[0] for f in ("random", "planes", "axis")])
+    h = host_scene(scene, True)
+    for staged in (0, 1):
+        plain = h.cast(rays, staged)
+        with K.poisoned():
+            got = h.cast(rays, staged)
+        assert got.tobytes() == plain.tobytes(), f"{scene} staged={staged}: {K.mismatches(got, plain).size} of {len(rays)} records differ"
 
 
 def ray(o=(0.0, 0.5, 0.0), d=(0.0, -1.0, 0.0), t_max=np.inf, flags=0):

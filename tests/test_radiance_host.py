@@ -1,6 +1,7 @@
 """vrt_trace_radiance on the host: the per-item functions of voxel_rt2_amd/csrc/vrt_radiance.h compiled with g++ (tests/emul/radiance_emul.cpp
 drives them the way the library and its two kernels do) against the oracle's render body (tests/emul/radiance_orc.cpp), bit for bit, on
-every case of tests/radiance.py and both views of the pyramid.  Then what the oracle's records cover (a condition, not a measurement),
+every case of tests/radiance.py and both views of the pyramid; and again with every frame parameter a query does not read poisoned: the
+same bytes.  Then what the oracle's records cover (a condition, not a measurement),
 the chunk plan, the fold across chunks, invalid rays, and the boundary: exports, bindings, record sizes, the error codes that need no
 device."""
 import ctypes as C
@@ -52,6 +53,35 @@ def test_host_build_equals_oracle(host_scene, case):
         for n, rec in want.items():
             for staged in (0, 1):
                 X.check(h.trace(rays, n, staged=staged), rays, rec, f"{case} pose {pose} samples {n} staged={staged}")
+
+
+def test_poison_is_live(host_scene):
+    """tests/test_cast_rays_host.py's check on this emulator's conversion (scene_sampled: camera_is_moving 1 plain, 0 poisoned)."""
+    from test_cast_rays_host import check_probe_is_live
+    h = host_scene("sunlit_d5")
+    plain = X.probe(h.s)
+    with X.poisoned():
+        poisoned = X.probe(h.s)
+    check_probe_is_live(plain, poisoned, (1, 0))
+    assert X.lib().radiance_emul_poison(0) == 0
+
+
+@pytest.mark.parametrize("case", HOST_CASES)
+def test_poisoned_frame_parameters_change_no_byte(host_scene, case):
+    """Every field of FrameParams a radiance query is not meant to read (the matrices, camera_pos, inv_res, the jitter, W, H, the rows
+    and stripes, render_scale, max_accum_frames, exposure, frame; camera_is_moving flipped) poisoned: the same bytes as in the plain mode
+    -- which test_host_build_equals_oracle pins to the oracle -- for every pose and sample count, on both views, in the plan's chunks
+    and in chunks of one sample."""
+    h = host_scene(case)
+    for pose, (rays, want) in X.expected(case).items():
+        for n in want:
+            for staged in (0, 1):
+                plain = h.trace(rays, n, staged=staged)
+                with X.poisoned():
+                    for per in (0, 1):
+                        got = h.trace(rays, n, staged=staged, per=per)
+                        assert got.tobytes() == plain.tobytes(), (f"{case} pose {pose} samples {n} staged={staged} per={per}: "
+                                                                   f"{X.mismatches(got, plain).size} of {len(rays)} records differ")
 
 
 def test_black_sun_and_sky_cases_are_what_they_claim():

@@ -1,7 +1,8 @@
 """vrt_gather_irradiance on the host: the per-item functions of voxel_rt2_amd/csrc/vrt_sensor.h compiled with g++ (tests/emul/sensor_emul.cpp
 drives them the way the library and its two kernels do) against the expectation of tests/sensor.py -- the oracle's own sampling, shadow
 ray, escape test and sky value (tests/emul/sensor_orc.cpp), the radiance query's host build for the hemisphere rays that hit, the fold
-in numpy -- bit for bit, on every case and both views of the pyramid.  Then what the oracle's data cover (conditions, not
+in numpy -- bit for bit, on every case and both views of the pyramid; and again with every frame parameter a gather does not read poisoned: the
+same bytes.  Then what the oracle's data cover (conditions, not
 measurements), the plan, the fold across chunks, invalid sensors, Renderer.surface_faces, and the boundary: exports, bindings, record
 sizes, the error codes that need no device."""
 import ctypes as C
@@ -23,6 +24,34 @@ def test_host_build_equals_expectation(case):
         want = S.expected_host(case, n)
         for staged in (0, 1):
             S.check(h.gather(sensors, n, staged=staged), sensors, want, f"{case} samples {n} staged={staged}")
+
+
+def test_poison_is_live():
+    """tests/test_cast_rays_host.py's check on this emulator's conversion (scene_sampled: camera_is_moving 1 plain, 0 poisoned)."""
+    from test_cast_rays_host import check_probe_is_live
+    h = S.host_scene("sunlit_d5")
+    plain = S.probe(h.s)
+    with S.poisoned():
+        poisoned = S.probe(h.s)
+    check_probe_is_live(plain, poisoned, (1, 0))
+    assert S.lib().sensor_emul_poison(0) == 0
+
+
+@pytest.mark.parametrize("case", list(S.CASES))
+def test_poisoned_frame_parameters_change_no_byte(case):
+    """Every field of FrameParams a gather is not meant to read poisoned (tests/emul/query_emul.h): the same bytes as in the plain mode
+    -- which test_host_build_equals_expectation pins to the expectation -- for every sensor and sample count, on both views, in the
+    plan's chunks and in chunks of one sample."""
+    h = S.host_scene(case)
+    sensors = S.sensors_of(case)
+    for n in S.SAMPLES:
+        for staged in (0, 1):
+            plain = h.gather(sensors, n, staged=staged)
+            with S.poisoned():
+                for per in (0, 1):
+                    got = h.gather(sensors, n, staged=staged, per=per)
+                    assert got.tobytes() == plain.tobytes(), (f"{case} samples {n} staged={staged} per={per}: "
+                                                               f"{S.mismatches(got, plain).size} of {len(sensors)} records differ")
 
 
 def test_the_oracles_data_cover_what_they_claim():

@@ -453,8 +453,13 @@ static int ensure_cast_stage(vrt_ctx* c, size_t need) {
     return VRT_OK;
 }
 extern "C++" {   // (templates below)
-// What every query reads.  Of the frame parameters: the floor and voxel_edges; the sampled queries also the light, the sky switch,
-// max_depth and the seed.  Of the scene: the pyramid and the texels; the sampled queries also the materials and the sky tables.
+// What every query reads.  Of the frame parameters: the floor (floor_height, floor_color, floor_material) and voxel_edges; the sampled
+// queries also the background, the light (light_dir, light_color, light_cos_max, light_weight), the sky switch (use_sky), max_depth and
+// the seed.  Of the scene: the pyramid, the texels and the culling box; the sampled queries also the materials and the sky tables.
+// Nothing else: not the camera (matrices, camera_pos, taa_jitter, camera_is_moving, render_scale, max_accum_frames), not the pixel grid
+// (W, H, inv_res, row0 / row1, the stripe fields), not exposure, not the frame counter -- the host emulation hands the same functions a
+// record with exactly the listed fields set and every other field poisoned, and gets the same bytes (tests/emul/query_emul.h), and the
+// device answers the oracle's records from contexts in every frame state (tests/test_gpu_query_states.py).
 struct QueryInputs { FrameParams fp; SceneData sc; };
 static QueryInputs query_inputs(vrt_ctx* c) {
     QueryInputs q{make_frame_params(c), make_scene_data(c)};
