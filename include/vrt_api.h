@@ -235,6 +235,46 @@ int vrt_trace_radiance(vrt_ctx* ctx, int64_t n, const vrt_path_ray* rays, int n_
 typedef struct vrt_sensor { float pos[3]; uint32_t stream; float normal[3]; uint32_t reserved; } vrt_sensor;        /* 32 bytes */
 typedef struct vrt_irradiance { float sky_rgb[3]; float sky; float sun_rgb[3]; float sun; } vrt_irradiance;         /* 32 bytes */
 int vrt_gather_irradiance(vrt_ctx* ctx, int64_t n, const vrt_sensor* sensors, int n_samples, uint32_t first_frame, vrt_irradiance* out, int on_device);
+/* The light at a point in EMPTY space, for any normal a caller may later present: n caller-supplied probes -- a position in WORLD units, no
+ * normal -- on a PREPARED scene, each sampled n_samples times, and per probe the means in out[k]: nine spherical-harmonic coefficients per
+ * colour channel of the radiance arriving from all directions, with the sun kept apart as a directional term (an irradiance volume's
+ * record).  Sample s of probe k uses frame f = first_frame + s and is, in binary32 and uncontracted (include/vrt_detmath.h):
+ *   1. g = the random stream (cfg.seed, f, probe.stream, 5) -- 5: probe directions;
+ *   2. the sun: ldir = sample_cone_oriented(light_cos_theta_max, light_direction) on g's first two draws, exactly as vrt_gather_irradiance
+ *      draws it.  The shadow ray next_hit(pos, ldir, inf, shadow_ray) is ALWAYS cast: there is no normal and so no ndl test.  If it returns
+ *      >= inf: vis_s = 1 and sun_s = (T * light_weight) * light_color, T = sample_skybox_transmittance(ldir) under use_physical_sky, else 1.
+ *      Otherwise vis_s = 0 and sun_s = 0.  This is the sun's irradiance on a surface that FACES it: the caller multiplies by
+ *      max(0, dot(n, light_direction));
+ *   3. the sphere: on g's next two draws u0, u1: a = 1 - 2 * u0, b = sqrt(1 - a * a), w = normalized((b * cos(2 pi u1), b * sin(2 pi u1), a))
+ *      -- sample_cosine_weighted_hemisphere's lines without the normal and without the 1e-5 shrink: uniform on the sphere.  L_s is what
+ *      vrt_gather_irradiance's step 3 forms for ray (pos, w, probe.stream) at frame f -- a fresh path on stream (seed, f, stream, 0),
+ *      scrubbed diffuse + specular, and a ray whose FIRST segment escapes into the sky evaluated with hit_sun = 0: step 2 has counted the
+ *      sun.  sky_s = 1 for such a ray, else 0.  The origin is pos itself, with no offset;
+ *   4. the projection: with (x, y, z) = w, Lw = L_s * 12.5663706f per channel (4 pi: the uniform density is 1 / (4 pi)) and, each line
+ *      evaluated left to right,
+ *          Y0 = 0.282094792f                          Y1 = 0.488602512f * y          Y2 = 0.488602512f * z
+ *          Y3 = 0.488602512f * x                      Y4 = 1.09254843f * (x * y)     Y5 = 1.09254843f * (y * z)
+ *          Y6 = 0.315391565f * (3.0f * (z * z) - 1.0f)   Y7 = 1.09254843f * (x * z)     Y8 = 0.546274215f * (x * x - y * y)
+ *      the term of coefficient i, channel ch is Lw[ch] * Yi;
+ *   5. thirty-two running sums over s = 0 .. n_samples - 1, in order: sh[i][ch] += term, sky += sky_s, sun_rgb += sun_s, sun += vis_s, each
+ *      divided by (float)n_samples at the end.  How the work is scheduled or cut into chunks does not change a bit of them.
+ * The basis is the real spherical harmonics of bands 0 to 2 with the world's Z AS THE POLAR AXIS, in the order (l, m) = (0, 0), (1, -1),
+ * (1, 0), (1, 1), (2, -2), (2, -1), (2, 0), (2, 1), (2, 2).  The world's UP is Y, not z: Y1 is the coefficient that tells up from down.
+ * sh reconstructs radiance, L(d) ~ sum_i sh[i] * Yi(d); the irradiance on a unit normal n is
+ * pi * sh[0] * Y0 + (2 pi / 3) * sum_{i = 1..3} sh[i] * Yi(n) + (pi / 4) * sum_{i = 4..8} sh[i] * Yi(n) + sun_rgb * max(0, dot(n, light_direction)).
+ * `sky` is the open share of the sphere, `sun` the visible share of the sun's disc.
+ * INVALID probes -- a non-finite pos component -- are not walked and get an all-zero record.  (A sample whose ray (pos, w) vrt_trace_radiance
+ * would not trace is all zeros too; for a finite pos there is none.)  A probe INSIDE a solid voxel, below the floor or outside the grid's
+ * box is NOT special-cased: it gets whatever next_hit gives from there.
+ * n_samples, on_device, ordering, purity and error codes are vrt_gather_irradiance's, word for word: n_samples in 1 ..
+ * VRT_RADIANCE_MAX_SAMPLES; on_device = 0: host arrays, the call returns when `out` is filled; 1: device memory, queued on the context's
+ * stream, `out` carries the running sums between chunks; a gather queued after an edit sees the new grid; the call READS scene data and
+ * nothing else, does not force the pending accumulation and touches no statistic; it follows vrt_set_reference_indexing.
+ * VRT_E_INVALID: NULL arguments, n < 0, n_samples out of range, on_device not 0 or 1 (a probe has no `reserved` field to check);
+ * VRT_E_STATE: before vrt_prepare; n = 0 returns VRT_OK.  No counterpart in the reference. */
+typedef struct vrt_probe { float pos[3]; uint32_t stream; } vrt_probe;                                              /* 16 bytes */
+typedef struct vrt_sh_probe { float sh[9][3]; float sky; float sun_rgb[3]; float sun; } vrt_sh_probe;                /* 128 bytes */
+int vrt_gather_probes(vrt_ctx* ctx, int64_t n, const vrt_probe* probes, int n_samples, uint32_t first_frame, vrt_sh_probe* out, int on_device);
 /* The mirror image of vrt_update_voxels: the stored materials and colours of the box [lo, hi) copied out as mat int8[hx][hy][hz] and
  * rgb uint8[hx][hy][hz][3] -- what a program reads after device-side edits, which the host never saw.  on_device = 0: host arrays, the
  * call synchronises; 1: device memory, queued on the context's stream.  Box rules and error codes are vrt_update_voxels'; the pending

@@ -24,6 +24,10 @@ assert PATH_RAY.itemsize == 32 and RADIANCE.itemsize == 16
 SENSOR = np.dtype([("pos", np.float32, 3), ("stream", np.uint32), ("normal", np.float32, 3), ("reserved", np.uint32)])
 IRRADIANCE = np.dtype([("sky_rgb", np.float32, 3), ("sky", np.float32), ("sun_rgb", np.float32, 3), ("sun", np.float32)])
 assert SENSOR.itemsize == 32 and IRRADIANCE.itemsize == 32
+# vrt_probe / vrt_sh_probe (vrt_gather_probes)
+PROBE = np.dtype([("pos", np.float32, 3), ("stream", np.uint32)])
+SH_PROBE = np.dtype([("sh", np.float32, (9, 3)), ("sky", np.float32), ("sun_rgb", np.float32, 3), ("sun", np.float32)])
+assert PROBE.itemsize == 16 and SH_PROBE.itemsize == 128
 
 
 class VrtConfig(C.Structure):
@@ -88,6 +92,7 @@ def declare(lib, prefix):
     sig("cast_rays", C.c_int, P, C.c_int64, P, P, C.c_int)
     sig("trace_radiance", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)
     sig("gather_irradiance", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)
+    sig("gather_probes", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)
     sig("fetch_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
     sig("sky_accumulate_clouds", C.c_int, P, C.c_int)
     sig("sky_compute_slice", C.c_int, P, C.c_int, C.c_int)

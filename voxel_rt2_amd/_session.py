@@ -140,6 +140,17 @@ class NativeSession:
         extra = (int(samples), C.c_uint32(int(first_frame) & 0xFFFFFFFF))
         return self._query("gather_irradiance", sensors, out, n, "SENSOR", "IRRADIANCE", extra, "sensor", "results")
 
+    def gather_probes(self, probes, samples=1, first_frame=0, out=None, n=None):
+        """Spherical-harmonic light probes at points in empty space (include/vrt_api.h, vrt_gather_probes): per probe the means over
+        `samples` samples of nine coefficients per colour channel of the arriving radiance, the open share of the sphere, the sun's
+        light on a surface that faces it and the visible share of its disc; sample s draws its directions from random stream
+        (seed, first_frame + s, probe.stream, 5).  Host path: `probes` is an array of _abi.PROBE, the result an array of
+        _abi.SH_PROBE (`out` if given).  Device path: `probes` and `out` are torch tensors on the device holding the same 16- and
+        128-byte records (any dtype; `n` probes, by default as many as `probes` holds); the work is queued on the session's stream and
+        `out` is returned, not yet filled."""
+        extra = (int(samples), C.c_uint32(int(first_frame) & 0xFFFFFFFF))
+        return self._query("gather_probes", probes, out, n, "PROBE", "SH_PROBE", extra, "probe", "results")
+
     def fetch_voxels(self, lo, hi, mat=None, rgb=None, on_device=False):
         """The stored voxels of the box [lo, hi) (include/vrt_api.h, vrt_fetch_voxels).  Host path: returns (mat, rgb), arrays of shape
         hi - lo and (hi - lo, 3).  Device path (on_device=True): `mat` and `rgb` are integer device pointers to int8[hx][hy][hz] and

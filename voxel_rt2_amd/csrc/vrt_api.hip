@@ -440,7 +440,7 @@ int vrt_update_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], cons
                         c->d_l0c, c->d_l0c_base, c->d_cull));
     return read_cull_record(c);   // (the wait also ends the loan of the host arrays)
 }
-// ---- asking the scene: vrt_cast_rays, vrt_trace_radiance, vrt_gather_irradiance, vrt_fetch_voxels ------------------------------
+// ---- asking the scene: vrt_cast_rays, vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes, vrt_fetch_voxels ------------------------------
 // All READ scene data (pyramid, texels, stored voxels), on the context's stream: behind every edit queued so far, ahead of every
 // later one.  Render launches read the same data on their own streams and nothing here writes what they or their passes touch, so
 // neither main_dirty nor the pending accumulation is concerned: no enter(), no flush.
@@ -484,10 +484,14 @@ static int staged_query(vrt_ctx* c, long long n, long long block, const In* in, 
     HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host arrays)
     return VRT_OK;
 }
-// The scratch plane of vrt_trace_radiance and vrt_gather_irradiance: a work counter (256 bytes) and VRT_RADIANCE_ITEMS item values of one or
-// VRT_SENSOR_ITEMS records of the other -- the same bytes; both run on the context's stream, whose order lets them share it.
+// The scratch plane of vrt_trace_radiance, vrt_gather_irradiance and vrt_gather_probes: a work counter (256 bytes) and VRT_RADIANCE_ITEMS
+// item values of the first, VRT_SENSOR_ITEMS records of the second or VRT_PROBE_ITEMS items of the third -- the same bytes; all run on the
+// context's stream, whose order lets them share it.
 static_assert((size_t)VRT_SENSOR_ITEMS * sizeof(vrt_irradiance) <= (size_t)VRT_RADIANCE_ITEMS * sizeof(f3), "the sensor plane must fit the radiance plane");
 static_assert(sizeof(vrt_irradiance) == VRT_SENSOR_ITEM_BYTES && sizeof(vrt_sensor) == 32, "record sizes of include/vrt_api.h");
+static_assert((size_t)VRT_PROBE_ITEMS * sizeof(ProbeItem) <= (size_t)VRT_RADIANCE_ITEMS * sizeof(f3), "the probe plane must fit the radiance plane");
+static_assert(sizeof(ProbeItem) == VRT_PROBE_ITEM_BYTES && sizeof(vrt_probe) == 16 && sizeof(vrt_sh_probe) == 128, "record sizes of include/vrt_api.h");
+static_assert(VRT_PROBE_ITEMS >= (1 << 18), "one sample of a full block (plan_query_rays) must fit the probe plane");
 // A sampled query (vrt_query.h) reads what vrt_cast_rays reads plus the materials and the sky tables, and is ordered the same way.
 // Blocks of records (plan_query_rays), a block's samples in chunks of whole samples (plan_query_chunk): one item launch and one fold
 // launch a chunk, all on the context's stream, where stream order lets every chunk reuse the scratch plane.  name, noun: the entry
@@ -501,8 +505,9 @@ static int sampled_query(vrt_ctx* c, const char* name, const char* noun, int64_t
     if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
     if (!c->prepared) return fail(VRT_E_STATE, std::string(name) + " asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
     if (n == 0) return VRT_OK;
-    if (!on_device)
-        for (int64_t k = 0; k < n; k++) if (in[k].reserved != 0u) return fail(VRT_E_INVALID, std::string("a ") + noun + "'s `reserved` field must be 0");
+    if constexpr (Q::has_reserved)
+        if (!on_device)
+            for (int64_t k = 0; k < n; k++) if (in[k].reserved != 0u) return fail(VRT_E_INVALID, std::string("a ") + noun + "'s `reserved` field must be 0");
     HIP_TRY(hipSetDevice(c->device));
     const QueryInputs q = query_inputs(c);
     if (!c->d_radiance_plane) HIP_TRY(dmalloc(c, &c->d_radiance_plane, 256 + (size_t)VRT_RADIANCE_ITEMS * sizeof(f3)));   // [0]: the work counter
@@ -544,6 +549,9 @@ int vrt_trace_radiance(vrt_ctx* c, int64_t n, const vrt_path_ray* rays, int n_sa
 }
 int vrt_gather_irradiance(vrt_ctx* c, int64_t n, const vrt_sensor* sensors, int n_samples, uint32_t first_frame, vrt_irradiance* out, int on_device) {
     return sampled_query<SensorQuery>(c, "vrt_gather_irradiance", "sensor", n, sensors, n_samples, first_frame, out, on_device);
+}
+int vrt_gather_probes(vrt_ctx* c, int64_t n, const vrt_probe* probes, int n_samples, uint32_t first_frame, vrt_sh_probe* out, int on_device) {
+    return sampled_query<ProbeQuery>(c, "vrt_gather_probes", "probe", n, probes, n_samples, first_frame, out, on_device);
 }
 int vrt_fetch_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], void* mat, void* rgb, int on_device) {
     if (!c || !lo || !hi || !mat || !rgb) return fail(VRT_E_INVALID, "null argument");

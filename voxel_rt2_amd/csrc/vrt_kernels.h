@@ -55,8 +55,8 @@ hipError_t launch_cast_rays(hipStream_t st, int grid_res, bool staged, bool oob,
                             const vrt_ray* rays, vrt_ray_hit* hits);
 // vrt_fetch_voxels: the stored voxels of `box` (valid, not empty) gathered into box_mat / box_rgb (device memory)
 hipError_t launch_fetch_voxels(hipStream_t st, int grid_res, const EditBox& box, const int8_t* mat, const uint8_t* rgb, int8_t* box_mat, uint8_t* box_rgb);
-// A sampled query Q (vrt_query.h: RadianceQuery, SensorQuery): samples [s0, s0 + count) of n records (device memory) worked into
-// plane[n * count] by the query's item kernel (k_trace_radiance, k_gather_irradiance) and folded into out[n] (k_fold_query).
+// A sampled query Q (vrt_query.h: RadianceQuery, SensorQuery, ProbeQuery): samples [s0, s0 + count) of n records (device memory) worked into
+// plane[n * count] by the query's item kernel (k_trace_radiance, k_gather_irradiance, k_gather_probes) and folded into out[n] (k_fold_query).
 // n * count <= Q::max_items; staged / oob as for launch_cast_rays; head: one word of device memory, the launch's work counter.
 template <class Q>
 hipError_t launch_sampled_query(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n, int s0,

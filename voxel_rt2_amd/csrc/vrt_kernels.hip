@@ -17,7 +17,8 @@
 //   k_cast_rays / k_fetch_voxels                          vrt_cast_rays: caller-supplied rays through next_hit; vrt_fetch_voxels
 //   k_trace_radiance                                      vrt_trace_radiance: caller-supplied rays through the path state machine
 //   k_gather_irradiance                                   vrt_gather_irradiance: a sun sample and a hemisphere path per (sensor, sample)
-//   k_fold_query<Q>                                       the ordered sums of either (vrt_query.h)
+//   k_gather_probes                                       vrt_gather_probes: a sun sample and a sphere path per (probe, sample)
+//   k_fold_query<Q>                                       the ordered sums of any of the three (vrt_query.h)
 //
 // k_render is a persistent-thread kernel: the grid is sized to the device's residency, each wave
 // keeps 64 path records in registers and pulls pixels (8x8 tiles, tile-major order) from a global
@@ -997,7 +998,7 @@ __global__ __launch_bounds__(64) void k_shade_probe(FrameParams fp, SceneData sc
                     lane_tables ? lane_tables + (size_t)i * VRT_SHADE_LANE_TABLE : nullptr);
 }
 
-// ---- the scene queries: what k_cast_rays, k_trace_radiance and k_gather_irradiance share -------------------------------------------
+// ---- the scene queries: what k_cast_rays, k_trace_radiance, k_gather_irradiance and k_gather_probes share -------------------------------------------
 // A query kernel's view of the pyramid.  STAGED: the coarse levels in LDS exactly as k_render keeps them for LdsPyramid (at 256^3 the
 // 32 KiB l1 level), the fine level through L2, and with MATS the material table beside them as k_render has it; else the launch is small
 // and everything is read from global memory.  OOB (STAGED only; GlobalPyramid always can): the instantiation carries the reference's
@@ -1224,6 +1225,78 @@ __global__ __launch_bounds__(256, 2) void k_gather_irradiance(FrameParams fp, Sc
     }
 }
 
+// ---- vrt_gather_probes: caller-supplied points in empty space; sun sample and sphere path per (probe, sample) (vrt_probe_sh.h) ----------
+// The work item is (probe, sample): item i of a launch is probe i % n_probes, sample s0 + i / n_probes of the block.  Schedule, refill and
+// the shadow rays walked TOGETHER are k_gather_irradiance's (VRT_SENSOR_SUN_BATCH is shared: the same trade); here every item has a shadow
+// ray.  The plane holds the compact ProbeItem; the basis and the products are k_fold_query's (probe_fold).  Every item has one writer per
+// field of its plane record: w and the pad at the refill, the sun terms behind the shadow ray, sky_s at the path's first segment, L_s at
+// its end; no atomics on results.  An invalid probe's items, and an item whose ray probe_begin refuses, are all zeros and are not walked.
+template <int G, bool STAGED, bool OOB>
+__global__ __launch_bounds__(256, 2) void k_gather_probes(FrameParams fp, SceneData sc, unsigned n_probes, unsigned total, unsigned s0, uint32_t first_frame,
+                                                          const vrt_probe* __restrict__ probes, ProbeItem* __restrict__ plane, unsigned* head) {
+    __shared__ unsigned long long s_l1[STAGED ? QueryLds<G>::N1 : 1];
+    __shared__ unsigned long long s_l2[STAGED ? QueryLds<G>::N2 : 1];
+    __shared__ float s_mats[STAGED ? 128 * 14 : 1];
+    __shared__ float s_cull[8];
+    QueryView<G, STAGED, OOB> P;
+    SceneData scl = sc;
+    stage_query<G, STAGED, OOB, true>(sc, s_l1, s_l2, s_mats, s_cull, P, scl);
+    const int lane = threadIdx.x & 63;
+    Path<false> p;
+    p.depth = -1;
+    unsigned item = 0u;                        // the lane's item while p.depth >= 0 (< total: the plane's bound)
+    bool sun_pending = false;                  // the item's shadow ray is still to be walked (then p.depth == 0)
+    f3 ldir = mk3(0.0f);                       // ... along ldir
+    TraceStats ts;                             // a sink: a query counts nothing
+    stats_zero(ts);
+    WaveItems items;
+    for (;;) {
+        const bool need = p.depth < 0;
+        const unsigned long long mask = __ballot(need);
+        unsigned my = 0u;
+        if (mask != 0ULL && !items.exhausted && items.take(mask, need, lane, head, total, my)) {
+            const unsigned probe = my % n_probes, sample = s0 + my / n_probes;
+            const vrt_probe q = probes[probe];
+            f3 w;
+            if (probe_valid(q) && probe_begin(fp, p, q, first_frame + sample, ldir, w)) {
+                item = my;
+                sun_pending = true;
+                ProbeItem* rec = plane + my;
+                rec->w[0] = w.x; rec->w[1] = w.y; rec->w[2] = w.z; rec->pad = 0.0f;
+            } else {
+                plane[my] = ProbeQuery::zero();
+            }
+        }
+        const unsigned long long live = __ballot(p.depth >= 0);
+        if (live == 0ULL) {
+            if (items.exhausted) break;
+            continue;
+        }
+        const unsigned long long waiting = __ballot(sun_pending);   // a subset of `live`
+        if (waiting != 0ULL && (__popcll(waiting) >= VRT_SENSOR_SUN_BATCH || waiting == live || items.exhausted)) {
+            if (sun_pending) {
+                float vis;
+                const f3 sun = probe_sun(fp, scl, P, p.pos, ldir, ts, vis);
+                ProbeItem* rec = plane + item;
+                rec->sun[0] = sun.x; rec->sun[1] = sun.y; rec->sun[2] = sun.z; rec->vis = vis;
+                sun_pending = false;
+            }
+        }
+        if (p.depth >= 0 && !sun_pending) {
+            const bool first = p.depth == 0;
+            float sky = 0.0f;
+            const bool done = probe_segment(fp, scl, P, p, ts, sky);
+            ProbeItem* rec = plane + item;
+            if (first) rec->sky = sky;
+            if (done) {
+                const f3 L = probe_value(p);
+                rec->L[0] = L.x; rec->L[1] = L.y; rec->L[2] = L.z;
+                p.depth = -1;
+            }
+        }
+    }
+}
+
 // ---- the sampled queries' fold (query_fold, vrt_query.h) -------------------------------------------------------------------------
 // One lane per record of the block: the chunk's `count` plane values of the record added in sample order to the sum the chunks before
 // left in out[k] (first: to zero), and with the last chunk the division by the call's number of samples.
@@ -1443,6 +1516,10 @@ template <> struct ItemKernel<SensorQuery> {
     typedef void (*fn_t)(FrameParams, SceneData, unsigned, unsigned, unsigned, uint32_t, const vrt_sensor*, vrt_irradiance*, unsigned*);
     template <int G, bool STAGED, bool OOB> static fn_t get() { return k_gather_irradiance<G, STAGED, OOB>; }
 };
+template <> struct ItemKernel<ProbeQuery> {
+    typedef void (*fn_t)(FrameParams, SceneData, unsigned, unsigned, unsigned, uint32_t, const vrt_probe*, ProbeItem*, unsigned*);
+    template <int G, bool STAGED, bool OOB> static fn_t get() { return k_gather_probes<G, STAGED, OOB>; }
+};
 
 hipError_t launch_cast_rays(hipStream_t st, int grid_res, bool staged, bool oob, int n_cu, const FrameParams& fp, const SceneData& sc, long long n,
                             const vrt_ray* rays, vrt_ray_hit* hits) {
@@ -1489,5 +1566,7 @@ template hipError_t launch_sampled_query<RadianceQuery>(hipStream_t, int, bool, 
                                                         const vrt_path_ray*, f3*, vrt_radiance*, unsigned*);
 template hipError_t launch_sampled_query<SensorQuery>(hipStream_t, int, bool, bool, int, const FrameParams&, const SceneData&, long long, int, int, int, uint32_t,
                                                       const vrt_sensor*, vrt_irradiance*, vrt_irradiance*, unsigned*);
+template hipError_t launch_sampled_query<ProbeQuery>(hipStream_t, int, bool, bool, int, const FrameParams&, const SceneData&, long long, int, int, int, uint32_t,
+                                                     const vrt_probe*, ProbeItem*, vrt_sh_probe*, unsigned*);
 
 }  // namespace vrt

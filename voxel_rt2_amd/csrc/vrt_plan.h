@@ -214,7 +214,7 @@ static inline int plan_cast_blocks(long long n, int n_cu, int blocks_per_cu) {
     return (int)(want < fit ? want : fit);
 }
 
-// ---- the sampled queries: vrt_trace_radiance, vrt_gather_irradiance (vrt_query.h) ----------------------------------------------------
+// ---- the sampled queries: vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes (vrt_query.h) ----------------------------------------------------
 // The work item is (record, sample) -- (ray, sample) or (sensor, sample); a finished item leaves its value in a scratch plane -- 12 bytes
 // an item for a radiance, a 32-byte vrt_irradiance record of four terms for a sensor -- which k_fold_query sums per record in sample
 // order.  The plane is bounded: a call is cut into blocks of records, and a block's samples into chunks of WHOLE samples (every record of
@@ -227,6 +227,10 @@ static inline int plan_cast_blocks(long long n, int n_cu, int blocks_per_cu) {
 #define VRT_RADIANCE_ITEMS (1 << 20)
 #define VRT_SENSOR_ITEM_BYTES 32
 #define VRT_SENSOR_ITEMS ((VRT_RADIANCE_ITEMS * 12) / VRT_SENSOR_ITEM_BYTES)
+// The probes' item is the 48-byte ProbeItem (vrt_probe_sh.h) -- the fold forms the 27 products, the plane does not hold them -- so the same
+// bytes hold 12 MiB / 48 = 2^18 items: exactly one sample of a full block (plan_query_rays), which is the least plan_query_chunk needs.
+#define VRT_PROBE_ITEM_BYTES 48
+#define VRT_PROBE_ITEMS ((VRT_RADIANCE_ITEMS * 12) / VRT_PROBE_ITEM_BYTES)
 // Records of a block (also what a host-path call stages at a time: 48 bytes of device memory a ray, 64 a sensor): one sample of a block
 // fits either plane.
 static inline long long plan_query_rays(long long n) { return n < (1 << 18) ? n : (1 << 18); }
@@ -243,3 +247,5 @@ static inline int plan_radiance_chunk(long long n_rays, int n_samples) { return 
 static inline bool plan_radiance_staged(long long items, int knob) { return plan_cast_staged(items, knob); }
 static inline long long plan_sensor_rays(long long n) { return plan_query_rays(n); }
 static inline int plan_sensor_chunk(long long n_sensors, int n_samples) { return plan_query_chunk(VRT_SENSOR_ITEMS, n_sensors, n_samples); }
+static inline long long plan_probe_rays(long long n) { return plan_query_rays(n); }
+static inline int plan_probe_chunk(long long n_probes, int n_samples) { return plan_query_chunk(VRT_PROBE_ITEMS, n_probes, n_samples); }

@@ -142,6 +142,59 @@ class VoxelStore:
         centre = ((cell.astype(np.float64) + 0.5 - g / 2) * dx + normal.astype(np.float64) * (0.5 * dx)).astype(np.float32)
         return cell, face, centre, normal
 
+    def probe_lattice(self, lo=None, hi=None, step=4):
+        """Where light probes go: the EMPTY cells (material <= 0) of the box [lo, hi) of array indices -- by default the whole grid --
+        taken every `step` cells from lo on each axis.  Host numpy on voxel_material, no device (after device-side edits run
+        sync_voxels_from_device first).  Returns (centre float32[m, 3] the cells' centres in world units, cell int32[m, 3] array
+        indices), x slowest."""
+        g = self.voxel_grid_res
+        step = int(step)
+        if step < 1:
+            raise ValueError("step must be at least 1")
+        lo = np.clip(np.array((0, 0, 0) if lo is None else lo, np.int64), 0, g)
+        hi = np.clip(np.array((g, g, g) if hi is None else hi, np.int64), 0, g)
+        hi = np.maximum(hi, lo)
+        axes = [np.arange(int(a), int(b), step) for a, b in zip(lo, hi)]
+        cell = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, 3)
+        cell = cell[self.voxel_material[cell[:, 0], cell[:, 1], cell[:, 2]] <= 0].astype(np.int32).reshape(-1, 3)
+        centre = ((cell.astype(np.float64) + 0.5 - g / 2) * (2.0 / g)).astype(np.float32)
+        return centre, cell
+
+    # -- reading vrt_sh_probe records (include/vrt_api.h, vrt_gather_probes) ------------------------------------------------------
+    SH_BAND_WEIGHTS = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)   # A_l per coefficient: the clamped-cosine lobe's
+
+    @staticmethod
+    def sh_basis(dirs):
+        """Y0 .. Y8 of include/vrt_api.h at unit vectors: float64[n, 9], with the constants at float64's precision (the library's are
+        their binary32 roundings).  The polar axis is z; the world's up is y."""
+        d = np.asarray(dirs, np.float64).reshape(-1, 3)
+        x, y, z = d[:, 0], d[:, 1], d[:, 2]
+        k0, k1, k2, k3, k4 = 0.5 * np.sqrt(1.0 / np.pi), np.sqrt(0.75 / np.pi), 0.5 * np.sqrt(15.0 / np.pi), 0.25 * np.sqrt(5.0 / np.pi), 0.25 * np.sqrt(15.0 / np.pi)
+        return np.stack([np.full(len(d), k0), k1 * y, k1 * z, k1 * x, k2 * (x * y), k2 * (y * z), k3 * (3.0 * (z * z) - 1.0), k2 * (x * z), k4 * (x * x - y * y)],
+                        axis=1)
+
+    @staticmethod
+    def sh_radiance(records, dirs):
+        """The plain expansion L(d) = sum_i sh[i] * Yi(d) of _abi.SH_PROBE records at unit directions: float64[n, 3].  records and dirs
+        pair up one to one (one of either serves all of the other)."""
+        sh = np.asarray(np.atleast_1d(records)["sh"], np.float64).reshape(-1, 9, 3)
+        return (VoxelStore.sh_basis(dirs)[:, :, None] * sh).sum(axis=1)
+
+    @staticmethod
+    def sh_irradiance(records, normals, light_direction=None):
+        """The irradiance on unit normals from _abi.SH_PROBE records, float64[n, 3]:
+        E = pi c0 Y0 + (2 pi / 3) sum_{i=1..3} ci Yi(n) + (pi / 4) sum_{i=4..8} ci Yi(n) + sun_rgb * max(0, n . light_direction);
+        the sun's term is left out when no light direction is passed.  records and normals pair up one to one (one of either serves
+        all of the other)."""
+        rec = np.atleast_1d(records)
+        sh = np.asarray(rec["sh"], np.float64).reshape(-1, 9, 3)
+        n = np.asarray(normals, np.float64).reshape(-1, 3)
+        e = ((VoxelStore.sh_basis(n) * VoxelStore.SH_BAND_WEIGHTS)[:, :, None] * sh).sum(axis=1)
+        if light_direction is not None:
+            ndl = np.maximum(n @ np.asarray(light_direction, np.float64).reshape(3), 0.0)
+            e = e + np.asarray(rec["sun_rgb"], np.float64).reshape(-1, 3) * ndl[:, None]
+        return e
+
 
 class Renderer(VoxelStore):
     def __init__(self, dx, image_res, up, voxel_edges, exposure=3, *, max_depth=None, use_restir=None, seed=None, sky_res=None,
@@ -392,6 +445,37 @@ class Renderer(VoxelStore):
         face k of the list."""
         cell, face, centre, normal = self.surface_faces(lo, hi)
         return cell, face, self.gather_irradiance(centre, normal, samples=samples)
+
+    # -- the light at points in empty space (include/vrt_api.h, vrt_gather_probes; no counterpart in the reference) -------------------
+    def gather_probes(self, points, samples=64, first_frame=0, streams=None):
+        """Spherical-harmonic light probes at caller-supplied points in world units, on the scene as prepare_data() / update_voxels()
+        left it: a structured array of _abi.SH_PROBE, one record a point -- sh (nine coefficients per colour channel of the arriving
+        radiance, sun excluded; polar axis z, the world's up is y), sky (the open share of the sphere), sun_rgb (the sun's irradiance on
+        a surface that faces it), sun (the visible share of its disc), each the mean of `samples` samples.  sh_irradiance / sh_radiance
+        read the records.  points: (n, 3) or (3,), a numpy array or a torch tensor on the device (that goes through the device path).
+        Sample s of point k draws from random streams (seed, first_frame + s, streams[k], 5) and (.., 0); streams defaults to arange(n)."""
+        if not getattr(self, "_prepared", False):
+            raise NativeError("gather_probes asks a prepared scene: call prepare_data() first")
+        self._push()
+        if hasattr(points, "data_ptr"):
+            import torch
+            dev = points.device
+            o = points.to(torch.float32).reshape(-1, 3)
+            n = o.shape[0]
+            rec = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+            rec[:, 0:3] = o
+            st = torch.arange(n, device=dev, dtype=torch.int64) if streams is None else torch.as_tensor(streams, device=dev).to(torch.int64).reshape(-1)
+            rec.view(torch.int32)[:, 3] = (((st & 0xFFFFFFFF) + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32)   # the stream's 32 bits
+            out = torch.empty((n, 32), dtype=torch.float32, device=dev)
+            torch.cuda.synchronize(dev)               # the tensors are written on torch's stream, read on the session's
+            self._s.gather_probes(rec, samples, first_frame, out)
+            self._s.sync()
+            return out.cpu().numpy().view(_abi.SH_PROBE).reshape(-1)
+        o = np.asarray(points, np.float32).reshape(-1, 3)
+        probes = np.zeros(len(o), _abi.PROBE)
+        probes["pos"] = o
+        probes["stream"] = np.arange(len(probes), dtype=np.uint32) if streams is None else np.asarray(streams).astype(np.uint32)
+        return self._s.gather_probes(probes, samples, first_frame)
 
     @staticmethod
     def panorama_dirs(width, height):
