@@ -298,7 +298,7 @@ int vrt_sky_table_io(vrt_ctx* ctx, int which /* VRT_BUF_SKY_SCATTERING | VRT_BUF
  * scene parameters that stood when ITS call was made -- vrt_set_camera (a new jitter), vrt_set_scene and vrt_end_frame between
  * calls neither force nor disturb it.  The pending accumulation is queued on the context's stream, before anything else the call
  * does, by every call that can observe or change what a pass per launch would have produced: vrt_sync, every vrt_fetch_*
- * (blocking, device, async) and vrt_fetch_buffer, vrt_get_stats / vrt_reset_stats, vrt_reset, vrt_set_stream,
+ * (blocking, device, async), vrt_fetch_buffer and vrt_denoise, vrt_get_stats / vrt_reset_stats, vrt_reset, vrt_set_stream,
  * vrt_set_hdr_targets, vrt_set_history_exchange / vrt_history_rows_io, vrt_set_row_stripes, vrt_upload_*, vrt_update_voxels, vrt_prepare,
  * vrt_set_instrumented, vrt_set_reference_indexing, vrt_destroy, a vrt_accumulate call whose launch is of another kind (moving
  * camera, render scale below 1, another pipeline depth) or fails.  Results are those of a pass per launch, bit for bit; a caller
@@ -378,6 +378,43 @@ int vrt_set_row_stripes(vrt_ctx* ctx, int stripe_rows, int n_parts, int part);
 int vrt_set_history_exchange(vrt_ctx* ctx, int on);
 int vrt_history_rows_io(vrt_ctx* ctx, int row0, int row1, void* device_ptr, int to_library);
 int vrt_fetch_buffer(vrt_ctx* ctx, int which, void* out);
+/* The accumulated frame through a spatial filter, for the frames that have few samples behind them (after a vrt_reset, behind a moving
+ * camera): an edge-avoiding a-trous filter -- B3-spline 5x5, the stride doubling per iteration -- over albedo-demodulated diffuse and over
+ * specular, each by itself; taps gated by material id, normal and distance to the centre pixel's plane and weighted by their sample
+ * count; the result fades back to the unfiltered accumulation as the pixel's own sample count grows.  out: f32[H][W][3], laid out like
+ * vrt_fetch_hdr's.  on_device = 0: host memory, the call returns when `out` is filled; 1: device memory, the work is only queued on the
+ * context's stream.  params = NULL means {5, 0.25f, 0.5f, 64.0f}: defaults of TASTE, not validated on images by anybody.
+ * The call forces the pending accumulation (vrt_accumulate) as every fetch does, and then READS and nothing else: no history, g-buffer,
+ * HDR buffer, counter or statistic is written, and frames rendered after it are bit for bit the frames rendered without it.  Launches
+ * queued after the call do not overtake it: it has read what they write before they write it.
+ * Inputs, with idx = v * W + u, each exactly what vrt_fetch_buffer / vrt_fetch_hdr would return at the moment of the call:
+ *   Hd, Hs  VRT_BUF_HISTORY_DIFFUSE, VRT_BUF_HISTORY_SPECULAR (f32x4; w: the samples behind the pixel)
+ *   P       VRT_BUF_GBUF_POSITION           N   oct_decode(VRT_BUF_GBUF_NORMAL) (math_utils.py:209-215 on the two binary16 halves)
+ *   M       VRT_BUF_GBUF_MAT: id = M & 255, A = unpack_albedo(M) = (float)((M >> 8, 16, 24) & 255) / 255.0f per channel
+ *   HDR     vrt_fetch_hdr
+ *   moving  camera_is_moving of the camera the most recent vrt_accumulate rendered with (recorded at that call: vrt_set_camera may
+ *           have run since)
+ * Arithmetic: binary32, uncontracted (include/vrt_detmath.h), every expression left to right as written, 3-vector operations per
+ * channel; dot3(a, b) = a.x * b.x + a.y * b.y + a.z * b.z and lum(c) = dot3((0.2125f, 0.7154f, 0.0721f), c).
+ *   1. Split and demodulate.  A pixel is a SURFACE pixel unless P.x * P.x + P.y * P.y + P.z * P.z < 1e-7f.  For a surface pixel
+ *      A' = dm_max(A, 0.00392156886f), Id = moving ? Hd.xyz : Hd.xyz / A' (the moving camera's diffuse history is demodulated already),
+ *      Is = Hs.xyz, and the counts cd = Hd.w, cs = Hs.w, which stay as they are through all iterations.
+ *   2. Iterations i = 0 .. iterations - 1 at stride s = 1 << i, on the two signals X = d, s independently.  For a surface pixel p =
+ *      (u, v): sum = 0, wsum = 0; taps dy = -2 .. 2 (outer loop), dx = -2 .. 2 (inner loop), q = (u + dx * s, v + dy * s).  A tap is
+ *      skipped when q lies outside the frame, when q is no surface pixel, and unless ALL of id_q == id_p, dot3(N_p, N_q) >= 0.9f and
+ *      dm_abs(dot3(N_p, P_q - P_p)) <= tol hold, tol = plane_tolerance * cfg.dx formed once; the centre is a tap like any other.
+ *      w = (K[|dx|] * K[|dy|]) * c_q with K = {0.375f, 0.25f, 0.0625f} and c_q the tap's count for this signal.  For i >= 1 and
+ *      sigma_l > 0: lp = lum(X_p), lq = lum(X_q), t = dm_abs(lq - lp) / (sigma_l * ((lp + lq) * 0.5f) + 0.001f), w = w / (1.0f + t * t).
+ *      sum = sum + w * X_q, wsum = wsum + w.  X'_p = wsum > 0 ? sum / wsum : X_p.  An iteration reads the previous iteration's values only.
+ *   3. Fade and recompose.  F: the last iteration's value, U: step 1's.  Per signal a = full_at > 0 ? dm_min(c_p / full_at, 1.0f) : 0.0f
+ *      and R = F + (U - F) * a; out = (R_d * (moving ? A : A')) + R_s.  A pixel that is no surface pixel gets HDR[idx], bit for bit.
+ * VRT_E_INVALID: NULL ctx or out, on_device not 0 or 1, iterations outside 1 .. 6, a plane_tolerance, sigma_l or full_at that is not
+ * finite or is negative.  VRT_E_STATE: no vrt_accumulate since vrt_create or since the last vrt_reset; a row tile (row_begin / row_end),
+ * row stripes or the history exchange (the filter reaches 62 rows, a tile holds a 2-row halo); the most recent vrt_accumulate rendered
+ * at a render scale other than 1.  ReSTIR, the moving camera, instrumented launches, reserved CUs and vrt_set_reference_indexing are all
+ * allowed.  No counterpart in the reference, which shows its frames as they accumulate. */
+typedef struct vrt_denoise_params { int32_t iterations; float plane_tolerance; float sigma_l; float full_at; } vrt_denoise_params;   /* 16 bytes */
+int vrt_denoise(vrt_ctx* ctx, const vrt_denoise_params* params, void* out, int on_device);
 /* waits for everything queued so far, the accumulation of every rendered launch included (see vrt_accumulate) */
 int vrt_sync(vrt_ctx* ctx);
 int vrt_get_stats(vrt_ctx* ctx, vrt_stats* out);

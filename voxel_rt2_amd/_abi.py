@@ -57,6 +57,14 @@ class VrtCamera(C.Structure):
     ]
 
 
+class VrtDenoiseParams(C.Structure):
+    """vrt_denoise_params; the defaults are include/vrt_api.h's (a matter of taste, not validated on images)."""
+    _fields_ = [("iterations", C.c_int32), ("plane_tolerance", C.c_float), ("sigma_l", C.c_float), ("full_at", C.c_float)]
+
+    def __init__(self, iterations=5, plane_tolerance=0.25, sigma_l=0.5, full_at=64.0):
+        super().__init__(int(iterations), float(plane_tolerance), float(sigma_l), float(full_at))
+
+
 class VrtStats(C.Structure):
     _fields_ = [
         ("path_samples", C.c_uint64), ("rays", C.c_uint64), ("dda_iters", C.c_uint64),
@@ -116,6 +124,7 @@ def declare(lib, prefix):
     sig("set_hdr_targets", C.c_int, P, C.POINTER(C.c_void_p), C.c_int)
     sig("hdr_targets_written", C.c_int, P, C.POINTER(C.c_uint64))
     sig("fetch_buffer", C.c_int, P, C.c_int, P)
+    sig("denoise", C.c_int, P, C.POINTER(VrtDenoiseParams), P, C.c_int)
     sig("sync", C.c_int, P)
     sig("get_stats", C.c_int, P, C.POINTER(VrtStats))
     sig("last_error", C.c_char_p)

@@ -332,6 +332,24 @@ class NativeSession:
         self._call("fetch_buffer", int(which), out.ctypes.data_as(C.c_void_p))
         return out
 
+    def denoise(self, params=None, out=None):
+        """The accumulated frame through the g-buffer-guided a-trous filter (include/vrt_api.h, vrt_denoise): HDR float32[H][W][3].
+        `params` is an _abi.VrtDenoiseParams (None: the library's defaults).  Host path: the result is an array (`out` if given).  Device
+        path: `out` is a torch tensor on the device of H * W * 12 bytes; the work is queued on the session's stream and `out` is returned,
+        not yet filled."""
+        p = None if params is None else C.byref(params)
+        if out is not None and hasattr(out, "data_ptr"):
+            if out.numel() * out.element_size() < self.H * self.W * 12 or not out.is_contiguous():
+                raise ValueError(f"device path: `out` is a contiguous device tensor of {self.H * self.W * 12} bytes")
+            self._call("denoise", p, C.c_void_p(out.data_ptr()), 1)
+            return out
+        if out is None:
+            out = np.empty((self.H, self.W, 3), dtype=np.float32)
+        if out.dtype != np.float32 or out.shape != (self.H, self.W, 3) or not out.flags.c_contiguous:
+            raise ValueError("`out` must be a contiguous float32 array [H, W, 3]")
+        self._call("denoise", p, out.ctypes.data_as(C.c_void_p), 0)
+        return out
+
     def stats(self):
         s = _abi.VrtStats()
         self._call("get_stats", C.byref(s))

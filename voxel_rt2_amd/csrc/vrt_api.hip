@@ -648,6 +648,7 @@ int vrt_reset(vrt_ctx* c) {
         HIP_TRY(hipMemsetAsync(c->d_hx_hist_d, 0, n * sizeof(f4), c->stream));
         HIP_TRY(hipMemsetAsync(c->d_hx_hist_s, 0, n * sizeof(f4), c->stream));
     }
+    c->acc_valid = false;   // nothing accumulated: vrt_denoise has no frame to work on
     return VRT_OK;
 }
 int vrt_end_frame(vrt_ctx* c) {
@@ -844,6 +845,55 @@ int vrt_fetch_buffer(vrt_ctx* c, int which, void* out) {
         return VRT_OK;
     }
     return fail(VRT_E_INVALID, "unknown buffer id");
+}
+// ---- vrt_denoise: a spatial filter behind the frame (vrt_denoise.h) -------------------------------------------------------------------
+// Reads what vrt_fetch_buffer / vrt_fetch_hdr would return now and writes its own scratch and `out`: no history, g-buffer, HDR buffer,
+// counter or statistic.  Ordered as those fetches are: the pending accumulation first (enter), the work on the context's stream.  The
+// histories, the HDR buffers and the rotating normal planes are next written by passes on that stream or by launches that wait for such
+// a pass, so stream order keeps them behind the call.  NOT so the position and material planes of the last launch's copy: the launch
+// that takes the copy again waits for the pass that last read it (PlaneSet::ev_t), which was queued BEFORE this call.  Only the prepare
+// kernel reads them, so the call records that event again behind it: the copy's next writer then waits for the prepare kernel too.
+// main_dirty / main_touched stay as a fetch leaves them.
+static bool denoise_value_ok(float x) { return x >= 0.0f && x <= 3.402823466e+38f; }   // finite and not negative (a NaN fails both)
+int vrt_denoise(vrt_ctx* c, const vrt_denoise_params* params, void* out, int on_device) {
+    if (!c || !out) return fail(VRT_E_INVALID, "null argument");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    const vrt_denoise_params p = params ? *params : vrt_denoise_params{5, 0.25f, 0.5f, 64.0f};
+    if (p.iterations < 1 || p.iterations > VRT_DENOISE_MAX_ITERATIONS) return fail(VRT_E_INVALID, "iterations must be 1 .. 6");
+    if (!denoise_value_ok(p.plane_tolerance) || !denoise_value_ok(p.sigma_l) || !denoise_value_ok(p.full_at))
+        return fail(VRT_E_INVALID, "plane_tolerance, sigma_l and full_at must be finite and not negative");
+    if (!c->acc_valid) return fail(VRT_E_STATE, "vrt_denoise works on an accumulated frame: call vrt_accumulate first (also after vrt_reset)");
+    if (is_row_tile(c) || c->stripe_rows || c->hx_on)
+        return fail(VRT_E_STATE, "vrt_denoise needs the whole frame: not on a row tile, with row stripes or with the history exchange (the filter reaches 62 rows)");
+    if (c->acc_scale != 1.0f) return fail(VRT_E_STATE, "vrt_denoise needs a frame rendered at render scale 1");
+    if (enter(c) != VRT_OK) return VRT_E_DEVICE;
+    const size_t n = c->npix;   // (the whole frame: buf0 = 0, buf1 = height)
+    if (!c->dn.guide) {
+        bool ok = dmalloc(c, &c->dn.guide, n * sizeof(DenoiseGuide)) == hipSuccess && dmalloc(c, &c->dn.mat, n * sizeof(uint32_t)) == hipSuccess;
+        for (int k = 0; k < 3 && ok; k++) ok = dmalloc(c, &c->dn.d[k], n * sizeof(f4)) == hipSuccess && dmalloc(c, &c->dn.s[k], n * sizeof(f4)) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            (void)dfree(c, &c->dn.guide); (void)dfree(c, &c->dn.mat);
+            for (int k = 0; k < 3; k++) { (void)dfree(c, &c->dn.d[k]); (void)dfree(c, &c->dn.s[k]); }
+            return fail(VRT_E_DEVICE, "no device memory for the denoiser's planes");
+        }
+    }
+    if (!on_device && !c->d_dn_out) HIP_TRY(dmalloc(c, &c->d_dn_out, n * sizeof(f3)));
+    f3* const d_out = on_device ? (f3*)out : c->d_dn_out;
+    const PlaneSet& last = c->sets[c->last_set];
+    const DenoiseSource src{last.gb_pos, c->last_gb_normal, last.gb_mat, c->d_hist_d[c->hist_in], c->d_hist_s[c->hist_in], c->d_cbuf[c->cidx]};
+    const DenoiseSettings set{p.iterations, p.plane_tolerance * c->cfg.dx, p.sigma_l, p.full_at, c->acc_moving};
+    HIP_TRY(launch_denoise_prepare(c->stream, c->cfg.width, c->cfg.height, set.moving, src, c->dn, d_out));
+    if (last.ev_t) {   // (the overlapped pipeline's copies: a launch on the context's own stream is behind the call as it is)
+        PlaneSet& l = c->sets[c->last_set];
+        HIP_TRY(hipEventRecord(l.ev_t, c->stream));
+        l.ev_t_valid = true; l.ev_t_of = c->last_set;
+    }
+    HIP_TRY(launch_denoise_filter(c->stream, c->cfg.width, c->cfg.height, set, c->dn, d_out));
+    if (on_device) return VRT_OK;
+    HIP_TRY(hipMemcpyAsync(out, d_out, n * sizeof(f3), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(sync_guarded(c, c->stream));   // (also ends the loan of the host array)
+    return VRT_OK;
 }
 int vrt_get_stats(vrt_ctx* c, vrt_stats* out) {
     if (!c || !out) return fail(VRT_E_INVALID, "null argument");

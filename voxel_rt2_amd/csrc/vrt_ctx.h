@@ -212,6 +212,13 @@ struct vrt_ctx {
     hipStream_t fetch_stream = nullptr;
     hipEvent_t ev_fetch[VRT_FETCH_SLOTS] = {}, ev_fetch_src = nullptr, ev_cbuf_read[2] = {};
     bool fetch_valid[VRT_FETCH_SLOTS] = {}, cbuf_read_pending[2] = {};
+    // vrt_denoise: what the most recent vrt_accumulate rendered with (the camera may have been set again since), and the pass's scratch
+    // planes (allocated on first use)
+    bool acc_valid = false;           // a vrt_accumulate has rendered since vrt_create / the last vrt_reset
+    int acc_moving = 0;               // its camera_is_moving
+    float acc_scale = 1.0f;           // its render_scale
+    DenoiseScratch dn{};
+    f3* d_dn_out = nullptr;           // the host path's result on its way out
     // History exchange (vrt_set_history_exchange): a row tile's whole-frame copy of the previous frame's temporal state, which the
     // moving-camera pass resamples from.  Own rows are stored by every vrt_accumulate call, the other rows imported by the caller
     // (vrt_history_rows_io); hx_row_epoch[r] = hx_epoch when row r was imported after the most recent call.

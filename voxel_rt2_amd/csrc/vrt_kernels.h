@@ -15,6 +15,7 @@
 #include "vrt_edit.h"
 #include "vrt_cast.h"
 #include "vrt_query.h"
+#include "vrt_denoise.h"
 
 #define VRT_RENDER_THREADS 256
 #ifndef VRT_RENDER_MIN_WAVES
@@ -81,6 +82,14 @@ hipError_t launch_temporal(hipStream_t st, const FrameParams& fp, const Temporal
 hipError_t launch_temporal_group(hipStream_t st, const TemporalGroup& tg, int r0, int r1);
 hipError_t launch_tonemap(hipStream_t st, const FrameParams& fp, const f3* hdr, f4* ldr, int r0, int r1);
 hipError_t launch_tonemap8(hipStream_t st, const FrameParams& fp, const f3* hdr, uint32_t* ldr8 /* rgba, 8 bits each */, int r0, int r1);
+// vrt_denoise (vrt_denoise.h), whole frames of W x H.  The planes the pass reads of the context -- the last launch's g-buffer, the
+// histories, the HDR frame -- and its own scratch: d[0] / s[0] hold step 1's signals, the iterations alternate between the other two.
+struct DenoiseSource { const f3* gb_pos; const uint32_t* gb_normal; const uint32_t* gb_mat; const f4* hist_d; const f4* hist_s; const f3* hdr; };
+struct DenoiseScratch { DenoiseGuide* guide; uint32_t* mat; f4* d[3]; f4* s[3]; };
+// step 1 into the scratch; out (f32[H][W][3], device memory) receives the pixels that are no surface pixels.  Reads `src` and nothing else does
+hipError_t launch_denoise_prepare(hipStream_t st, int W, int H, int moving, const DenoiseSource& src, const DenoiseScratch& scr, f3* out);
+// set.iterations a-trous kernels at strides 1, 2, 4, ..; the last one fades, recomposes and writes the surface pixels of `out`
+hipError_t launch_denoise_filter(hipStream_t st, int W, int H, const DenoiseSettings& set, const DenoiseScratch& scr, f3* out);
 hipError_t launch_diag_read(hipStream_t st, unsigned long long* out, int reset);  // -DVRT_DIAG_REGIONS builds only
 hipError_t launch_detmath_probe(hipStream_t st, int op, int n, const float* a, const float* b, float* out);
 // n rays (origin, direction: 6 floats each, voxel units) through walk PROBE_WALK_* against `cull`'s box (vrt_probe.h)

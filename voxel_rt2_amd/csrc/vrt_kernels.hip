@@ -936,6 +936,44 @@ __global__ __launch_bounds__(256) void k_tonemap8(FrameParams fp, const f3* hdr,
                                          (dm_f2u32(dm_saturate(c.z) * 255.0f + 0.5f) << 16) | (dm_f2u32(dm_saturate(c.w) * 255.0f + 0.5f) << 24);
     }
 }
+// ---- vrt_denoise (vrt_denoise.h) ---------------------------------------------------------------------------------------------------
+// Step 1 of every pixel, and the ONLY kernel of the pass that reads planes the render launches and their passes write: the guide record,
+// the material word and the two signals go to the pass's own scratch, and a pixel that is no surface pixel gets its HDR value here.
+__global__ __launch_bounds__(256) void k_denoise_prepare(int W, int H, int moving, DenoiseSource src, DenoiseGuide* __restrict__ guide, uint32_t* __restrict__ mat,
+                                                         f4* __restrict__ d, f4* __restrict__ s, f3* __restrict__ out) {
+    const int u = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int v = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (u >= W || v >= H) return;
+    const int idx = v * W + u;
+    const uint32_t M = src.gb_mat[idx];
+    DenoiseGuide g;
+    f4 xd, xs;
+    const bool surface = denoise_prepare(src.gb_pos[idx], src.gb_normal[idx], M, src.hist_d[idx], src.hist_s[idx], moving, g, xd, xs);
+    guide[idx] = g;
+    mat[idx] = M;
+    d[idx] = xd;
+    s[idx] = xs;
+    if (!surface) out[idx] = src.hdr[idx];
+}
+// One iteration at stride S: a 32 x 8 pixel tile per workgroup, a pixel a lane, the 25 taps gathered from global memory (DESIGN.md
+// section 4 says why not through LDS).  The last iteration (out != nullptr) goes on to step 3 and writes the surface pixels of the
+// result instead of the signals; u_d / u_s: step 1's values.
+template <int S>
+__global__ __launch_bounds__(256) void k_denoise_atrous(DenoiseIn in, DenoiseSettings st, int use_lum, f4* __restrict__ d_out, f4* __restrict__ s_out,
+                                                        const f4* __restrict__ u_d, const f4* __restrict__ u_s, f3* __restrict__ out) {
+    const int u = blockIdx.x * 32 + (threadIdx.x & 31);
+    const int v = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (u >= in.W || v >= in.H) return;
+    const int idx = v * in.W + u;
+    f4 xd, xs;
+    const bool surface = denoise_iteration(in, u, v, S, use_lum != 0, st.sigma_l, st.tol, xd, xs);
+    if (out) {
+        if (surface) out[idx] = denoise_finish(xd, xs, u_d[idx], u_s[idx], in.mat[idx], st.moving, st.full_at);
+    } else {
+        d_out[idx] = xd;
+        s_out[idx] = xs;
+    }
+}
 #if defined(VRT_DIAG_REGIONS)
 __global__ void k_diag_read(unsigned long long* out, int reset) {
     int i = threadIdx.x;
@@ -1463,6 +1501,36 @@ hipError_t launch_tonemap8(hipStream_t st, const FrameParams& fp, const f3* hdr,
     dim3 g((fp.W + 63) / 64, (r1 - r0 + 3) / 4), b(256);
     hipLaunchKernelGGL(k_tonemap8, g, b, 0, st, fp, hdr, ldr8, r0, r1);
     VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_denoise_prepare(hipStream_t st, int W, int H, int moving, const DenoiseSource& src, const DenoiseScratch& scr, f3* out) {
+    dim3 g((W + 63) / 64, (H + 3) / 4), b(256);
+    hipLaunchKernelGGL(k_denoise_prepare, g, b, 0, st, W, H, moving, src, scr.guide, scr.mat, scr.d[0], scr.s[0], out);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_denoise_filter(hipStream_t st, int W, int H, const DenoiseSettings& set, const DenoiseScratch& scr, f3* out) {
+    dim3 g((W + 31) / 32, (H + 7) / 8), b(256);
+    int from = 0;   // the copy iteration i reads: step 1's, then the two others in turn
+    for (int i = 0; i < set.iterations; i++) {
+        const int to = from == 1 ? 2 : 1;
+        const DenoiseIn in{scr.guide, scr.mat, scr.d[from], scr.s[from], W, H};
+        const int use_lum = i >= 1 && set.sigma_l > 0.0f;
+        f3* const last = i == set.iterations - 1 ? out : nullptr;
+#define VRT_DENOISE_AT(S_) hipLaunchKernelGGL(k_denoise_atrous<S_>, g, b, 0, st, in, set, use_lum, scr.d[to], scr.s[to], scr.d[0], scr.s[0], last)
+        switch (i) {
+            case 0: VRT_DENOISE_AT(1); break;
+            case 1: VRT_DENOISE_AT(2); break;
+            case 2: VRT_DENOISE_AT(4); break;
+            case 3: VRT_DENOISE_AT(8); break;
+            case 4: VRT_DENOISE_AT(16); break;
+            case 5: VRT_DENOISE_AT(32); break;
+            default: return hipErrorInvalidValue;
+        }
+#undef VRT_DENOISE_AT
+        VRT_LAUNCH_CHECK();
+        from = to;
+    }
     return hipSuccess;
 }
 hipError_t launch_detmath_probe(hipStream_t st, int op, int n, const float* a, const float* b, float* out) {

@@ -581,6 +581,11 @@ extern "C" int vrt_accumulate(vrt_ctx* c, int n_samples) {
 #endif
     if (rc != VRT_OK) abort_pipeline(c);
     else c->hdr_targets_committed = c->hdr_targets_written;
+    if (rc == VRT_OK && n_samples > 0) {   // what vrt_denoise must know of this call: vrt_set_camera may run before it does
+        c->acc_valid = true;
+        c->acc_moving = c->cam.camera_is_moving;
+        c->acc_scale = c->cam.render_scale;
+    }
     if (rc == VRT_OK && hx) {
         if (store_history_rows(c) != VRT_OK) { abort_pipeline(c); return VRT_E_DEVICE; }
         c->hx_epoch++;

@@ -552,6 +552,17 @@ class Renderer(VoxelStore):
     def fetch_hdr(self):
         return self._s.fetch_hdr()
 
+    def fetch_denoised(self, iterations=5, plane_tolerance=0.25, sigma_l=0.5, full_at=64.0, ldr=False):
+        """The accumulated frame through the g-buffer-guided spatial filter (include/vrt_api.h, vrt_denoise), for frames with few samples
+        behind them -- after an edit and a reset, behind a moving camera: linear HDR float32 [H, W, 3] (row 0 = bottom), the counterpart
+        of fetch_hdr().  `iterations` a-trous passes (1 .. 6, strides 1, 2, 4, ..); taps further than `plane_tolerance` voxels from the
+        centre pixel's plane are left out; `sigma_l` is the luminance stopping's relative width (0: off); a pixel with `full_at` samples
+        or more gets its unfiltered value (0: always the filtered one).  The defaults are a matter of taste: nobody has validated them
+        on images.  With ldr=True the result is tone_map(hdr) -- the numpy presentation curve WITHOUT fetch_image's vignette -- as
+        float rgba [H, W, 4] for save_image.  Nothing is written back: the accumulation goes on as if the call had not been made."""
+        hdr = self._s.denoise(_abi.VrtDenoiseParams(iterations, plane_tolerance, sigma_l, full_at))
+        return self.tone_map(hdr) if ldr else hdr
+
     def set_reference_indexing(self, on=True):
         """Occupancy queries outside the grid read the bit the reference's index arithmetic addresses (raytracer.py:17-38)
         instead of "empty" (the default).  Also `VRT_REFERENCE_INDEXING=1` in the environment."""
