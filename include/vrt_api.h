@@ -100,7 +100,12 @@ typedef struct vrt_stats {
                                      bits 5..7: a launch takes 1 / this many of the workgroup slots (1, 2 or 4);
                                      bits 8..23: times the host released that wait (error paths, synchronisation watchdog);
                                      bits 24..31: times the pipeline was drained to change its depth (a caller that changes the
-                                     sample count of its calls: the depth follows the launch size) */
+                                     sample count of its calls: the depth follows the launch size) -- EXCEPT in the two-stream shape of
+                                     half-slot launches named above (1 in bits 2..4 with 2 in bits 5..7), where
+                                     bit 24: the context's stream is a render lane -- launches take turns over the library's two streams
+                                     and the context's (the caller's after vrt_set_stream), which is made to wait for the other lanes
+                                     when an entry point looks at it or queues work on it, not with every launch; and
+                                     bits 25..31: the times the pipeline was drained (at most 127) */
 } vrt_stats;
 
 /* buffers readable through vrt_fetch_buffer (tests and the multi-GPU gather) */

@@ -583,6 +583,7 @@ int vrt_sky_accumulate_clouds(vrt_ctx* c, int max_samples) {
     float cm;
     sun_of(c, sd, sc_, cm);
     c->main_dirty = true;
+    if (settle_ctx_stream(c) != VRT_OK) return VRT_E_DEVICE;   // (behind the render launches that read the tables)
     HIP_TRY(launch_sky_clouds(c->stream, make_sky(c), sd, sc_, cm, max_samples, c->cloud_pass, 0, c->cfg.sky_res));
     c->cloud_pass++;
     return VRT_OK;
@@ -600,6 +601,7 @@ int vrt_sky_accumulate_clouds_slice(vrt_ctx* c, int max_samples, int slice_idx, 
     if (c->cfg.sky_res % max_slices != 0) return fail(VRT_E_INVALID, "sky_res is not a multiple of max_slices: trailing table columns would belong to no slice");
     const int w = c->cfg.sky_res / max_slices;
     c->main_dirty = true;
+    if (settle_ctx_stream(c) != VRT_OK) return VRT_E_DEVICE;   // (behind the render launches that read the tables)
     HIP_TRY(launch_sky_clouds(c->stream, make_sky(c), sd, sc_, cm, max_samples, c->cloud_pass, w * slice_idx, w * (slice_idx + 1)));
     c->cloud_pass++;
     return VRT_OK;
@@ -618,6 +620,7 @@ int vrt_sky_table_io(vrt_ctx* c, int which, int u0, int u1, void* device_ptr, in
     char* lib = (char*)table + (size_t)u0 * col;
     const size_t bytes = (size_t)(u1 - u0) * col;
     c->main_dirty = true;
+    if (settle_ctx_stream(c) != VRT_OK) return VRT_E_DEVICE;
     if (to_library) HIP_TRY(hipMemcpyAsync(lib, device_ptr, bytes, hipMemcpyDeviceToDevice, c->stream));
     else HIP_TRY(hipMemcpyAsync(device_ptr, lib, bytes, hipMemcpyDeviceToDevice, c->stream));
     return VRT_OK;
@@ -632,6 +635,7 @@ int vrt_sky_compute_slice(vrt_ctx* c, int slice_idx, int max_slices) {
     int w = c->cfg.sky_res / max_slices;  // atmos.py:162: floor division -- trailing columns (3840 / 32 has none) belong to no slice, as in the reference
     if (w == 0) return VRT_OK;   // fewer columns than slices: every slice is empty
     c->main_dirty = true;
+    if (settle_ctx_stream(c) != VRT_OK) return VRT_E_DEVICE;
     HIP_TRY(launch_sky_slice(c->stream, make_sky(c), sd, sc_, cm, w * slice_idx, w * (slice_idx + 1)));
     return VRT_OK;
 }
@@ -707,6 +711,11 @@ int vrt_set_stream(vrt_ctx* c, void* hip_stream) {
     HIP_TRY(sync_guarded(c, c->stream));
     resolve_events(c);
     for (PlaneSet& p : c->sets) p.ev_t_valid = false;  // everything recorded on the old stream has completed
+    if (c->ctx_lane) {   // the stream is a render lane: the other lanes are drained too (as where the pipeline changes its shape), the lane goes on on the new stream
+        drain_all(c);
+        forget_passes(c);
+        c->lanes[c->n_streams].last_seq = 0u;
+    }
     c->main_dirty = true;
     c->main_touched = true;
     if (c->owns_stream && c->stream) hipStreamDestroy(c->stream);
@@ -895,6 +904,8 @@ int vrt_denoise(vrt_ctx* c, const vrt_denoise_params* params, void* out, int on_
     HIP_TRY(sync_guarded(c, c->stream));   // (also ends the loan of the host array)
     return VRT_OK;
 }
+// Launches of half the slots on two streams of the pipeline's own: the shape whose flags give bit 24 to the context's lane (include/vrt_api.h).
+static bool lean_shape(const vrt_ctx* c) { return c->overlap_ready && c->n_streams == 2 && c->grid_div == 2; }
 int vrt_get_stats(vrt_ctx* c, vrt_stats* out) {
     if (!c || !out) return fail(VRT_E_INVALID, "null argument");
     if (enter(c) != VRT_OK) return VRT_E_DEVICE;
@@ -910,7 +921,8 @@ int vrt_get_stats(vrt_ctx* c, vrt_stats* out) {
         c->stats.render_launches = c->passes_n[0]; c->stats.temporal_launches = c->passes_n[1]; c->stats.gris_launches = c->passes_n[2];
     }
     c->stats.pipeline_flags = (c->overlap_ready ? 1u : 0u) | (c->drain_signal ? 2u : 0u) | (((uint32_t)c->gate_releases & 0xFFFFu) << 8) |
-                              ((c->mode_switches < 255u ? c->mode_switches : 255u) << 24) |
+                              (lean_shape(c) ? ((c->mode_switches < 127u ? c->mode_switches : 127u) << 25) | (c->ctx_lane ? 1u << 24 : 0u)
+                                             : (c->mode_switches < 255u ? c->mode_switches : 255u) << 24) |
                               (c->overlap_ready ? ((uint32_t)(c->n_streams == 3 ? 2 : c->n_streams >> 1) << 2) | ((uint32_t)c->grid_div << 5) : 0u);
     *out = c->stats;
     return VRT_OK;
@@ -933,6 +945,7 @@ int vrt_sky_probe(vrt_ctx* c, int op, int n, const float* in, int in_stride, flo
     if (c->cfg.sky_res <= 0) return fail(VRT_E_STATE, "context was created without sky tables (sky_res = 0)");
     HIP_TRY(hipSetDevice(c->device));
     c->main_dirty = true;
+    if (settle_ctx_stream(c) != VRT_OK) return VRT_E_DEVICE;
     if (trans_lut) HIP_TRY(hipMemcpyAsync(c->d_trans_lut, trans_lut, 256 * 128 * 3 * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
     float *d_in = nullptr, *d_out = nullptr;
     HIP_TRY(hipMalloc((void**)&d_in, (size_t)n * in_stride * sizeof(float)));

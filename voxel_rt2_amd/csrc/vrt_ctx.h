@@ -80,6 +80,7 @@ struct Lane {
     uint32_t* pool_scratch = nullptr;
     PrimaryRecord* prim_cache = nullptr;   // camera-ray records of fused launches (allocated on first use)
     unsigned last_seq = 0;                 // launch_seq + 1 of the last launch queued on this stream (0: none)
+    int last_set = -1;                     // the copy that launch wrote: its ev_r is the lane's latest (-1: none since the streams were drained)
 };
 
 struct vrt_ctx {
@@ -160,8 +161,16 @@ struct vrt_ctx {
     int n_streams = 2;   // the shape in use (plan_pipeline_shape, ensure_overlap)
     int grid_div = 1;
     bool pass_on_render = false;
+    // The context's stream as render lane number n_streams (PipelineShape::ctx_lane): lanes[n_streams] holds that lane's scratch and
+    // camera-ray table and NO stream -- lane_stream() answers with the context's, whichever the caller has set (vrt_set_stream).
+    bool ctx_lane = false;
+    bool pass_on_last = false;   // grouped passes run on the lane of the group's last launch (PipelineShape::pass_on_last)
+    // Passes and launches on the OTHER lanes that the context's stream has not been made to wait for: with ctx_lane a wait queued
+    // with every pass would hold the stream's own next launch behind it, so the waits are queued where somebody is about to look at
+    // the stream or to queue work on it (settle_ctx_stream: flush_deferred's callers, the sky entry points, abort_pipeline).
+    bool ctx_unsettled = false;
     int defer_k = 1;
-    int n_sets = 3;      // copies in use: n_streams + defer_k
+    int n_sets = 3;      // copies in use: lanes + defer_k
     bool overlap_ready = false, overlap_failed = false;
     unsigned mode_switches = 0;   // times the pipeline was drained to change its depth (ensure_overlap)
     // A render launch queued behind another on another render stream would be dispatched at once and sit in the
@@ -185,10 +194,10 @@ struct vrt_ctx {
     // planes stay occupied until then: n_sets = n_streams + K copies.
     struct Deferred { TemporalSlice slice; int set; int lane; bool timed; };
     std::vector<Deferred> deferred;
-    // Where a grouped pass runs: on the context's stream, or (pass_on_render, an A/B shape that no configuration selects) on the
-    // render stream of the group's last launch -- behind it in stream order, behind the others by their events, passes following
-    // one another by last_pass_ev; the context's stream then only WAITS for the pass's event (queue_group), so that whatever is
-    // queued on it next, by the library or the caller, comes behind it.
+    // Where a grouped pass runs: on the context's stream, or (pass_on_last: the shape with ctx_lane, and the A/B shapes of
+    // VRT_PASS_STREAM=1) on the lane of the group's last launch -- behind it in stream order, behind the others by their events,
+    // passes following one another by last_pass_ev; the context's stream then only WAITS for the pass's event (queue_group; with
+    // ctx_lane: settle_ctx_stream), so that whatever is queued on it next, by the library or the caller, comes behind it.
     hipEvent_t last_pass_ev = nullptr;   // event of the most recent pass queued on a render stream (nullptr: none since the streams were drained)
     int last_pass_lane = -1;
     bool main_touched = true;   // the context's stream was given work since the last pass on a render stream: that pass's successor waits for it
@@ -262,6 +271,18 @@ static hipError_t dfree(vrt_ctx* c, T** p) {
 // Queues the accumulation of every render launch whose pass was deferred (vrt_pipeline.hip).  Everything that observes or changes
 // what a pass per launch would have produced calls it first.
 static int flush_deferred(vrt_ctx* c, bool split_tail = true);
+// Lanes of the pipeline in use, and the stream of each.
+static int n_lanes(const vrt_ctx* c) { return c->n_streams + (c->ctx_lane ? 1 : 0); }
+static hipStream_t lane_stream(const vrt_ctx* c, int lane) { return c->ctx_lane && lane == c->n_streams ? c->stream : c->lanes[lane].stream; }
+// The context's stream comes behind every pass and every render launch queued on another lane so far (vrt_ctx::ctx_unsettled).
+static int settle_ctx_stream(vrt_ctx* c) {
+    if (!c->ctx_unsettled) return VRT_OK;
+    if (c->last_pass_ev && lane_stream(c, c->last_pass_lane) != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, c->last_pass_ev, 0));
+    for (int s = 0; s < c->n_streams; s++)   // (launches whose pass is not queued yet: what a caller's upload must not overtake)
+        if (c->lanes[s].last_set >= 0) HIP_TRY(hipStreamWaitEvent(c->stream, c->sets[c->lanes[s].last_set].ev_r, 0));
+    c->ctx_unsettled = false;
+    return VRT_OK;
+}
 // The preamble of the entry points that look at, or queue work behind, what vrt_accumulate has produced.
 static int enter(vrt_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));

@@ -67,7 +67,7 @@ static bool gate_self_test(vrt_ctx* c) {
 
 // Streams, copies and events for a pipeline `want` launches deep (what a shallower one already has is kept; every buffer is
 // looked at by itself, so an attempt that failed half way is completed, not allocated over).
-static bool grow_pipeline(vrt_ctx* c, int want, int want_sets) {
+static bool grow_pipeline(vrt_ctx* c, int want, int want_sets, bool ctx_lane) {
     const size_t n = c->npix;
     bool ok = true;
     for (int s = 1; s < want_sets && ok; s++) {
@@ -82,6 +82,10 @@ static bool grow_pipeline(vrt_ctx* c, int want, int want_sets) {
         ok = (s == 0 || l.pool_scratch || dmalloc(c, &l.pool_scratch, c->pool_scratch_bytes) == hipSuccess) &&
              hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking) == hipSuccess;
     }
+    if (ctx_lane && ok) {   // the lane of the context's stream: a scratch of its own, no stream (lane_stream)
+        Lane& l = c->lanes[want];
+        ok = l.pool_scratch || dmalloc(c, &l.pool_scratch, c->pool_scratch_bytes) == hipSuccess;
+    }
     for (int s = 0; s < want_sets && ok; s++) {
         PlaneSet& p = c->sets[s];
         ok = (p.ev_r || hipEventCreateWithFlags(&p.ev_r, hipEventDisableTiming) == hipSuccess) &&
@@ -95,7 +99,9 @@ static bool grow_pipeline(vrt_ctx* c, int want, int want_sets) {
 static bool can_defer(const vrt_ctx* c) { return c->hdr_targets.empty() && !c->hx_on && c->stripe_rows == 0; }
 static void forget_passes(vrt_ctx* c) {   // every stream was drained: no pass is left to wait for
     for (PlaneSet& p : c->sets) p.ev_t_valid = false;
+    for (Lane& l : c->lanes) l.last_set = -1;
     c->last_pass_ev = nullptr;
+    c->ctx_unsettled = false;
 }
 // The pipeline for a launch of `items` work items; false (and never tried again) if its streams and copies cannot be had.  The
 // depth follows the launch: a context whose caller changes habit (one sample per call, then four) is drained once and goes on in
@@ -104,10 +110,15 @@ static bool ensure_overlap(vrt_ctx* c, size_t items, bool heavy) {
     if (c->overlap_failed) return false;
     PipelineShape sh = plan_pipeline_shape(items, heavy, c->knobs.hw_queues, can_defer(c), c->knobs);
     const bool first = !c->overlap_ready;
-    if (!first && sh.n_streams == c->n_streams && sh.grid_div == c->grid_div && sh.pass_on_render == c->pass_on_render) return true;
-    bool ok = grow_pipeline(c, sh.n_streams, sh.n_streams + sh.defer_k);
+    if (!first && sh.n_streams == c->n_streams && sh.grid_div == c->grid_div && sh.pass_on_render == c->pass_on_render && sh.ctx_lane == c->ctx_lane &&
+        sh.pass_on_last == c->pass_on_last) return true;
+    bool ok = grow_pipeline(c, sh.n_streams, sh.n_streams + (sh.ctx_lane ? 1 : 0) + sh.defer_k, sh.ctx_lane);
     if (first) {
-        if (!ok && sh.defer_k > 1) { sh.defer_k = 1; ok = grow_pipeline(c, sh.n_streams, sh.n_streams + 1); }   // no memory for the deferred launches' copies: a pass per launch
+        if (!ok && sh.defer_k > 1) {   // no memory for the deferred launches' copies: a pass per launch, on the context's stream (which is no lane then)
+            sh.defer_k = 1; sh.ctx_lane = false; sh.pass_on_last = sh.pass_on_render;
+            c->knobs.ctx_lane = 0;   // (nor is the lane asked for again: the shape of later launches compares equal to this one)
+            ok = grow_pipeline(c, sh.n_streams, sh.n_streams + 1, false);
+        }
     } else {
         if (!ok) return true;   // no memory for the other mode: this one goes on
         if (sync_guarded(c, c->stream) != hipSuccess) return true;   // (with the deferred passes of the mode that ends)
@@ -120,7 +131,10 @@ static bool ensure_overlap(vrt_ctx* c, size_t items, bool heavy) {
     c->n_streams = sh.n_streams;
     c->grid_div = sh.grid_div;
     c->pass_on_render = sh.pass_on_render;
-    c->n_sets = sh.n_streams + sh.defer_k;
+    c->ctx_lane = sh.ctx_lane;
+    c->pass_on_last = sh.pass_on_last;
+    if (sh.ctx_lane) c->lanes[sh.n_streams].last_seq = 0u;   // (nothing of this mode is on the context's stream yet)
+    c->n_sets = sh.n_streams + (sh.ctx_lane ? 1 : 0) + sh.defer_k;
     c->defer_k = sh.defer_k;
     if (!first) return true;
     ok = ok && hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming) == hipSuccess;
@@ -188,13 +202,16 @@ static int queue_group(vrt_ctx* c, size_t first, size_t n) {
     tg.inv_res = mk2((float)(1.0 / (double)tg.W), (float)(1.0 / (double)tg.H));   // (make_frame_params)
     tg.n_slices = (int)n;
     bool timed = false;
-    // the stream the pass runs on: the context's, or the render stream of the group's last launch (vrt_ctx::pass_on_render)
-    const int lane = c->pass_on_render ? c->deferred[first + n - 1].lane : -1;
-    hipStream_t ps = lane >= 0 ? c->lanes[lane].stream : c->stream;
+    // the stream the pass runs on: the context's, or the lane of the group's last launch (vrt_ctx::pass_on_last) -- which with
+    // ctx_lane is the context's stream one time in n_lanes
+    const int lane = c->pass_on_last ? c->deferred[first + n - 1].lane : -1;
+    hipStream_t ps = lane >= 0 ? lane_stream(c, lane) : c->stream;
     if (lane >= 0) {
         if (c->main_touched) {   // histories reset, frames fetched, passes of launches that were not deferred: all on the context's stream
-            HIP_TRY(hipEventRecord(c->ev_main, c->stream));
-            HIP_TRY(hipStreamWaitEvent(ps, c->ev_main, 0));
+            if (ps != c->stream) {
+                HIP_TRY(hipEventRecord(c->ev_main, c->stream));
+                HIP_TRY(hipStreamWaitEvent(ps, c->ev_main, 0));
+            }
             c->main_touched = false;
         }
         // the history ping-pong makes passes sequential
@@ -220,8 +237,10 @@ static int queue_group(vrt_ctx* c, size_t first, size_t n) {
     HIP_TRY(hipEventRecord(done, ps));
     if (lane >= 0) {
         // Whatever comes next on the context's stream -- a fetch, a synchronisation, a pass of a launch that is not deferred,
-        // the caller's own work -- comes behind the pass: a wait, no kernel.
-        HIP_TRY(hipStreamWaitEvent(c->stream, done, 0));
+        // the caller's own work -- comes behind the pass: a wait, no kernel.  Where the stream is a lane that wait is queued when
+        // such work is about to come (settle_ctx_stream), not in front of the lane's next launch.
+        if (c->ctx_lane) c->ctx_unsettled = c->ctx_unsettled || ps != c->stream;
+        else HIP_TRY(hipStreamWaitEvent(c->stream, done, 0));
         c->last_pass_ev = done;
         c->last_pass_lane = lane;
     } else {
@@ -239,7 +258,7 @@ static int flush_deferred(vrt_ctx* c, bool split_tail) {
     const size_t m = c->deferred.size();
     // (split_tail: every caller but the K-th launch of a group is about to look at, or to queue work on, the context's stream)
     if (split_tail) c->main_touched = true;
-    if (m == 0) return VRT_OK;
+    if (m == 0) return split_tail ? settle_ctx_stream(c) : VRT_OK;
     int rc = VRT_OK;
     bool split = false;
     if (split_tail && m > 1) {
@@ -253,6 +272,8 @@ static int flush_deferred(vrt_ctx* c, bool split_tail) {
         rc = queue_group(c, 0, m);
     }
     c->deferred.clear();   // (after a failure too: the caller's abort_pipeline drains what was queued)
+    if (split_tail) c->main_touched = true;   // (what the caller queues now comes BEHIND the passes above: the next pass on a lane waits for it)
+    if (rc == VRT_OK && split_tail) rc = settle_ctx_stream(c);
     return rc;
 }
 // What this launch's own pass would have been given, as it stands now (camera, scene, planes).
@@ -300,7 +321,7 @@ static int size_render_grid(vrt_ctx* c) {
     HIP_TRY(sync_guarded(c, c->stream));
     for (int s = 0; s < VRT_MAX_STREAMS; s++) {   // lane 0's, then that of every other stream the pipeline has, whatever the depth in use
         Lane& l = c->lanes[s];
-        if (s > 0 && !(c->overlap_ready && l.stream)) continue;
+        if (s > 0 && !(c->overlap_ready && (l.stream || l.pool_scratch))) continue;   // (the lane of the context's stream has a scratch and no stream)
         HIP_TRY(dfree(c, &l.pool_scratch));
         HIP_TRY(dmalloc(c, &l.pool_scratch, c->pool_scratch_bytes));
     }
@@ -322,8 +343,8 @@ static bool pipeline_nearly_empty(vrt_ctx* c) {
 
 // An overlapped launch into copy `set` on render stream `lane` comes behind what it depends on.
 static int order_overlapped_launch(vrt_ctx* c, int set, int lane) {
-    hipStream_t rs = c->lanes[lane].stream;
-    if (c->main_dirty) {  // uploads / prepare / sky kernels queued on the main stream come first
+    hipStream_t rs = lane_stream(c, lane);
+    if (c->main_dirty) {  // uploads / prepare / sky kernels queued on the main stream come first (where it is a lane itself: in stream order)
         HIP_TRY(hipEventRecord(c->ev_main, c->stream));
         for (int s = 0; s < c->n_streams; s++) HIP_TRY(hipStreamWaitEvent(c->lanes[s].stream, c->ev_main, 0));
         c->main_dirty = false;
@@ -477,8 +498,8 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
         const bool defer = overlapped && c->defer_k > 1 && can_defer(c);
         if (!defer && flush_deferred(c) != VRT_OK) return VRT_E_DEVICE;
         const int set = overlapped ? plan_set_of(c->pipe_seq, c->n_sets) : 0;
-        const int lane = overlapped ? plan_lane_of(c->pipe_seq, c->n_streams) : 0;
-        hipStream_t rs = overlapped ? c->lanes[lane].stream : c->stream;
+        const int lane = overlapped ? plan_lane_of(c->pipe_seq, n_lanes(c)) : 0;
+        hipStream_t rs = overlapped ? lane_stream(c, lane) : c->stream;
         bool lone = !overlapped;   // every workgroup slot
         if (overlapped && c->grid_div > 1) lone = pipeline_nearly_empty(c);
         if (overlapped) {
@@ -524,6 +545,8 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
             if (!defer) HIP_TRY(hipStreamWaitEvent(c->stream, p.ev_r, 0));
             c->last_render_set = set;
             c->lanes[lane].last_seq = seq + 1u;
+            c->lanes[lane].last_set = set;
+            if (c->ctx_lane && rs != c->stream) c->ctx_unsettled = true;
         }
         if (defer) capture_slice(c, fp, out, g, set, lane, timed);
         // ReSTIR: spatial reuse and accumulation sample by sample over the planes of the launch (one pass with one sample)

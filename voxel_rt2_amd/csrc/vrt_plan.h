@@ -25,7 +25,7 @@
 // A build with -DVRT_DEV_KNOBS (build_variants/libvrt_dev.so: `python -m voxel_rt2_amd.build --variant dev -DVRT_DEV_KNOBS`,
 // loaded by tests/test_gpu_pipeline.py and the A/B runs of tools/) adds the development switches: the fault-injection hook
 // VRT_TEST_FAIL_LAUNCH and the A/B switches VRT_CULL, VRT_DENSE, VRT_DEEP_ITEMS, VRT_DEEPER_ITEMS, VRT_STREAMS, VRT_GRID_DIV,
-// VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER, VRT_PASS_STREAM, VRT_CAST_VIEW.
+// VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER, VRT_PASS_STREAM, VRT_CTX_LANE, VRT_CAST_VIEW.
 struct Knobs {
     int render = -1;               // -1: the library's choice, 0: fused, 1: pool; -2: a value VRT_RENDER does not know
     bool overlap = true;
@@ -36,6 +36,7 @@ struct Knobs {
     long long deep_items = (long long)12 << 20, deeper_items = (long long)9 << 19;
     int streams = 0, grid_div = 0; // 0: decided from the frame size (plan_pipeline_shape)
     int pass_stream = -1;          // -1: decided with the pipeline's shape (plan_pipeline_shape), 0: grouped passes on the context's stream, 1: on a render stream
+    int ctx_lane = -1;             // -1: decided with the pipeline's shape, 0 / 1: the context's stream is not / is a render lane (where launches can be deferred)
     bool drain_gate = true, fuse_restir = true, overlap_single = true;
     int max_fused = VRT_MAX_FUSED, full_below = 2, chunk = 0, fail_launch = -1, gate_extra = 0, time_every = 0;
     int defer4 = VRT_DEFER_4DEEP, defer8 = 1;   // render launches whose accumulation runs as one pass, per pipeline depth (VRT_DEFER: both)
@@ -55,6 +56,7 @@ static Knobs read_knobs() {
     if (const char* e = getenv("VRT_DEEPER_ITEMS")) k.deeper_items = atoll(e);
     if (const char* e = getenv("VRT_STREAMS")) { const int v = atoi(e); if (v == 2 || v == 3 || v == 4 || v == 8) k.streams = v; }
     if (const char* e = getenv("VRT_PASS_STREAM")) { const int v = atoi(e); if (v == 0 || v == 1) k.pass_stream = v; }
+    if (const char* e = getenv("VRT_CTX_LANE")) { const int v = atoi(e); if (v == 0 || v == 1) k.ctx_lane = v; }
     if (const char* e = getenv("VRT_GRID_DIV")) { const int v = atoi(e); if (v >= 1 && v <= 4) k.grid_div = v; }
     if (const char* e = getenv("VRT_DRAIN_GATE")) k.drain_gate = atoi(e) != 0;
     if (const char* e = getenv("VRT_FUSE")) { const int v = atoi(e); if (v >= 1 && v <= VRT_MAX_FUSED) k.max_fused = v; }
@@ -130,11 +132,20 @@ static inline RenderVariant plan_render_variant(const RenderInputs& in) {
 // 8 547-8 572).  Three render streams lose a quarter at four queues with the pass on either stream (two of them share a queue:
 // 6 650-6 750), the pass on a render stream loses 2.6 % with two (it holds that stream's next launch back: 8 715-8 720) and
 // changes nothing with four (profiles/r06_a_shapes.txt).
+// The context's stream as a third lane.  In the queue-lean shape the context's stream has a queue to itself and carries one pass per
+// K launches.  ctx_lane makes it the lane behind the library's own streams: launches take turns over n_streams + 1 lanes on as many
+// queues, launch k waits for launch k - 2's drain signal (the dispatch gate, as with four streams) instead of its completion, and the
+// grouped pass runs on the lane of the group's last launch, whose next launch is a whole round away.  Only where every launch is
+// deferred (a pass per launch would put every pass in front of the context's stream's own launches), and not beside a forced shape
+// (VRT_STREAMS, VRT_GRID_DIV, VRT_PASS_STREAM measure the shapes above as they were measured); VRT_CTX_LANE=0|1 overrides both
+// for A/B runs, VRT_PASS_STREAM=0 then keeps every pass on the context's stream.
 struct PipelineShape {
     int n_streams;         // depth of the launch pipeline: 2, 4 with launches of half the workgroup slots each, or 8 with quarters
     int grid_div;          // an overlapped launch takes render_blocks / grid_div workgroups
     bool pass_on_render;   // grouped passes run on a render stream (development switch VRT_PASS_STREAM=1: measured, not faster in any shape)
     int defer_k;           // K: render launches whose accumulation runs as one pass (1: every launch has a pass of its own)
+    bool ctx_lane;         // the context's stream is render lane number n_streams: n_streams + 1 lanes, n_streams streams of the pipeline's own
+    bool pass_on_last;     // grouped passes run on the lane of the group's last launch: pass_on_render, or ctx_lane unless VRT_PASS_STREAM=0
 };
 static inline PipelineShape plan_pipeline_shape(size_t items, bool heavy, int hw_queues, bool can_defer, const Knobs& knobs) {
     // (heavy: the dense-grid kernel -- six rays a path instead of two: an item is about twice the work, a rank's 4.1 M items of an
@@ -154,6 +165,11 @@ static inline PipelineShape plan_pipeline_shape(size_t items, bool heavy, int hw
     int k = !can_defer ? 1 : (ns == 4 || (ns < 4 && sh.grid_div == 2)) ? knobs.defer4 : ns == 8 ? knobs.defer8 : 1;
     if (k > VRT_MAX_SETS - ns) k = VRT_MAX_SETS - ns;
     sh.defer_k = k < 1 ? 1 : k;
+    sh.ctx_lane = lean && can_defer && !knobs.streams && !knobs.grid_div && knobs.pass_stream < 0;
+    if (knobs.ctx_lane >= 0) sh.ctx_lane = knobs.ctx_lane != 0 && can_defer;
+    if (sh.defer_k < 2 || ns + 1 > VRT_MAX_STREAMS) sh.ctx_lane = false;
+    if (sh.ctx_lane && sh.defer_k > VRT_MAX_SETS - ns - 1) sh.defer_k = VRT_MAX_SETS - ns - 1;
+    sh.pass_on_last = sh.pass_on_render || (sh.ctx_lane && knobs.pass_stream != 0);
     return sh;
 }
 
@@ -193,7 +209,7 @@ static inline int plan_partial_blocks(int all_blocks, int grid_div) { return (al
 // Which copy overlapped launch number `pipe_seq` writes, and which render stream (and pool scratch) it goes to: consecutive
 // launches take turns.
 static inline int plan_set_of(unsigned pipe_seq, int n_sets) { return (int)(pipe_seq % (unsigned)n_sets); }
-static inline int plan_lane_of(unsigned pipe_seq, int n_streams) { return (int)(pipe_seq % (unsigned)n_streams); }
+static inline int plan_lane_of(unsigned pipe_seq, int n_lanes) { return (int)(pipe_seq % (unsigned)n_lanes); }
 
 // ---- vrt_cast_rays (its two rules of thumb also serve the sampled queries, below) ------------------------------------------------
 // Which view of the pyramid a batch of n rays is walked on: the coarse levels staged in LDS once per workgroup (k_render's
