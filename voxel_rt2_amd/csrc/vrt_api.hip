@@ -47,6 +47,7 @@ static FrameParams make_frame_params(const vrt_ctx* c) {
     fp.light_color = mk3(c->scene.light_color[0], c->scene.light_color[1], c->scene.light_color[2]);
     fp.light_cos_max = c->scene.light_cos_theta_max;
     fp.light_weight = c->scene.light_weight;
+    fp.light_cone_pdf = cone_pdf_inside(fp.light_cos_max);
     fp.floor_height = c->scene.floor_height;
     fp.floor_color = mk3(c->scene.floor_color[0], c->scene.floor_color[1], c->scene.floor_color[2]);
     fp.floor_material = c->scene.floor_material;
@@ -80,6 +81,7 @@ static SceneData make_scene_data(const vrt_ctx* c) {
     sc.pyr.ref_oob = c->ref_oob ? 1 : 0;
     sc.grid = c->d_grid;
     sc.mats = c->d_mats;
+    sc.mats_x = c->d_mats_x;
     sc.sky.scattering = c->d_sky_scat;
     sc.sky.transmittance = c->d_sky_trans;
     sc.sky.res = c->cfg.sky_res;

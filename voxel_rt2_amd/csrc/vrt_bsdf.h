@@ -23,6 +23,21 @@ VRT_DEV void ortho_basis(f3 n, f3& x, f3& y) {  // :32-37
     y = norm3(cross3(n, h));
     x = cross3(n, y);
 }
+// ortho_basis() of a normal whose components are +-0 or +-1 (a voxel face, the floor, a DDA step normal: hit_floor, walk_trip,
+// normal_decode).  With exactly one component of magnitude 1, cross(n, h) has length exactly 1, and sqrt(1) = 1, 1 / 1 = 1,
+// 1 * c = c for every c, signed zeros included: the normalisation changes no bit and is left out.  A step normal taken on an
+// exact tie has two or three non-zero components (and a ray that never stepped has none): those take ortho_basis() -- rare,
+// so that code runs only in waves that hold one.  Returns whether the short form was taken (tests).
+VRT_DEV bool ortho_basis_axis_normal(f3 n, f3& x, f3& y) {
+    if (dm_abs(n.x) + dm_abs(n.y) + dm_abs(n.z) == 1.0f) {
+        f3 h = (dm_abs(n.y) > 0.9f) ? mk3(1.0f, 0.0f, 0.0f) : mk3(0.0f, 1.0f, 0.0f);
+        y = cross3(n, h);
+        x = cross3(n, y);
+        return true;
+    }
+    ortho_basis(n, x, y);
+    return false;
+}
 VRT_DEV f3 cone_dir_from(float cos_max, f3 n, f3 bx, f3 by, float u0, float u1) {  // :44-59 after its two draws, basis hoisted
     float ct = (1.0f - u0) + u0 * cos_max;
     float st = dm_sqrt(1.0f - ct * ct);
@@ -35,8 +50,15 @@ VRT_DEV f3 cone_dir(float cos_max, f3 n, f3 bx, f3 by, dm_rng& rng) {
     const float u0 = dm_rng_f32(&rng), u1 = dm_rng_f32(&rng);
     return cone_dir_from(cos_max, n, bx, by, u0, u1);
 }
+VRT_DEV float cone_pdf_inside(float cos_max) { return 1.0f / (DM_TWO_PI * (1.0f - cos_max)); }
 VRT_DEV float cone_pdf(float cos_max, float cos_theta) {  // :61-63
-    return (cos_theta >= cos_max) ? 1.0f / (DM_TWO_PI * (1.0f - cos_max)) : 0.0f;
+    return (cos_theta >= cos_max) ? cone_pdf_inside(cos_max) : 0.0f;
+}
+// cone_pdf(fp.light_cos_max, cos_theta) with the quotient taken from the frame's parameter block where its maker worked it out
+// (gfx950 has no scalar float division: evaluated in place, the uniform quotient costs every vertex a vector division)
+VRT_DEV float light_cone_pdf(const FrameParams& fp, float cos_theta) {
+    const float inside = (fp.light_cone_pdf > 0.0f) ? fp.light_cone_pdf : cone_pdf_inside(fp.light_cos_max);   // (uniform: a scalar branch)
+    return (cos_theta >= fp.light_cos_max) ? inside : 0.0f;
 }
 VRT_DEV f3 cosine_dir(f3 n, dm_rng& rng) {  // :21-30
     float u0 = dm_rng_f32(&rng), u1 = dm_rng_f32(&rng);

@@ -196,6 +196,7 @@ struct LdsPyramid2 {
     __device__ __forceinline__ bool oob_ref() const { return oob; }
     static constexpr bool flat_descend = true;   // the pooled kernel walks with nearly full waves
     static constexpr bool shadow_branchy = SHBR_;   // ... except SHADE's inline shadow rays in a dense grid (raytrace, vrt_trace.h)
+    static constexpr bool mats_packed = true;   // render_pool_body stages packed material rows (pack_material_row, vrt_path.h)
     const unsigned long long* l0;
     const ulonglong2* l12;
     const unsigned long long* l2;
@@ -228,6 +229,7 @@ struct LdsPyramid2<256, CULL_, SHBR_, OOB_> {
     __device__ __forceinline__ bool oob_ref() const { return oob; }
     static constexpr bool flat_descend = true;
     static constexpr bool shadow_branchy = SHBR_;
+    static constexpr bool mats_packed = true;
     const unsigned long long* l0;
     const unsigned long long* l1;   // LDS [4096]
     const unsigned long long* l2;   // LDS [64]
@@ -418,7 +420,21 @@ __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const Sc
         for (uint32_t i = threadIdx.x; i < n_fine; i += blockDim.x) s_fine[i] = sc.pyr.l0c[i];
         P.l12 = s_l12; P.fine_base = s_fine_base; P.fine = s_fine; P.n_fine = n_fine;
     }
-    for (int i = threadIdx.x; i < 128 * 14; i += blockDim.x) s_mats[i] = sc.mats[i];
+    if constexpr (decltype(P)::mats_packed) {
+        // One packed row per material id: the eight raw columns path_shade() reads and mat_derive() of the row, from the table
+        // k_mat_derived refreshed at the last material upload, on the context's stream.  That refresh is ordered before this
+        // launch on a render lane the way the upload of `mats` itself is: vrt_upload_materials waits for the context's stream
+        // before it returns, and it (like vrt_create, whose refresh nothing waits for) leaves main_dirty set, so the next
+        // launch's lanes wait for an event recorded behind it (order_overlapped_launch, vrt_pipeline.hip); a launch that is
+        // not overlapped runs on the context's stream itself.  A SceneData without the table: derived here, by the same
+        // function.
+        for (int id = threadIdx.x; id < 128; id += blockDim.x) {
+            const Material m = load_material(sc.mats, id);
+            pack_material_row(s_mats + MP_COUNT * id, m, sc.mats_x ? load_mat_derived(sc.mats_x, id) : mat_derive(m));
+        }
+    } else {
+        for (int i = threadIdx.x; i < 128 * 14; i += blockDim.x) s_mats[i] = sc.mats[i];
+    }
     if (threadIdx.x < 8) s_cull[threadIdx.x] = sc.cull[threadIdx.x];
     if (blockIdx.x == 0 && threadIdx.x < VRT_WORK_HEADS) next_counter[threadIdx.x * VRT_WORK_HEAD_STRIDE] = 0u;  // the next launch's heads (idle during this launch)
     if (blockIdx.x == 0 && threadIdx.x == 0) next_counter[1] = 0u;  // and its "drain announced" word

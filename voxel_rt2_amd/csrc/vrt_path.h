@@ -79,6 +79,8 @@ VRT_DEV uint32_t pack_material(int id, f3 albedo) {
     return dm_f2u32((float)id) | (dm_f2u32(albedo.x * 255.0f) << 8) | (dm_f2u32(albedo.y * 255.0f) << 16) |
            (dm_f2u32(albedo.z * 255.0f) << 24);
 }
+// (The divisions stay: with byte_over_255() -- the same bits, vrt_types.h -- the spatial-reuse kernel runs 2 % SLOWER and path_colours()
+// evaluates the then cheap emission for every lane instead of branching round it; measured, profiles/README.md.)
 VRT_DEV f3 unpack_albedo(uint32_t enc) {
     return mk3((float)((enc >> 8) & 255u) / 255.0f, (float)((enc >> 16) & 255u) / 255.0f, (float)((enc >> 24) & 255u) / 255.0f);
 }
@@ -89,6 +91,33 @@ VRT_DEV Material load_material(const float* mats, int id) {
     m.subsurface = p[3]; m.metallic = p[4]; m.specular = p[5]; m.specular_tint = p[6]; m.roughness = p[7];
     m.anisotropic = p[8]; m.sheen = p[9]; m.sheen_tint = p[10]; m.clearcoat = p[11]; m.clearcoat_gloss = p[12];
     m.ior_minus_one = p[13];
+    return m;
+}
+// The material row as path_shade() reads it where a kernel stages its own copy of the table (the pooled render kernels): what
+// mat_derive() makes of the row -- five divisions and a square root per shaded vertex that depend on the material id alone --
+// stands in the row itself, in the place of the six columns no reader of the staged copy uses: base[3] (path_shade() takes the
+// texel's albedo), anisotropic and clearcoat_gloss (only mat_derive() reads them) and ior_minus_one (nobody does).  Still 14
+// floats, so the staged table costs no LDS.  A pyramid type says `mats_packed = true` when the SceneData handed to path_shade()
+// beside it holds such rows in `mats`; every other caller's `mats` is the host's [128][14] table and path_shade() derives inline.
+enum { MP_SUBSURFACE = 0, MP_METALLIC, MP_SPECULAR, MP_SPECULAR_TINT, MP_ROUGHNESS, MP_SHEEN, MP_SHEEN_TINT, MP_CLEARCOAT,
+       MP_AX, MP_AY, MP_CC_ALPHA, MP_W_D, MP_W_S, MP_W_C, MP_COUNT };
+static_assert(MP_COUNT == 14, "a packed material row is as long as a raw one");
+template <class T, class = void> struct mats_packed_of { static constexpr bool value = false; };
+template <class T> struct mats_packed_of<T, std::void_t<decltype(T::mats_packed)>> { static constexpr bool value = T::mats_packed; };
+VRT_DEV void pack_material_row(float* row, const Material& m, const MatDerived& x) {
+    row[MP_SUBSURFACE] = m.subsurface; row[MP_METALLIC] = m.metallic; row[MP_SPECULAR] = m.specular; row[MP_SPECULAR_TINT] = m.specular_tint;
+    row[MP_ROUGHNESS] = m.roughness; row[MP_SHEEN] = m.sheen; row[MP_SHEEN_TINT] = m.sheen_tint; row[MP_CLEARCOAT] = m.clearcoat;
+    row[MP_AX] = x.ax; row[MP_AY] = x.ay; row[MP_CC_ALPHA] = x.cc_alpha; row[MP_W_D] = x.w_d; row[MP_W_S] = x.w_s; row[MP_W_C] = x.w_c;
+}
+// row `id` of a packed table for a vertex of albedo `base`; the three columns the row does not carry read 0 and are not to be used
+VRT_DEV Material load_material_packed(const float* mats, int id, f3 base, MatDerived& x) {
+    const float* p = mats + MP_COUNT * (id & 127);
+    Material m;
+    m.base = base;
+    m.subsurface = p[MP_SUBSURFACE]; m.metallic = p[MP_METALLIC]; m.specular = p[MP_SPECULAR]; m.specular_tint = p[MP_SPECULAR_TINT];
+    m.roughness = p[MP_ROUGHNESS]; m.sheen = p[MP_SHEEN]; m.sheen_tint = p[MP_SHEEN_TINT]; m.clearcoat = p[MP_CLEARCOAT];
+    m.anisotropic = 0.0f; m.clearcoat_gloss = 0.0f; m.ior_minus_one = 0.0f;
+    x.ax = p[MP_AX]; x.ay = p[MP_AY]; x.cc_alpha = p[MP_CC_ALPHA]; x.w_d = p[MP_W_D]; x.w_s = p[MP_W_S]; x.w_c = p[MP_W_C];
     return m;
 }
 
@@ -108,6 +137,7 @@ VRT_DEV f3 xform(const mat4& m, f3 p, float w) {
     return mk3(r.x, r.y, r.z);
 }
 VRT_DEV f2 pixel_texcoord(const FrameParams& fp, float u, float v) {
+    if (fp.render_scale == 1.0f) return mk2((u + 0.5f) * fp.inv_res.x, (v + 0.5f) * fp.inv_res.y);   // x / 1 = x for every x: a uniform test against two divisions
     return mk2((u + 0.5f) * fp.inv_res.x / fp.render_scale, (v + 0.5f) * fp.inv_res.y / fp.render_scale);
 }
 VRT_DEV bool outside_render_area(const FrameParams& fp, float u, float v) {  // pathtracer.py:289-291
@@ -239,10 +269,22 @@ VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& 
     if (surface) {
         VRT_REGION(2);
         p.pos = hit_pos + h.normal * VRT_EPS;
-        Material m = load_material(sc.mats, h.mat_id);
-        m.base = h.albedo;
+        // surf_init(): the material-only terms from the staged row where there is one, the basis in its face-normal form
         Surf s;
-        surf_init(s, m, h.normal, -p.d);
+        {
+            Material m;
+            MatDerived mx;
+            if constexpr (mats_packed_of<PyrT>::value) {
+                m = load_material_packed(sc.mats, h.mat_id, h.albedo, mx);
+            } else {
+                m = load_material(sc.mats, h.mat_id);
+                m.base = h.albedo;
+                mx = mat_derive(m);
+            }
+            f3 tx, ty;
+            ortho_basis_axis_normal(h.normal, tx, ty);
+            surf_set(s, m, mx, h.normal, -p.d, tx, ty);
+        }
 
         // Sun sample (pathtracer.py:435-476) and next direction (478-497).  The random draws keep the reference's
         // order -- two for the cone, then the BSDF sampler's -- but the shadow ray, which draws nothing, is traced
@@ -272,7 +314,7 @@ VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& 
         if (!final_segment) {
             VRT_REGION(10);
             next_d = sample_bsdf(s, p.rng, brdf, pdf, lobe);
-            bounce_light_pdf = cone_pdf(fp.light_cos_max, dot3(fp.light_dir, next_d));
+            bounce_light_pdf = light_cone_pdf(fp, dot3(fp.light_dir, next_d));
         }
         if constexpr (BLACK_SUN && !RESTIR) {
             if (depth > 0 && bounce_light_pdf > 0.0f) {  // case (b): the only use of the sun direction under a black sun
@@ -293,7 +335,7 @@ VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& 
                     VRT_REGION(4);
                     const float light_bsdf_pdf = pdf_all(s, ldir);
                     float w = 1.0f;
-                    if (depth > 0) w = power_heuristic(cone_pdf(fp.light_cos_max, 1.0f), light_bsdf_pdf);
+                    if (depth > 0) w = power_heuristic(light_cone_pdf(fp, 1.0f), light_bsdf_pdf);
                     f3 bd, bs;
                     eval_lobes(s, ldir, LOBE_ALL, bd, bs);
                     f3 sky_t = mk3(1.0f);
@@ -305,7 +347,7 @@ VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& 
                         p.nee_s = p.nee_s + firefly(p.thr * ns);
                         if constexpr (!RESTIR) {
                             // pathtracer.py:567-578: the first-vertex light-sample MIS weight is known here
-                            const float lw = power_heuristic(cone_pdf(fp.light_cos_max, 1.0f), light_bsdf_pdf);
+                            const float lw = power_heuristic(light_cone_pdf(fp, 1.0f), light_bsdf_pdf);
                             p.nee_d = p.nee_d * lw;
                             p.nee_s = p.nee_s * lw;
                         }

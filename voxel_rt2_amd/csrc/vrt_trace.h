@@ -28,6 +28,10 @@ struct SceneData {
     Counters* counters;     // instrumented build only
     const float* cull;      // [8] the solid voxels' bounding box grown by VRT_CULL_MARGIN, voxel units: lo xyz, hi xyz (cull_ray);
                             // [6] != 0: the box leaves part of the grid out, i.e. there are rays to cull (a dense scene: 0)
+    const float* mats_x;    // [128][8] mat_derive() of every row of `mats` (k_mat_derived), or null: whoever stages packed material rows
+                            // (pack_material_row, vrt_path.h) then derives them itself.  Read by that staging alone, so a maker of this
+                            // record that does not know the field need only not stage packed rows (no initialiser: the record stays
+                            // trivial, the host builds clear it with memset)
 };
 
 struct BrickCache { int key; unsigned long long word; };
@@ -520,10 +524,9 @@ VRT_DEV void hit_voxel(const FrameParams& fp, const SceneData& sc, f3 eye, f3 d,
             int m = 0, light = 0;
             if (((tr.ix | tr.iy | tr.iz) & ~(G - 1)) == 0) {
                 uint32_t texel = sc.grid[texel_index<G>(tr.ix, tr.iy, tr.iz)];
-                col = mk3((float)(texel & 255u) / 255.0f, (float)((texel >> 8) & 255u) / 255.0f,
-                          (float)((texel >> 16) & 255u) / 255.0f);
-                float a = (float)(texel >> 24) / 255.0f;
-                m = (int)(a * 255.0f);
+                col = mk3(byte_over_255((float)(texel & 255u)), byte_over_255((float)((texel >> 8) & 255u)),
+                          byte_over_255((float)((texel >> 16) & 255u)));
+                m = (int)(texel >> 24);   // = (int)(((float)k / 255.0f) * 255.0f) for every byte k: the round trip loses nothing
                 light = (m == 2) ? 1 : 0;
             }
             h.albedo = col * (1.0f - 0.9f * f);

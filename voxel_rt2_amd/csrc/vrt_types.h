@@ -60,6 +60,16 @@ VRT_DEV float sq(float x) { return x * x; }
 VRT_DEV bool near_zero3(f3 v) { return dot3(v, v) < 1e-7f; }
 VRT_DEV float lum(f3 c) { return dot3(mk3(0.2125f, 0.7154f, 0.0721f), c); }
 VRT_DEV f3 firefly(f3 v) { return clamp3(v, 0.0f, 300.0f); }
+// (float)k / 255.0f for a byte k = 0..255 (the texel channels, voxel_world.py:47-50; math_utils.py:238-247) without the division's
+// 11-instruction expansion: a product with the rounded reciprocal and one exact-remainder correction.  The same bits as the
+// correctly rounded quotient for each of the 256 inputs it is ever given (tests/test_shade_tables.py compares them all); NOT
+// a division for other operands.
+VRT_DEV float byte_over_255(float k) {
+    const float r = 1.0f / 255.0f;
+    const float q0 = k * r;
+    const float rem = dm_fma(-q0, 255.0f, k);
+    return dm_fma(rem, r, q0);
+}
 
 // Per-pixel results the render kernel writes once and never reads back: streamed (non-temporal) on the device so
 // that they do not push the pooled kernel's scratch lines and the brick words out of L2.
@@ -191,6 +201,11 @@ struct FrameParams {
     float voxel_edges, exposure;
     int max_depth;
     uint32_t seed, frame;
+    // Frame-only expressions, evaluated once where the block is made instead of at every path vertex (the host's IEEE single
+    // division is the correctly rounded one the device code is built with).  Anything but a value > 0 = not worked out -- a maker
+    // that knows nothing of the field and zeroes the block, or poisons it with NaNs (tests/emul/query_emul.h): the reader then
+    // evaluates the expression itself.  (No initialiser: the block stays a trivial record that memset may clear.)
+    float light_cone_pdf;   // cone_pdf_inside(light_cos_max), vrt_bsdf.h: > 0 for every cone (+inf for cos_max = 1)
 };
 
 // First image row of the launch's t-th 8-row tile row, and whether row v is one the launch renders (always, without stripes).
