@@ -181,6 +181,52 @@ typedef struct vrt_ray_hit { float t; int32_t kind; int32_t cell[3]; float norma
 enum { VRT_HIT_MISS = 0, VRT_HIT_FLOOR = 1, VRT_HIT_VOXEL = 2 };
 enum { VRT_RAY_ANY_HIT = 1 };
 int vrt_cast_rays(vrt_ctx* ctx, int64_t n, const vrt_ray* rays, vrt_ray_hit* hits, int on_device);
+/* Ask a PREPARED scene where a moving box first touches it: n caller-supplied axis-aligned boxes, in WORLD units.  At parameter t box k
+ * occupies [lo + t * move, hi + t * move]; hits[k] reports the smallest t in [0, t_max) at which the box's OPEN interior meets a solid
+ * voxel or the floor.  move = 0 is the plain overlap test.  All arithmetic is binary32, uncontracted (include/vrt_detmath.h), left to
+ * right as written; division is the correctly rounded one.
+ * Plane k of the grid is p(k) = (float)k * dx - 1.0f (exact in binary32 for grid_res 128 and 256); cell c, in the index space of
+ * vrt_upload_voxels, spans [p(c_a), p(c_a + 1)] on axis a.
+ * ONE CELL.  For every axis a:
+ *   move_a > 0:   e_a = (p(c_a) - hi_a) / move_a,      x_a = (p(c_a + 1) - lo_a) / move_a;
+ *   move_a < 0:   e_a = (p(c_a + 1) - lo_a) / move_a,  x_a = (p(c_a) - hi_a) / move_a;
+ *   move_a == 0 (either sign of zero): the axis overlaps iff lo_a < p(c_a + 1) && hi_a > p(c_a); then e_a = -inf, x_a = +inf, otherwise
+ *                 the cell is never met.
+ * enter = max(e_x, e_y, e_z) and exit = min(x_x, x_y, x_z), formed with dm_max / dm_min in axis order.  The cell is MET iff
+ * enter < exit && exit > 0.  Met with enter < 0: the box overlaps the cell at the start.  Met with enter >= 0: a contact at
+ * t = enter + 0.0f (a -0 becomes +0), which counts iff t < t_max; the contact axis is the lowest a with e_a == enter and the normal is
+ * -1 or +1 on that axis, against the sign of move_a, zero on the other two.  Touching is not overlapping (the inequalities are strict):
+ * a box resting on a voxel's top face is stopped at t = 0 when it moves down and slides free when it moves sideways.
+ * THE FLOOR is the infinite plane y = floor_height, solid below -- not the render's radius-10 disc.  lo_y < floor_height: the box
+ * overlaps it at the start.  Else, if move_y < 0: t_f = (floor_height - lo_y) / move_y + 0.0f, normal (0, 1, 0), which counts iff
+ * t_f < t_max.  VRT_SWEEP_NO_FLOOR leaves the floor out.
+ * THE RECORD.  (1) The floor overlaps at the start: kind = VRT_SWEEP_START, t = 0, cell = -1, normal = 0.  (2) Else a solid cell
+ * overlaps at the start: kind = VRT_SWEEP_START, t = 0, cell = the overlapping cell with the smallest linear index (x * G + y) * G + z,
+ * normal = 0.  (3) Else the smallest t over the floor and all solid cells wins: the floor is tested first, so a floor / voxel tie is the
+ * floor's (kind = VRT_SWEEP_FLOOR, cell = -1); among cells with bit-equal t the smallest linear index wins (kind = VRT_SWEEP_VOXEL).
+ * (4) Nothing is met: t = +inf, kind = VRT_SWEEP_MISS, cell = -1, normal = 0.
+ * "Solid" is the bit of the occupancy pyramid's finest level (material > 0), and only cells inside the grid exist:
+ * vrt_set_reference_indexing does NOT change the answer (there is no walk whose steps could leave the grid).
+ * INVALID boxes are not tested and get the miss record: a non-finite field (t_max = +inf is allowed); lo_a > hi_a on some axis; a lo or
+ * hi component outside [-VRT_SWEEP_MAX_COORD, VRT_SWEEP_MAX_COORD] (the grid is [-1, 1]^3; the bound keeps the rounding of p - hi far
+ * below one cell); t_max NaN or <= 0.  lo == hi on an axis (a sheet, a segment, a point) is valid; move may be any finite value --
+ * subnormal, 1e30, all zeros.  `reserved` must be 0: on the host path this is checked before anything runs (VRT_E_INVALID), on the
+ * device path such a box is treated as invalid.  Every box ends: the work is bounded by the grid's (grid_res / 4)^3 bricks.
+ * on_device = 0: host arrays, borrowed for the call, staged in chunks (n is limited by memory only); the call returns when `hits` is
+ * filled.  on_device = 1: both are device memory (a torch tensor's data_ptr()); the work is only queued on the context's stream, no
+ * host synchronisation -- the caller keeps both unchanged until work queued on that stream behind the call has run.  Ordered like
+ * vrt_update_voxels: a query queued after an edit sees the new grid, one queued before it the old.
+ * The query READS scene data and nothing else: no history, g-buffer, counter, frame number or statistic is touched, the pending
+ * accumulation (vrt_accumulate) is not forced, and frames rendered around it are bit for bit the frames rendered without it.
+ * VRT_E_INVALID: NULL arguments, n < 0, on_device not 0 or 1, a non-zero `reserved` (host path); VRT_E_STATE: before vrt_prepare, or
+ * after a vrt_upload_voxels that no vrt_prepare has followed; n = 0 returns VRT_OK.  No counterpart in the reference: its scene is a
+ * picture. */
+typedef struct vrt_box_sweep { float lo[3]; uint32_t flags; float hi[3]; uint32_t reserved; float move[3]; float t_max; } vrt_box_sweep;   /* 48 bytes */
+typedef struct vrt_sweep_hit { float t; int32_t kind; int32_t cell[3]; float normal[3]; } vrt_sweep_hit;   /* 32 bytes */
+enum { VRT_SWEEP_MISS = 0, VRT_SWEEP_FLOOR = 1, VRT_SWEEP_VOXEL = 2, VRT_SWEEP_START = 3 };
+enum { VRT_SWEEP_NO_FLOOR = 1 };
+#define VRT_SWEEP_MAX_COORD 64.0f
+int vrt_sweep_boxes(vrt_ctx* ctx, int64_t n, const vrt_box_sweep* boxes, vrt_sweep_hit* hits, int on_device);
 /* How much light arrives along a ray: n caller-supplied rays, in WORLD units, each path-traced n_samples times on a PREPARED scene, and
  * the mean of the samples in out[k].  Sample s (0 <= s < n_samples) of ray k is one run of the reference's render body
  * (pathtracer.py:355-632) with ReSTIR off and a static camera, started at `origin` along `dir` instead of the camera's position and

@@ -15,6 +15,14 @@ RAY = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("dir", np.flo
 HIT = np.dtype([("t", np.float32), ("kind", np.int32), ("cell", np.int32, 3), ("normal", np.float32, 3), ("albedo", np.float32, 3),
                 ("mat_id", np.int32)])
 assert RAY.itemsize == 32 and HIT.itemsize == 48
+# vrt_box_sweep / vrt_sweep_hit (vrt_sweep_boxes)
+SWEEP_MISS, SWEEP_FLOOR, SWEEP_VOXEL, SWEEP_START = 0, 1, 2, 3
+SWEEP_NO_FLOOR = 1
+SWEEP_MAX_COORD = 64.0
+BOX_SWEEP = np.dtype([("lo", np.float32, 3), ("flags", np.uint32), ("hi", np.float32, 3), ("reserved", np.uint32), ("move", np.float32, 3),
+                      ("t_max", np.float32)])
+SWEEP_HIT = np.dtype([("t", np.float32), ("kind", np.int32), ("cell", np.int32, 3), ("normal", np.float32, 3)])
+assert BOX_SWEEP.itemsize == 48 and SWEEP_HIT.itemsize == 32
 # vrt_path_ray / vrt_radiance (vrt_trace_radiance)
 PATH_RAY = np.dtype([("origin", np.float32, 3), ("stream", np.uint32), ("dir", np.float32, 3), ("reserved", np.uint32)])
 RADIANCE = np.dtype([("rgb", np.float32, 3), ("t", np.float32)])
@@ -98,6 +106,7 @@ def declare(lib, prefix):
     sig("prepare", C.c_int, P)
     sig("update_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
     sig("cast_rays", C.c_int, P, C.c_int64, P, P, C.c_int)
+    sig("sweep_boxes", C.c_int, P, C.c_int64, P, P, C.c_int)
     sig("trace_radiance", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)
     sig("gather_irradiance", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)
     sig("gather_probes", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)

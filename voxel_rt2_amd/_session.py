@@ -121,6 +121,13 @@ class NativeSession:
         `out` is returned, not yet filled."""
         return self._query("cast_rays", rays, out, n, "RAY", "HIT", (), "ray", "records")
 
+    def sweep_boxes(self, boxes, out=None, n=None):
+        """Moving boxes against the prepared scene (include/vrt_api.h, vrt_sweep_boxes).  Host path: `boxes` is an array of
+        _abi.BOX_SWEEP, the result an array of _abi.SWEEP_HIT (`out` if given).  Device path: `boxes` and `out` are torch tensors on the
+        device holding the same 48- and 32-byte records (any dtype; `n` boxes, by default as many as `boxes` holds); the work is queued
+        on the session's stream and `out` is returned, not yet filled."""
+        return self._query("sweep_boxes", boxes, out, n, "BOX_SWEEP", "SWEEP_HIT", (), "box", "records")
+
     def trace_radiance(self, rays, samples=1, first_frame=0, out=None, n=None):
         """Path-traced radiance along rays (include/vrt_api.h, vrt_trace_radiance): the mean of `samples` samples a ray, sample s on
         random stream (seed, first_frame + s, ray.stream, 0).  Host path: `rays` is an array of _abi.PATH_RAY, the result an array of

@@ -546,6 +546,26 @@ int vrt_cast_rays(vrt_ctx* c, int64_t n, const vrt_ray* rays, vrt_ray_hit* hits,
     if (on_device) return queue((long long)n, rays, hits);
     return staged_query(c, (long long)n, std::min<long long>(plan_cast_chunk(), (long long)n), rays, hits, queue);
 }
+static_assert(sizeof(vrt_box_sweep) == 48 && sizeof(vrt_sweep_hit) == 32, "record sizes of include/vrt_api.h");
+int vrt_sweep_boxes(vrt_ctx* c, int64_t n, const vrt_box_sweep* boxes, vrt_sweep_hit* hits, int on_device) {
+    if (!c || !boxes || !hits) return fail(VRT_E_INVALID, "null argument");
+    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    if (!c->prepared) return fail(VRT_E_STATE, "vrt_sweep_boxes asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
+    if (n == 0) return VRT_OK;
+    if (!on_device)
+        for (int64_t k = 0; k < n; k++) if (boxes[k].reserved != 0u) return fail(VRT_E_INVALID, "a box's `reserved` field must be 0");
+    HIP_TRY(hipSetDevice(c->device));
+    QueryInputs q = query_inputs(c);
+    // the scene's box in either indexing mode: only cells inside the grid exist for a sweep, so no box "meets" anything outside it
+    q.sc.cull = c->d_cull + (c->knobs.cull != 0 ? 0 : 8);
+    auto queue = [&](long long m, const vrt_box_sweep* d_boxes, vrt_sweep_hit* d_hits) -> int {
+        HIP_TRY(launch_sweep_boxes(c->stream, c->cfg.grid_res, c->n_cu, q.fp.floor_height, q.sc, m, d_boxes, d_hits));
+        return VRT_OK;
+    };
+    if (on_device) return queue((long long)n, boxes, hits);
+    return staged_query(c, (long long)n, std::min<long long>(plan_sweep_chunk(), (long long)n), boxes, hits, queue);
+}
 int vrt_trace_radiance(vrt_ctx* c, int64_t n, const vrt_path_ray* rays, int n_samples, uint32_t first_frame, vrt_radiance* out, int on_device) {
     return sampled_query<RadianceQuery>(c, "vrt_trace_radiance", "ray", n, rays, n_samples, first_frame, out, on_device);
 }

@@ -14,6 +14,7 @@
 #include "vrt_plan.h"
 #include "vrt_edit.h"
 #include "vrt_cast.h"
+#include "vrt_sweep.h"
 #include "vrt_query.h"
 #include "vrt_denoise.h"
 
@@ -56,6 +57,10 @@ hipError_t launch_cast_rays(hipStream_t st, int grid_res, bool staged, bool oob,
                             const vrt_ray* rays, vrt_ray_hit* hits);
 // vrt_fetch_voxels: the stored voxels of `box` (valid, not empty) gathered into box_mat / box_rgb (device memory)
 hipError_t launch_fetch_voxels(hipStream_t st, int grid_res, const EditBox& box, const int8_t* mat, const uint8_t* rgb, int8_t* box_mat, uint8_t* box_rgb);
+// vrt_sweep_boxes: n boxes (device memory) through k_sweep_boxes, a wave a box (vrt_sweep.h); four boxes a workgroup per turn of its loop,
+// the grid n_cu x the kernel's residency at most (plan_sweep_blocks).  Of sc the two finest pyramid levels and the culling box are read.
+hipError_t launch_sweep_boxes(hipStream_t st, int grid_res, int n_cu, float floor_height, const SceneData& sc, long long n, const vrt_box_sweep* boxes,
+                              vrt_sweep_hit* hits);
 // A sampled query Q (vrt_query.h: RadianceQuery, SensorQuery, ProbeQuery): samples [s0, s0 + count) of n records (device memory) worked into
 // plane[n * count] by the query's item kernel (k_trace_radiance, k_gather_irradiance, k_gather_probes) and folded into out[n] (k_fold_query).
 // n * count <= Q::max_items; staged / oob as for launch_cast_rays; head: one word of device memory, the launch's work counter.

@@ -15,6 +15,7 @@
 //   k_temporal_group                                      the passes of several consecutive launches in one (static camera)
 //   k_tonemap                                             LDR presentation
 //   k_cast_rays / k_fetch_voxels                          vrt_cast_rays: caller-supplied rays through next_hit; vrt_fetch_voxels
+//   k_sweep_boxes                                         vrt_sweep_boxes: caller-supplied boxes moved through the pyramid, a wave a box
 //   k_trace_radiance                                      vrt_trace_radiance: caller-supplied rays through the path state machine
 //   k_gather_irradiance                                   vrt_gather_irradiance: a sun sample and a hemisphere path per (sensor, sample)
 //   k_gather_probes                                       vrt_gather_probes: a sun sample and a sphere path per (probe, sample)
@@ -1145,6 +1146,34 @@ __global__ void k_fetch_voxels(EditBox box, int G, const int8_t* __restrict__ ma
     if (i < edit_box_voxels(box)) fetch_box_voxel(box, G, i, mat, rgb, box_mat, box_rgb);
 }
 
+// ---- vrt_sweep_boxes: caller-supplied boxes moved through the occupancy pyramid (vrt_sweep.h holds everything but the merge) ------------------
+// One WAVE per box, four boxes in flight per workgroup, a grid-stride loop over the batch on a grid that fits the chip (plan_sweep_blocks).
+// The 64 lanes share the 4x4x4 bricks of the box's candidate region, x fastest, so a wave's l0 loads are neighbours; each lane keeps its
+// best candidate as one 64-bit key (sweep_lane), a butterfly of six __shfl_xor steps leaves the smallest on every lane, and lane 0 writes
+// the record with ordinary vector stores.  Nothing is staged: a box reads the few l1 words over its region and the l0 words behind their
+// set bits once, so there is no reuse for LDS to serve, and no LDS means residency is bounded by registers alone.  The box record is
+// read by all 64 lanes from one address (a broadcast load).  Everything a lane branches on outside sweep_lane is wave-uniform.
+__global__ __launch_bounds__(256) void k_sweep_boxes(SceneData sc, float floor_height, int G, long long n, const vrt_box_sweep* __restrict__ boxes,
+                                                     vrt_sweep_hit* __restrict__ hits) {
+    const int lane = threadIdx.x & 63;
+    const long long stride = (long long)gridDim.x * VRT_SWEEP_BOXES_PER_BLOCK;
+    for (long long i = (long long)blockIdx.x * VRT_SWEEP_BOXES_PER_BLOCK + (threadIdx.x >> 6); i < n; i += stride) {
+        const vrt_box_sweep b = boxes[i];
+        bool walk;
+        SweepKey best = sweep_begin(b, floor_height, walk);
+        if (walk) {
+            const SweepRegion r = sweep_region(b, G, sc.cull);
+            if (!r.empty) best = sweep_lane(b, r, G, sc.pyr.l0, sc.pyr.l1, best, lane, 64, true);
+            for (int m = 32; m >= 1; m >>= 1) best = sweep_better(best, __shfl_xor(best, m, 64));
+        }
+        if (lane == 0) {
+            vrt_sweep_hit h;
+            sweep_record(best, b, G, h);
+            hits[i] = h;
+        }
+    }
+}
+
 // ---- vrt_trace_radiance: caller-supplied rays through the path state machine (vrt_radiance.h holds the per-item body) --------------
 // The work item is (ray, sample): item i of a launch is ray i % n_rays, sample s0 + i / n_rays of the block -- a sample's rays side by
 // side, so neighbouring lanes start on neighbouring rays, and one ray with 4096 samples fills the chip as 4096 rays with one do.
@@ -1617,6 +1646,20 @@ hipError_t launch_cast_rays(hipStream_t st, int grid_res, bool staged, bool oob,
 }
 hipError_t launch_fetch_voxels(hipStream_t st, int grid_res, const EditBox& box, const int8_t* mat, const uint8_t* rgb, int8_t* box_mat, uint8_t* box_rgb) {
     hipLaunchKernelGGL(k_fetch_voxels, dim3((edit_box_voxels(box) + 255) / 256), dim3(256), 0, st, box, grid_res, mat, rgb, box_mat, box_rgb);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t launch_sweep_boxes(hipStream_t st, int grid_res, int n_cu, float floor_height, const SceneData& sc, long long n, const vrt_box_sweep* boxes,
+                              vrt_sweep_hit* hits) {
+    static std::atomic<int> residency{0};   // (asked once: it depends on nothing a call can change)
+    int per_cu = residency.load(std::memory_order_relaxed);
+    if (per_cu == 0) {
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sweep_boxes, 256, 0);
+        if (e != hipSuccess) return e;
+        residency.store(per_cu, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(k_sweep_boxes, dim3(plan_sweep_blocks(n, n_cu, per_cu)), dim3(256), 0, st, sc, floor_height, grid_res, n, boxes, hits);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -230,6 +230,17 @@ static inline int plan_cast_blocks(long long n, int n_cu, int blocks_per_cu) {
     return (int)(want < fit ? want : fit);
 }
 
+// ---- vrt_sweep_boxes ------------------------------------------------------------------------------------------------------------------
+// Boxes a host-path call stages at a time (80 bytes of device memory a box, as a ray: the batch size is limited by the caller's memory only).
+static inline long long plan_sweep_chunk() { return 1 << 18; }
+// Workgroups of a launch over n boxes: a wave of 64 lanes a box, so four boxes a workgroup of 256 per turn of its loop, and no more
+// workgroups than fit on the chip at once (plan_cast_blocks' rule with 4 in the place of 256).
+#define VRT_SWEEP_BOXES_PER_BLOCK 4
+static inline int plan_sweep_blocks(long long n, int n_cu, int blocks_per_cu) {
+    const long long want = (n + VRT_SWEEP_BOXES_PER_BLOCK - 1) / VRT_SWEEP_BOXES_PER_BLOCK, fit = (long long)n_cu * (blocks_per_cu > 0 ? blocks_per_cu : 1);
+    return (int)(want < fit ? want : fit);
+}
+
 // ---- the sampled queries: vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes (vrt_query.h) ----------------------------------------------------
 // The work item is (record, sample) -- (ray, sample) or (sensor, sample); a finished item leaves its value in a scratch plane -- 12 bytes
 // an item for a radiance, a 32-byte vrt_irradiance record of four terms for a sensor -- which k_fold_query sums per record in sample

@@ -341,6 +341,38 @@ class Renderer(VoxelStore):
         rays["flags"] = np.where(np.asarray(any_hit, bool), _abi.RAY_ANY_HIT, 0)
         return self._s.cast_rays(rays)
 
+    # -- moving boxes through the scene (include/vrt_api.h, vrt_sweep_boxes; no counterpart in the reference) ----------------------
+    def sweep_boxes(self, lo, hi, move, t_max=1.0, floor=True):
+        """Where axis-aligned boxes [lo, hi] (world units) first touch the scene when moved by t * move, 0 <= t < t_max, on the scene as
+        prepare_data() / update_voxels() left it: an array of _abi.SWEEP_HIT (t, kind, cell, normal), one record a box.  lo, hi, move:
+        (n, 3) or (3,); t_max and floor: scalars or one value a box.  floor=False leaves the floor plane out.  kind is SWEEP_MISS,
+        SWEEP_FLOOR, SWEEP_VOXEL or SWEEP_START (the box overlaps something before it moves); the box may move to lo + t * move.
+        `cell` is an array index, as cast_rays reports it."""
+        if not getattr(self, "_prepared", False):
+            raise NativeError("sweep_boxes asks a prepared scene: call prepare_data() first")
+        self._push()
+        lo = np.asarray(lo, np.float32).reshape(-1, 3)
+        boxes = np.zeros(len(lo), _abi.BOX_SWEEP)
+        boxes["lo"], boxes["hi"], boxes["move"] = lo, np.asarray(hi, np.float32).reshape(-1, 3), np.asarray(move, np.float32).reshape(-1, 3)
+        boxes["t_max"] = t_max
+        boxes["flags"] = np.where(np.asarray(floor, bool), 0, _abi.SWEEP_NO_FLOOR)
+        return self._s.sweep_boxes(boxes)
+
+    def overlap_boxes(self, lo, hi, floor=True):
+        """Whether boxes [lo, hi] overlap a solid voxel or the floor where they stand (a sweep with move = 0; touching is not
+        overlapping): (bool[n], int32[n, 3]) -- the first overlapping cell by linear index, -1 for the floor and where nothing overlaps."""
+        lo = np.asarray(lo, np.float32).reshape(-1, 3)
+        hits = self.sweep_boxes(lo, hi, np.zeros_like(lo), 1.0, floor)
+        return hits["kind"] == _abi.SWEEP_START, hits["cell"].copy()
+
+    def box_of_voxels(self, lo_idx, hi_idx):
+        """The world-space (lo, hi) of the index box [lo_idx, hi_idx) of array indices -- what update_voxels edits and fetch_voxels
+        reads -- exact in float32: an edit box and a sweep box are the same thing."""
+        dx = np.float32(2.0 / self.voxel_grid_res)
+        lo = np.asarray(lo_idx, np.int64).astype(np.float32) * dx - np.float32(1.0)
+        hi = np.asarray(hi_idx, np.int64).astype(np.float32) * dx - np.float32(1.0)
+        return lo, hi
+
     def pick_ray(self, u, v):
         """(origin, direction) of the ray through the centre of pixel (u, v), v = 0 at the bottom: get_cast_dir (pathtracer.py:293-312)
         without the TAA jitter, statement by statement in float32, from the matrices and the position the renderer was last given."""
