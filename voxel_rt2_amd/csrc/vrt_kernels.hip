@@ -183,8 +183,8 @@ struct LdsPyramid {  // coarse levels in LDS, fine level through L2
     __device__ __forceinline__ unsigned long long load_l2(int i) const { return l2[i]; }
     __device__ __forceinline__ unsigned long long load_l3() const { return w3; }
 };
-// The pooled kernel's view.  128^3: each l1 word beside its parent l2 word ({w1, w2}[512], one 16-byte LDS read per
-// cell), and the head of the compacted fine level (Pyramid::l0c) in LDS too -- a sparse scene's fine level is a few
+// The pooled kernel's view.  128^3: each l1 word beside what the walk needs of its parent l2 word and the l1 cell's fine base
+// ({w1, coarse_pack()}[512], vrt_trace.h: one 16-byte LDS read per cell and nothing to evaluate above level 3), and the head of the compacted fine level (Pyramid::l0c) in LDS too -- a sparse scene's fine level is a few
 // hundred words, and the fine word is the load every other DDA step depends on (L2: ~700 cycles, LDS: ~130).
 // CULL: rays that cannot hit a voxel are not walked (cull_ray, vrt_trace.h).  A launch over a scene whose solids fill the grid
 // has nothing to cull and runs the instantiation without the test (its registers cost a dense 4K frame 2.5 %).
@@ -198,22 +198,31 @@ struct LdsPyramid2 {
     static constexpr bool flat_descend = true;   // the pooled kernel walks with nearly full waves
     static constexpr bool shadow_branchy = SHBR_;   // ... except SHADE's inline shadow rays in a dense grid (raytrace, vrt_trace.h)
     static constexpr bool mats_packed = true;   // render_pool_body stages packed material rows (pack_material_row, vrt_path.h)
+    static constexpr bool coarse_packed = true;   // load_coarse hands out coarse_pack() (vrt_trace.h) and no l2 word
     const unsigned long long* l0;
-    const ulonglong2* l12;
+    const ulonglong2* l1p;             // LDS [512]: {l1 word, coarse_pack() of the l1 cell}
     const unsigned long long* l2;
-    const uint32_t* fine_base;         // LDS copy of Pyramid::l0c_base
     const unsigned long long* fine;    // LDS copy of l0c[0 .. n_fine)
     uint32_t n_fine;
+    bool all_fine;                     // wave-uniform: n_fine is all the fine words the scene has
     __device__ __forceinline__ unsigned long long load_l0(int i) const { return l0[i]; }
-    __device__ __forceinline__ unsigned long long load_l1(int i) const { return l12[i].x; }
+    __device__ __forceinline__ unsigned long long load_l1(int i) const { return l1p[i].x; }
     __device__ __forceinline__ unsigned long long load_l2(int i) const { return l2[i]; }
     __device__ __forceinline__ unsigned long long load_l3() const { return 0ULL; }
-    __device__ __forceinline__ unsigned long long load_fine(int key, uint32_t idx) const { return idx < n_fine ? fine[idx] : l0[key]; }
-    __device__ __forceinline__ void load_coarse(int i1, int i2, unsigned long long& w1, unsigned long long& w2, uint32_t& base) const {
-        (void)i2;
-        const ulonglong2 v = l12[i1];
-        w1 = v.x; w2 = v.y;
-        base = fine_base[i1];
+    // A scene whose fine words all fit (every sparse one) asks LDS and nothing else.  Otherwise each lane asks the memory
+    // its word is in -- as two loads, an LDS and a global one: a single load through a selected generic address is a flat
+    // load behind a 64-bit address select.  (The address space is spelled out, or the loads are merged back into that.)
+    __device__ __forceinline__ unsigned long long load_fine(int key, uint32_t idx) const {
+        const auto staged = (const __attribute__((address_space(3))) unsigned long long*)fine;
+        if (all_fine) return staged[idx];
+        if (idx < n_fine) return staged[idx];
+        return l0[key];
+    }
+    __device__ __forceinline__ void load_coarse(int i1, int i2, unsigned long long& w1, unsigned long long& w2, uint32_t& packed) const {
+        (void)i2; (void)w2;
+        const ulonglong2 v = l1p[i1];
+        w1 = v.x;
+        packed = (uint32_t)v.y;
     }
 };
 // 256^3: the whole l1 level (16^3 words, 32 KiB) and l2 (4^3 words) resident in LDS -- the brick cache of this grid:
@@ -389,11 +398,10 @@ __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const Sc
     constexpr int WAVES = pool_shape<G>(D12).waves, SLOTS = pool_shape<G>(D12).slots;
     constexpr int WORDS = (SLOTS + 63) / 64;
     constexpr bool BIG = (G == 256);   // which coarse levels are staged how: see LdsPyramid2
-    __shared__ ulonglong2 s_l12[BIG ? 1 : 512];
+    __shared__ ulonglong2 s_l1p[BIG ? 1 : 512];
     __shared__ unsigned long long s_l1[BIG ? 4096 : 1];
     __shared__ unsigned long long s_l2[BIG ? 64 : 8];
     __shared__ unsigned long long s_fine[BIG ? 1 : VRT_POOL_FINE_WORDS];
-    __shared__ uint32_t s_fine_base[BIG ? 1 : 512];
     __shared__ float s_mats[128 * 14];
     __shared__ float s_cull[8];
     __shared__ uint32_t s_pool[WAVES][PF_COUNT * SLOTS];
@@ -408,18 +416,19 @@ __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const Sc
         P.l1 = s_l1;
         P.w3 = sc.pyr.l3[0];
     } else {
-        for (int i = threadIdx.x; i < 512; i += blockDim.x) {
+        // Packed here, every launch, from the levels as they stand: an edit or a rebuild of the scene needs no table of its own.
+        for (int i = threadIdx.x; i < 512; i += blockDim.x) {   // i = the l1 cell (z4, y4, x4), three bits each
             ulonglong2 v;
             v.x = sc.pyr.l1[i];
-            v.y = sc.pyr.l2[(((i >> 8) & 1) << 2) | (((i >> 5) & 1) << 1) | ((i >> 2) & 1)];
-            s_l12[i] = v;
-            s_fine_base[i] = sc.pyr.l0c_base[i];
+            const unsigned long long w2 = sc.pyr.l2[(((i >> 8) & 1) << 2) | (((i >> 5) & 1) << 1) | ((i >> 2) & 1)];
+            v.y = coarse_pack(w2, i & 7, (i >> 3) & 7, i >> 6, sc.pyr.l0c_base[i]);   // l0c_base <= 32768: below bit VRT_COARSE_BASE_BITS
+            s_l1p[i] = v;
         }
         if (threadIdx.x < 8) s_l2[threadIdx.x] = sc.pyr.l2[threadIdx.x];
-        uint32_t n_fine = *sc.pyr.l0c_count;  // non-empty fine words of the scene; the first VRT_POOL_FINE_WORDS live in LDS
-        if (n_fine > VRT_POOL_FINE_WORDS) n_fine = VRT_POOL_FINE_WORDS;
+        const uint32_t n_all = *sc.pyr.l0c_count;  // non-empty fine words of the scene; the first VRT_POOL_FINE_WORDS live in LDS
+        const uint32_t n_fine = n_all > VRT_POOL_FINE_WORDS ? VRT_POOL_FINE_WORDS : n_all;
         for (uint32_t i = threadIdx.x; i < n_fine; i += blockDim.x) s_fine[i] = sc.pyr.l0c[i];
-        P.l12 = s_l12; P.fine_base = s_fine_base; P.fine = s_fine; P.n_fine = n_fine;
+        P.l1p = s_l1p; P.fine = s_fine; P.n_fine = n_fine; P.all_fine = n_all <= VRT_POOL_FINE_WORDS;
     }
     if constexpr (decltype(P)::mats_packed) {
         // One packed row per material id: the eight raw columns path_shade() reads and mat_derive() of the row, from the table
@@ -1411,6 +1420,7 @@ hipError_t launch_prepare(hipStream_t st, int G, const int8_t* mat, const uint8_
     if (G == 256) {  // the top word: bit = l2 word non-zero
         hipLaunchKernelGGL(k_build_coarse, dim3(1), dim3(64), 0, st, (const unsigned long long*)l2, l3, 1);
     } else {         // the compacted fine level of the pooled kernel's LDS copy (128^3 only)
+        if (n0 * n0 * n0 >= (1 << (VRT_COARSE_BASE_BITS - 4))) return hipErrorInvalidValue;   // l0c_base counts fine words: coarse_pack (vrt_trace.h) keeps it below its level bits
         hipLaunchKernelGGL(k_build_l0c, dim3(1), dim3(512), 0, st, (const unsigned long long*)l0, (const unsigned long long*)l1, l0c, l0c_base);
     }
     VRT_LAUNCH_CHECK();

@@ -167,10 +167,36 @@ VRT_DEV unsigned brick_two_lods(unsigned long long w, int cx, int cy, int cz) {
 
 // The coarse context of a LOD-0 cell: the l1 and l2 brick words it falls in and where the fine words behind that
 // l1 word start in the compacted fine level (Pyramid::l0c).
+// (A pyramid type with `coarse_packed` leaves w2 alone and hands out coarse_pack() in `fine_base`: see there.)
 struct CoarseWords { unsigned long long w1, w2; uint32_t fine_base; };
 
-// All of it in one request (one 16-byte and one 4-byte LDS read in the kernels).  It depends on the cell only, so
-// the WALK loop asks for the next cell's context at the end of a step and meets it a step later.
+// What descend_flat() takes from the l2 word is the same for every cell of one 16^3 l1 cell (x4, y4, z4) = (x >> 4, y >> 4,
+// z >> 4): levels 4, 5 and 6 of its occupancy mask.  At 128^3 that is the index the l1 word and the fine base already hang on, so
+// whoever stages those per l1 cell can evaluate the three bits there, once, and ship them above the fine base:
+//   bits 0..28  Pyramid::l0c_base of the l1 cell.  At most 32^3 = 32768, the number of fine words of a 128^3 grid
+//               (VRT_COARSE_BASE_BITS; the launcher of k_build_l0c asserts the same)
+//   bit  29     level 4: the l1 cell is occupied          } brick_two_lods(w2, x4, y4, z4)
+//   bit  30     level 5: the 2x2x2 block of l1 cells is   }
+//   bit  31     level 6: the l2 word is not zero
+// -- the expressions of descend_flat() itself, so the mask is the same by construction.  A pyramid type says `coarse_packed`
+// when its load_coarse() returns this word in CoarseWords::fine_base (and no w2).
+// A base is in fact below bit 16, so four bits further down the entry is still clear of it: one shift by 25 leaves the three
+// levels at bits 4..6, where descend_flat() keeps them, over zeros (coarse_packed_levels).
+#define VRT_COARSE_BASE_BITS 29
+static_assert(GridDim<128>::n0 * GridDim<128>::n0 * GridDim<128>::n0 < (1 << (VRT_COARSE_BASE_BITS - 4)), "a fine base must stay below the packed level bits, shifted down to bits 4..6");
+VRT_DEV uint32_t coarse_pack(unsigned long long w2, int x4, int y4, int z4, uint32_t fine_base) {
+    const unsigned occ456 = (w2 != 0ULL ? 4u : 0u) | brick_two_lods(w2, x4, y4, z4);
+    return fine_base | (occ456 << VRT_COARSE_BASE_BITS);
+}
+VRT_DEV unsigned coarse_packed_occ456(uint32_t packed) { return packed >> VRT_COARSE_BASE_BITS; }
+VRT_DEV unsigned coarse_packed_levels(uint32_t packed) { return packed >> (VRT_COARSE_BASE_BITS - 4); }   // = occ456 << 4
+VRT_DEV uint32_t coarse_packed_base(uint32_t packed) { return packed & ((1u << VRT_COARSE_BASE_BITS) - 1u); }
+template <class T, class = void> struct coarse_packed_of { static constexpr bool value = false; };
+template <class T> struct coarse_packed_of<T, std::void_t<decltype(T::coarse_packed)>> { static constexpr bool value = T::coarse_packed; };
+
+// All of it in one request (one 16-byte LDS read in the pooled kernels at 128^3, a second, 4-byte one for the fine base
+// elsewhere).  It depends on the cell only, so the WALK loop asks for the next cell's context at the end of a step and meets
+// it a step later.
 template <class PyrT>
 VRT_DEV void coarse_fetch(const PyrT& P, int x, int y, int z, CoarseWords& c) {
     constexpr int G = PyrT::G;
@@ -195,8 +221,12 @@ VRT_DEV int descend_flat(const PyrT& P, const CoarseWords& c, int x, int y, int 
     const bool inside = ((x | y | z) & ~(G - 1)) == 0;  // outside the grid: empty, as in descend()
     if constexpr (oob_capable_of<PyrT>::value) { if (!inside && P.oob_ref()) return descend_outside(P, x, y, z, lod, solid, nq); }
     const int xm = x & (G - 1), ym = y & (G - 1), zm = z & (G - 1);
-    unsigned occ = (c.w2 != 0ULL ? 64u : 0u) | (brick_two_lods(c.w2, xm >> 4, ym >> 4, zm >> 4) << 4) |
-                   (brick_two_lods(c.w1, xm >> 2, ym >> 2, zm >> 2) << 2);
+    constexpr bool PACKED = coarse_packed_of<PyrT>::value;   // levels 4-6 come evaluated, above the fine base (coarse_pack)
+    static_assert(!PACKED || G == 128, "the packed coarse entry is the 128^3 one");
+    unsigned occ = brick_two_lods(c.w1, xm >> 2, ym >> 2, zm >> 2) << 2;
+    if constexpr (PACKED) occ |= coarse_packed_levels(c.fine_base);
+    else occ |= (c.w2 != 0ULL ? 64u : 0u) | (brick_two_lods(c.w2, xm >> 4, ym >> 4, zm >> 4) << 4);
+    const uint32_t fine_base = PACKED ? coarse_packed_base(c.fine_base) : c.fine_base;
     if (G == 256) occ |= (P.load_l3() & brick_sub(xm >> 6, ym >> 6, zm >> 6)) != 0ULL ? 128u : 0u;  // LOD 7 (LOD 6 = its bit = w2 != 0)
     const unsigned upto = (2u << lod) - 1u;  // levels 0..lod
     // the fine brick word matters only when every level from `lod` down to 2 is occupied
@@ -209,9 +239,9 @@ VRT_DEV int descend_flat(const PyrT& P, const CoarseWords& c, int x, int y, int 
             const unsigned long long below = c.w1 & ((1ULL << bit) - 1ULL);
             bc.key = key;
             bc.word = 0ULL;  // a walk that starts below LOD 2 can stand in an empty brick: nothing to load
-            if ((c.w1 >> bit) & 1ULL) bc.word = P.load_fine(key, c.fine_base + (uint32_t)__builtin_popcountll(below));
+            if ((c.w1 >> bit) & 1ULL) bc.word = P.load_fine(key, fine_base + (uint32_t)__builtin_popcountll(below));
         }
-        occ |= brick_two_lods(bc.word, xm, ym, zm);
+        occ |= brick_two_lods(bc.word, x, y, z);   // (its two low bits per axis: those of xm, ym, zm, without the masks)
     }
     const unsigned empty = inside ? (~occ & upto) : upto;
     solid = empty == 0u;
