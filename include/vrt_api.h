@@ -153,6 +153,51 @@ int vrt_prepare(vrt_ctx* ctx);
  * vrt_upload_voxels that no vrt_prepare has followed; an empty box returns VRT_OK and does nothing.  No counterpart in the
  * reference: its scene is authored before finish(), which never returns. */
 int vrt_update_voxels(vrt_ctx* ctx, const int32_t lo[3], const int32_t hi[3], const void* mat, const void* rgb, int on_device);
+/* Author a PREPARED scene from triangles: n caller-supplied triangles, in WORLD units, voxelised into the clip box [lo, hi) -- index
+ * space of vrt_upload_voxels, 0 <= lo <= hi <= grid_res per axis, as for vrt_update_voxels -- on the device.
+ * THE PAYLOAD.  voxel = r | g << 8 | b << 16 | (uint8_t)mat << 24, mat the int8 material byte as vrt_upload_voxels takes it.  A
+ * negative byte is stored as it is and its texel gets alpha 0, as everywhere.  mat == 0 is valid and CARVES: covered voxels become
+ * empty (and keep the payload's colour bytes).
+ * THE SNAP.  A world component w becomes u = (w + 1.0f) * (float)(grid_res / 2) in binary32, uncontracted (include/vrt_detmath.h), then
+ * s = (int32_t)rintf(u * 64.0f), round half to even: 64ths of a voxel.  The grid plane p(k) = (float)k * dx - 1.0f lands exactly on
+ * s = 64 k, so what Renderer.box_of_voxels returns snaps to cell boundaries exactly.  Everything after the snap is exact integer
+ * arithmetic on s; no float survives it.
+ * VALIDITY.  A triangle is INVALID if a vertex component is non-finite or outside [-VRT_TRI_MAX_COORD, VRT_TRI_MAX_COORD]; it is
+ * skipped and counted in result->invalid.  The bound keeps |s| <= (8 + 1) * 128 * 64 = 73 728 < 2^17; edge components are then < 2^18,
+ * components of a cross product of two edges < 2^37, and every projection of a vertex or of a cell's corner onto one (three terms,
+ * coordinates < 2^17) < 2^56: int64 never overflows.  reserved0 and reserved1 must be 0: on the host path this is checked before
+ * anything runs (VRT_E_INVALID), on the device path such a triangle is treated as invalid.
+ * COVERAGE.  Cell c is the closed cube [64 c_a, 64 c_a + 64]^3 in snapped units.  Triangle k COVERS cell c iff the closed triangle --
+ * the convex hull of its three snapped vertices; a segment or a point is a valid hull -- and the closed cube share a point.  This is
+ * decided by the separating-axis test in int64 on thirteen axes -- the three cube normals, the triangle's normal e0 x e1, the nine
+ * e_i x axis_a (e0 = v1 - v0, e1 = v2 - v1, e2 = v0 - v2) -- separated iff the projections are STRICTLY apart on one of them.  The
+ * test is complete for the degenerate hulls too: a segment's edges are parallel, so the nine cross products hold its direction
+ * crossed with the cube's three, which with the cube normals is the segment / box test; a point leaves the cube normals, the
+ * point-in-closed-box test; a zero axis separates nothing.  Consequence: a triangle lying exactly in a grid plane covers the cells
+ * on BOTH sides of it, a vertex on a grid vertex covers eight cells.  A caller who wants one layer offsets by half a voxel.
+ * THE RESULT.  Only cells inside the clip box exist.  Every cell of the box covered by at least one valid triangle takes the payload
+ * of the covering triangle with the HIGHEST index -- later triangles paint over earlier ones, whatever the scheduling, the batches
+ * or the host path's chunks -- and every other voxel keeps its content.  Afterwards everything vrt_prepare derives from the voxels
+ * (stored materials and colours, packed texels, every level of the occupancy pyramid, the compacted fine level, the culling box and
+ * the host's view of it) is exactly what vrt_upload_voxels(final grid) + vrt_prepare would have left; what vrt_prepare does that
+ * does not depend on voxels is left alone: the sky preparation, both sky tables, the cloud passes.  Histories and g-buffers are NOT
+ * touched (vrt_reset for a fresh accumulation).  Render launches and queries queued before the call see the old grid, those queued
+ * after it the new one.  The call synchronises with the device once (it reads the culling record back, as vrt_update_voxels does).
+ * `result` (may be NULL) receives the tight index box [lo, hi) of the WRITTEN cells -- those covered by a valid triangle, whether
+ * or not their content changed; all six zero if there is none -- their count, and the number of invalid triangles.
+ * on_device = 0: host triangles, borrowed for the call, staged in chunks (n is limited by memory only); ownership carries across
+ * chunks by the triangles' global indices.  on_device = 1: device memory (a torch tensor's data_ptr()), read on the context's stream.
+ * Scratch: 8 bytes per voxel of the box (4 of ownership, 4 of box arrays: 128 MB for a full 256^3 box) and 16 bytes per triangle of
+ * a batch of at most 2^20; grown on demand, kept by the context, freed by vrt_destroy.
+ * VRT_E_INVALID: NULL tris, lo or hi; n < 0 or n >= 2^32 - 1; lo > hi or a box outside the grid; on_device not 0 or 1; a non-zero
+ * reserved word (host path).  VRT_E_STATE: before vrt_prepare, or after a vrt_upload_voxels that no vrt_prepare has followed.
+ * n == 0 or an empty box returns VRT_OK, does nothing and zeroes the result.  Not done here: solid (interior) fill, thin
+ * 6-separating voxelisation (the reserved words leave room for a mode), textures.  No counterpart in the reference. */
+typedef struct vrt_triangle { float v0[3]; uint32_t voxel; float v1[3]; uint32_t reserved0; float v2[3]; uint32_t reserved1; } vrt_triangle;   /* 48 bytes */
+typedef struct vrt_voxelize_result { int32_t lo[3]; int32_t hi[3]; int64_t voxels; int64_t invalid; } vrt_voxelize_result;   /* 40 bytes */
+#define VRT_TRI_MAX_COORD 8.0f
+int vrt_voxelize_triangles(vrt_ctx* ctx, int64_t n, const vrt_triangle* tris, const int32_t lo[3], const int32_t hi[3],
+                           vrt_voxelize_result* result, int on_device);
 /* Ask a PREPARED scene: n caller-supplied rays, in WORLD units, through the reference's next_hit (pathtracer.py:218-244: floor plane,
  * hierarchical DDA, surface lookup) on the context's current grid, floor, voxel_edges and scene parameters, in the mode
  * vrt_set_reference_indexing selected -- a query sees what the frames see.  Ray k gets next_hit(origin, dir, t_max,

@@ -23,6 +23,12 @@ BOX_SWEEP = np.dtype([("lo", np.float32, 3), ("flags", np.uint32), ("hi", np.flo
                       ("t_max", np.float32)])
 SWEEP_HIT = np.dtype([("t", np.float32), ("kind", np.int32), ("cell", np.int32, 3), ("normal", np.float32, 3)])
 assert BOX_SWEEP.itemsize == 48 and SWEEP_HIT.itemsize == 32
+# vrt_triangle / vrt_voxelize_result (vrt_voxelize_triangles)
+TRI_MAX_COORD = 8.0
+TRIANGLE = np.dtype([("v0", np.float32, 3), ("voxel", np.uint32), ("v1", np.float32, 3), ("reserved0", np.uint32), ("v2", np.float32, 3),
+                     ("reserved1", np.uint32)])
+VOXELIZE_RESULT = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("voxels", np.int64), ("invalid", np.int64)])
+assert TRIANGLE.itemsize == 48 and VOXELIZE_RESULT.itemsize == 40
 # vrt_path_ray / vrt_radiance (vrt_trace_radiance)
 PATH_RAY = np.dtype([("origin", np.float32, 3), ("stream", np.uint32), ("dir", np.float32, 3), ("reserved", np.uint32)])
 RADIANCE = np.dtype([("rgb", np.float32, 3), ("t", np.float32)])
@@ -105,6 +111,7 @@ def declare(lib, prefix):
     sig("set_camera", C.c_int, P, C.POINTER(VrtCamera))
     sig("prepare", C.c_int, P)
     sig("update_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
+    sig("voxelize_triangles", C.c_int, P, C.c_int64, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, C.c_int)
     sig("cast_rays", C.c_int, P, C.c_int64, P, P, C.c_int)
     sig("sweep_boxes", C.c_int, P, C.c_int64, P, P, C.c_int)
     sig("trace_radiance", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)

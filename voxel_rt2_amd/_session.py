@@ -90,6 +90,32 @@ class NativeSession:
             pm, pr = mat.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p)
         self._call("update_voxels", (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), pm, pr, int(bool(on_device)))
 
+    def voxelize_triangles(self, tris, lo, hi, n=None):
+        """Triangles voxelised into the box [lo, hi) of a prepared scene (include/vrt_api.h, vrt_voxelize_triangles).  Host path: `tris`
+        is an array of _abi.TRIANGLE.  Device path: a torch tensor on the device holding the same 48-byte records (any dtype; `n`
+        triangles, by default as many as it holds), read on the session's stream.  Returns the result record, a numpy scalar of
+        _abi.VOXELIZE_RESULT (lo, hi, voxels, invalid)."""
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError("lo and hi are three coordinates each")
+        res = np.zeros(1, _abi.VOXELIZE_RESULT)
+        size = _abi.TRIANGLE.itemsize
+        if hasattr(tris, "data_ptr"):
+            if not getattr(tris, "is_cuda", False):   # (a host tensor's address must never reach the kernels as a device pointer)
+                raise ValueError("device path: the tensor must live on the device; hand host triangles over as a numpy array of _abi.TRIANGLE")
+            count = tris.numel() * tris.element_size() // size if n is None else int(n)
+            if count < 0 or tris.numel() * tris.element_size() < count * size or not tris.is_contiguous():
+                raise ValueError(f"device path: {count} triangles are a contiguous device tensor of {count * size} bytes")
+            ptr, on_device = C.c_void_p(tris.data_ptr()), 1
+        else:
+            tris = np.ascontiguousarray(tris, dtype=_abi.TRIANGLE).reshape(-1)
+            count, ptr, on_device = len(tris), tris.ctypes.data_as(C.c_void_p), 0
+        if count == 0:   # (an empty array's pointer may be NULL, which the library refuses whatever n is: it checks box and state all the same)
+            none = np.zeros(1, _abi.TRIANGLE)
+            ptr, on_device = none.ctypes.data_as(C.c_void_p), 0
+        self._call("voxelize_triangles", C.c_int64(count), ptr, (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), res.ctypes.data_as(C.c_void_p), on_device)
+        return res[0]
+
     def _query(self, entry, records, out, n, in_name, out_name, extra, noun, what):
         """The three scene queries' handling of their arrays: `records` of dtype _abi.<in_name> in, `out` of _abi.<out_name> back,
         `extra` arguments between them.  noun, what: the messages' words for an input record and for the results."""

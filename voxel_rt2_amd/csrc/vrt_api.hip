@@ -597,6 +597,67 @@ int vrt_fetch_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], void*
     HIP_TRY(sync_stream_only(c, c->stream));
     return VRT_OK;
 }
+// Voxelise triangles into the box [lo, hi) of a prepared context (vrt_voxelize.h): ownership of the box's voxels is settled batch by
+// batch on the device (launch_voxelize_batch), resolved into box arrays (launch_voxelize_resolve), and those go through launch_edit
+// like any other box -- ordered and synchronised exactly as vrt_update_voxels.  The host path stages plan_voxelize_chunk() triangles
+// at a time in the query staging buffer and resolves each chunk's owners while its triangles are still there; the device path
+// resolves once, over the caller's array.
+static_assert(sizeof(vrt_triangle) == 48 && sizeof(vrt_voxelize_result) == 40 && sizeof(VoxResult) == 40 && sizeof(VoxEntry) == 16, "record sizes of include/vrt_api.h");
+int vrt_voxelize_triangles(vrt_ctx* c, int64_t n, const vrt_triangle* tris, const int32_t lo[3], const int32_t hi[3], vrt_voxelize_result* result, int on_device) {
+    if (!c || !tris || !lo || !hi) return fail(VRT_E_INVALID, "null argument");
+    if (n < 0 || n >= 4294967295LL) return fail(VRT_E_INVALID, "n must be 0 .. 2^32 - 2");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    EditBox box;
+    for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
+    if (!edit_box_valid(box, c->cfg.grid_res)) return fail(VRT_E_INVALID, "the box must satisfy 0 <= lo <= hi <= grid_res on every axis");
+    if (!c->prepared) return fail(VRT_E_STATE, "vrt_voxelize_triangles edits a prepared grid: call vrt_prepare first (also after vrt_upload_voxels)");
+    if (!on_device)
+        for (int64_t k = 0; k < n; k++) if (tris[k].reserved0 != 0u || tris[k].reserved1 != 0u) return fail(VRT_E_INVALID, "a triangle's reserved words must be 0");
+    if (result) memset(result, 0, sizeof(*result));
+    const size_t nv = (size_t)edit_box_voxels(box);
+    if (nv == 0 || n == 0) return VRT_OK;
+    if (enter(c) != VRT_OK) return VRT_E_DEVICE;
+    const long long batch = std::min<long long>((long long)n, on_device ? plan_voxelize_batch() : plan_voxelize_chunk());
+    const size_t need = plan_voxelize_bytes(nv, (size_t)batch);
+    if (c->vox_bytes < need) {   // (hipFree waits for the device: no kernel is still using the old one)
+        HIP_TRY(dfree(c, &c->d_vox));
+        c->vox_bytes = 0;
+        HIP_TRY(dmalloc(c, &c->d_vox, need));
+        c->vox_bytes = need;
+    }
+    VoxScratch s;
+    s.owner = (uint32_t*)c->d_vox;
+    s.box_mat = (int8_t*)(c->d_vox + plan_voxelize_mat_at(nv));
+    s.box_rgb = c->d_vox + plan_voxelize_rgb_at(nv);
+    s.entries = (VoxEntry*)(c->d_vox + plan_voxelize_entries_at(nv));
+    s.heads = (unsigned long long*)(c->d_vox + plan_voxelize_heads_at(nv, (size_t)batch));
+    s.res = (VoxResult*)(s.heads + 8);
+    if (!on_device && ensure_cast_stage(c, (size_t)batch * sizeof(vrt_triangle)) != VRT_OK) return VRT_E_DEVICE;
+    c->main_dirty = true;
+    HIP_TRY(launch_voxelize_begin(c->stream, nv, s));
+    for (long long at = 0; at < (long long)n; at += batch) {   // (stream order lets batch k + 1 reuse what batch k has read)
+        const long long m = std::min(batch, (long long)n - at);
+        const vrt_triangle* d_tris = tris + at;
+        if (!on_device) {
+            HIP_TRY(hipMemcpyAsync(c->d_cast_stage, tris + at, (size_t)m * sizeof(vrt_triangle), hipMemcpyHostToDevice, c->stream));
+            d_tris = (const vrt_triangle*)c->d_cast_stage;
+        }
+        HIP_TRY(launch_voxelize_batch(c->stream, c->cfg.grid_res, c->n_cu, box, (unsigned long long)at, m, d_tris, s));
+        if (!on_device) HIP_TRY(launch_voxelize_resolve(c->stream, c->cfg.grid_res, box, (unsigned long long)at, d_tris, at + m >= (long long)n, c->d_mat, c->d_rgb, s));
+    }
+    if (on_device) HIP_TRY(launch_voxelize_resolve(c->stream, c->cfg.grid_res, box, 0ULL, tris, true, c->d_mat, c->d_rgb, s));
+    HIP_TRY(launch_edit(c->stream, c->cfg.grid_res, box, s.box_mat, s.box_rgb, c->d_mat, c->d_rgb, c->d_grid, c->d_l0, c->d_l1, c->d_l2, c->d_l3,
+                        c->d_l0c, c->d_l0c_base, c->d_cull));
+    VoxResult r;
+    if (result) HIP_TRY(hipMemcpyAsync(&r, s.res, sizeof(r), hipMemcpyDeviceToHost, c->stream));   // (waited for by the one synchronisation below)
+    const int rc = read_cull_record(c);   // (the wait also ends the loan of the host array)
+    if (rc == VRT_OK && result) {
+        result->voxels = (int64_t)r.voxels;
+        result->invalid = (int64_t)r.invalid;
+        if (r.voxels != 0ULL) for (int a = 0; a < 3; a++) { result->lo[a] = r.lo[a]; result->hi[a] = r.hi[a] + 1; }
+    }
+    return rc;
+}
 int vrt_sky_accumulate_clouds(vrt_ctx* c, int max_samples) {
     if (!c || max_samples <= 0) return fail(VRT_E_INVALID, "bad argument");
     if (!c->prepared || c->scene.use_physical_sky != 1) return fail(VRT_E_STATE, "needs vrt_prepare with use_physical_sky");

@@ -15,6 +15,7 @@
 #include "vrt_edit.h"
 #include "vrt_cast.h"
 #include "vrt_sweep.h"
+#include "vrt_voxelize.h"
 #include "vrt_query.h"
 #include "vrt_denoise.h"
 
@@ -61,6 +62,21 @@ hipError_t launch_fetch_voxels(hipStream_t st, int grid_res, const EditBox& box,
 // the grid n_cu x the kernel's residency at most (plan_sweep_blocks).  Of sc the two finest pyramid levels and the culling box are read.
 hipError_t launch_sweep_boxes(hipStream_t st, int grid_res, int n_cu, float floor_height, const SceneData& sc, long long n, const vrt_box_sweep* boxes,
                               vrt_sweep_hit* hits);
+// vrt_voxelize_triangles (vrt_voxelize.h).  The context's scratch, cut up by plan_voxelize_*: one ownership word per voxel of the clip
+// box, the box arrays launch_edit takes, the item-list entries of a batch, heads[0] the set-up pass's counter (entries << 40 | items),
+// heads[1] the rasterise pass's work head, and the result record (lo = INT32_MAX / hi = INT32_MIN while nothing is written; hi INCLUSIVE).
+struct VoxResult { int32_t lo[3], hi[3]; unsigned long long voxels, invalid; };
+struct VoxScratch { uint32_t* owner; int8_t* box_mat; uint8_t* box_rgb; VoxEntry* entries; unsigned long long* heads; VoxResult* res; };
+// ownership zeroed over the box's nv voxels, the result record opened
+hipError_t launch_voxelize_begin(hipStream_t st, size_t nv, const VoxScratch& s);
+// one batch of m <= plan_voxelize_batch() triangles (device memory), global numbers base .. base + m - 1: k_vox_setup, a lane a triangle,
+// counts the items and writes the entries; k_vox_raster, a wave an item, raises the ownership words
+hipError_t launch_voxelize_batch(hipStream_t st, int grid_res, int n_cu, const EditBox& clip, unsigned long long base, long long m, const vrt_triangle* tris,
+                                 const VoxScratch& s);
+// k_vox_resolve, a lane a few voxels of the box: payloads of the owners among tris (global numbers from base), and with `final` the grid's
+// stored voxels where nobody owns one, the count and the tight box
+hipError_t launch_voxelize_resolve(hipStream_t st, int grid_res, const EditBox& clip, unsigned long long base, const vrt_triangle* tris, bool final,
+                                   const int8_t* mat, const uint8_t* rgb, const VoxScratch& s);
 // A sampled query Q (vrt_query.h: RadianceQuery, SensorQuery, ProbeQuery): samples [s0, s0 + count) of n records (device memory) worked into
 // plane[n * count] by the query's item kernel (k_trace_radiance, k_gather_irradiance, k_gather_probes) and folded into out[n] (k_fold_query).
 // n * count <= Q::max_items; staged / oob as for launch_cast_rays; head: one word of device memory, the launch's work counter.

@@ -1674,6 +1674,166 @@ hipError_t launch_sweep_boxes(hipStream_t st, int grid_res, int n_cu, float floo
     return hipSuccess;
 }
 
+// ---- vrt_voxelize_triangles: caller-supplied triangles voxelised into a box (vrt_voxelize.h holds the arithmetic) -----------------------
+// Three kernels around an ownership buffer of one word per voxel of the clip box; launch_edit then does what it does for any box.
+//   k_vox_setup    a LANE a triangle: the gate, the snap, the 16^3 cells its clipped bounds touch = its work items.  A wave sums its
+//                  lanes' counts with a shuffle scan and takes entries and item numbers for all of them with ONE 64-bit atomic
+//                  (entries << 40 | items), so entries come out ordered by their first item; lane 0 also counts the invalid ones.
+//   k_vox_raster   a WAVE an item.  Waves reserve VRT_VOX_ITEMS_PER_GRAB consecutive items from a work head until it is exhausted, find
+//                  the first one's triangle by binary search and walk on from there; the set-up (thirteen axes) is redone only when
+//                  the triangle changes.  An item: the 16^3 cell is tested whole (wave-uniform), its 64 bricks by the 64 lanes, one
+//                  each, and for every brick of the ballot the 64 lanes test its 64 voxels, one each; a covered voxel's word is
+//                  raised to the triangle's global number + 1 with atomicMax, which is what makes the outcome independent of any of
+//                  this.  A triangle spanning the grid is 4096 items in 1024 grabs: no wave walks it alone.
+//   k_vox_resolve  a lane a few voxels of the box, z fastest like k_edit_store: the owner's payload, or the grid's stored voxel, into the
+//                  box arrays; the last batch's also counts the written voxels and bounds them, reduced over the workgroup first.
+// Plain C++ and vector memory operations throughout; the indices a wave branches on are made wave-uniform with readfirstlane so
+// that triangle and entry loads are scalar loads.
+#define VRT_VOX_ITEM_MASK ((1ULL << 40) - 1ULL)
+__global__ __launch_bounds__(256) void k_vox_begin(VoxResult* res) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        for (int a = 0; a < 3; a++) { res->lo[a] = 0x7fffffff; res->hi[a] = (int32_t)0x80000000; }
+        res->voxels = 0ULL; res->invalid = 0ULL;
+    }
+}
+__global__ __launch_bounds__(256) void k_vox_setup(int G, EditBox clip, long long m, const vrt_triangle* __restrict__ tris, unsigned long long* __restrict__ heads,
+                                                   VoxEntry* __restrict__ entries, VoxResult* __restrict__ res) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    bool valid = true;
+    uint32_t items = 0u;
+    if (i < m) items = vox_tri_items(tris[i], G, clip, valid);
+    const unsigned long long has = __ballot(items != 0u), bad = __ballot(!valid);
+    unsigned long long incl = items;
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    const unsigned long long total = __shfl(incl, 63, 64);
+    unsigned long long old = 0ULL;
+    if (lane == 0) {
+        if (has) old = atomicAdd(&heads[0], ((unsigned long long)__popcll(has) << 40) + total);
+        if (bad) atomicAdd(&res->invalid, (unsigned long long)__popcll(bad));
+    }
+    old = __shfl(old, 0, 64);
+    if (items != 0u) {   // (slot < m: a batch has no more entries than triangles)
+        VoxEntry e;
+        e.first = (old & VRT_VOX_ITEM_MASK) + incl - items;
+        e.tri = (uint32_t)i;
+        e.items = items;
+        entries[(old >> 40) + (unsigned long long)__popcll(has & ((1ULL << lane) - 1ULL))] = e;
+    }
+}
+__global__ __launch_bounds__(256) void k_vox_raster(int G, EditBox clip, unsigned long long base, const vrt_triangle* __restrict__ tris,
+                                                    unsigned long long* __restrict__ heads, const VoxEntry* __restrict__ entries, uint32_t* __restrict__ owner) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long h = heads[0], total = h & VRT_VOX_ITEM_MASK;
+    const long long n_entries = (long long)(h >> 40);
+    for (;;) {
+        unsigned long long g = 0ULL;
+        if (lane == 0) g = atomicAdd(&heads[1], (unsigned long long)VRT_VOX_ITEMS_PER_GRAB);
+        g = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(g >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)g);
+        if (g >= total) return;
+        const unsigned long long g1 = g + VRT_VOX_ITEMS_PER_GRAB < total ? g + VRT_VOX_ITEMS_PER_GRAB : total;
+        long long e = vox_find_entry(entries, n_entries, g);
+        while (g < g1 && e < n_entries) {   // (e < n_entries always: every item below `total` belongs to an entry)
+            const VoxEntry en = entries[e++];
+            VoxTri s;
+            vox_setup(tris[en.tri], G, s);
+            const EditCells cells = vox_cells(s, clip, 4), bricks = vox_cells(s, clip, 2);
+            const uint32_t mine = (uint32_t)(base + en.tri + 1ULL);
+            const unsigned long long end = en.first + en.items < g1 ? en.first + en.items : g1;
+            for (; g < end; g++) {
+                int cx, cy, cz;
+                edit_cell(cells, (int)(g - en.first), cx, cy, cz);
+                if (!vox_cube(s, cx, cy, cz, 4)) continue;
+                unsigned long long todo = __ballot(vox_lane_brick(s, bricks, cx, cy, cz, lane));
+                while (todo) {
+                    const int brick = __ffsll((long long)todo) - 1;
+                    todo &= todo - 1ULL;
+                    const int at = vox_lane_voxel(s, clip, cx, cy, cz, brick, lane);   // (-1, or inside the box: vox_in_box)
+                    if (at >= 0) atomicMax(&owner[at], mine);
+                }
+            }
+        }
+    }
+}
+// VRT_VOX_RESOLVE_PER_THREAD voxels a thread, a workgroup's 256 x that many consecutive voxels taken 256 apart so that a wave's loads and
+// stores stay neighbours.  Count and bounds are summed per thread, then over the wave with shuffles, then over the workgroup's four waves
+// through LDS, and one thread a workgroup issues the atomics -- the bounds' only where they would move the record (a plain load first):
+// one atomic per wave on seven words that every wave shares made the written voxels, not the box, set this kernel's time.
+#define VRT_VOX_RESOLVE_PER_THREAD 8
+__global__ __launch_bounds__(256) void k_vox_resolve(int G, EditBox clip, const uint32_t* __restrict__ owner, unsigned long long base,
+                                                     const vrt_triangle* __restrict__ tris, int final, const int8_t* __restrict__ mat,
+                                                     const uint8_t* __restrict__ rgb, int8_t* __restrict__ box_mat, uint8_t* __restrict__ box_rgb,
+                                                     VoxResult* res) {
+    __shared__ int part[4][7];
+    const int nv = edit_box_voxels(clip), first = blockIdx.x * (256 * VRT_VOX_RESOLVE_PER_THREAD) + threadIdx.x;
+    int count = 0, lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int32_t)0x80000000, (int32_t)0x80000000, (int32_t)0x80000000};
+    for (int k = 0; k < VRT_VOX_RESOLVE_PER_THREAD; k++) {
+        const int i = first + k * 256;
+        if (i < nv && vox_resolve_voxel(clip, G, i, owner, base, tris, final != 0, mat, rgb, box_mat, box_rgb) && final) {
+            int c[3];
+            edit_box_voxel(clip, i, c[0], c[1], c[2]);
+            count++;
+            for (int a = 0; a < 3; a++) { lo[a] = c[a] < lo[a] ? c[a] : lo[a]; hi[a] = c[a] > hi[a] ? c[a] : hi[a]; }
+        }
+    }
+    if (!final) return;
+    for (int d = 32; d >= 1; d >>= 1) {
+        count += __shfl_xor(count, d, 64);
+        for (int a = 0; a < 3; a++) {
+            const int l = __shfl_xor(lo[a], d, 64), u = __shfl_xor(hi[a], d, 64);
+            lo[a] = l < lo[a] ? l : lo[a];
+            hi[a] = u > hi[a] ? u : hi[a];
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        int* p = part[threadIdx.x >> 6];
+        p[0] = count;
+        for (int a = 0; a < 3; a++) { p[1 + a] = lo[a]; p[4 + a] = hi[a]; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) {
+            count += part[w][0];
+            for (int a = 0; a < 3; a++) { lo[a] = part[w][1 + a] < lo[a] ? part[w][1 + a] : lo[a]; hi[a] = part[w][4 + a] > hi[a] ? part[w][4 + a] : hi[a]; }
+        }
+        if (count) {
+            atomicAdd(&res->voxels, (unsigned long long)count);
+            for (int a = 0; a < 3; a++) {   // (a stale load only costs an atomic that changes nothing)
+                if (lo[a] < *(volatile int32_t*)&res->lo[a]) atomicMin(&res->lo[a], lo[a]);
+                if (hi[a] > *(volatile int32_t*)&res->hi[a]) atomicMax(&res->hi[a], hi[a]);
+            }
+        }
+    }
+}
+
+hipError_t launch_voxelize_begin(hipStream_t st, size_t nv, const VoxScratch& s) {
+    hipError_t e = hipMemsetAsync(s.owner, 0, 4 * nv, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_vox_begin, dim3(1), dim3(64), 0, st, s.res);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_voxelize_batch(hipStream_t st, int grid_res, int n_cu, const EditBox& clip, unsigned long long base, long long m, const vrt_triangle* tris,
+                                 const VoxScratch& s) {
+    hipError_t e = hipMemsetAsync(s.heads, 0, 16, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_vox_setup, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, grid_res, clip, m, tris, s.heads, s.entries, s.res);
+    VRT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_vox_raster, dim3(plan_voxelize_blocks(n_cu)), dim3(256), 0, st, grid_res, clip, base, tris, s.heads, (const VoxEntry*)s.entries, s.owner);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_voxelize_resolve(hipStream_t st, int grid_res, const EditBox& clip, unsigned long long base, const vrt_triangle* tris, bool final,
+                                   const int8_t* mat, const uint8_t* rgb, const VoxScratch& s) {
+    hipLaunchKernelGGL(k_vox_resolve, dim3((edit_box_voxels(clip) + 256 * VRT_VOX_RESOLVE_PER_THREAD - 1) / (256 * VRT_VOX_RESOLVE_PER_THREAD)), dim3(256), 0, st, grid_res, clip, (const uint32_t*)s.owner, base, tris,
+                       final ? 1 : 0, mat, rgb, s.box_mat, s.box_rgb, s.res);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
 // A sampled query's chunk -- samples [s0, s0 + count) of n records -- worked into `plane` by the query's item kernel and folded into `out`.
 // n * count is at most Q::max_items (plan_query_chunk); `head`: the launch's work counter, zeroed here on the stream.
 template <class Q>

@@ -241,6 +241,26 @@ static inline int plan_sweep_blocks(long long n, int n_cu, int blocks_per_cu) {
     return (int)(want < fit ? want : fit);
 }
 
+// ---- vrt_voxelize_triangles ----------------------------------------------------------------------------------------------------------
+// Triangles a host-path call stages at a time (48 bytes of device memory each), and triangles one set-up + rasterise pair of launches
+// takes on either path (16 bytes of item-list entry each): n is limited by the caller's memory only.
+static inline long long plan_voxelize_chunk() { return 1 << 18; }
+static inline long long plan_voxelize_batch() { return 1 << 20; }
+// Items (16^3 cells of a triangle, vrt_voxelize.h) a wave reserves per atomic on the work head: few enough that the 4096 items of a
+// grid-spanning triangle spread over 1024 waves (an item through the triangle's plane is some twenty bricks of 64 voxel tests: a grab
+// of them is the tail a lone large triangle adds to a call), enough that the search for an item's triangle is paid once per four items.
+#define VRT_VOX_ITEMS_PER_GRAB 4
+// Workgroups of the rasterise launch: a persistent grid of four waves a workgroup, eight workgroups a CU -- the item count is known
+// on the device only, and a wave that finds the head exhausted ends at once.
+static inline int plan_voxelize_blocks(int n_cu) { return (n_cu > 0 ? n_cu : 1) * 8; }
+// Bytes of the context's voxeliser scratch for a box of nv voxels and batches of at most `batch` triangles: ownership words, the box
+// arrays handed to launch_edit (materials padded to 256 bytes), the item-list entries, the two heads and the result record.
+static inline size_t plan_voxelize_mat_at(size_t nv) { return 4 * nv; }
+static inline size_t plan_voxelize_rgb_at(size_t nv) { return plan_voxelize_mat_at(nv) + ((nv + 255) & ~(size_t)255); }
+static inline size_t plan_voxelize_entries_at(size_t nv) { return (plan_voxelize_rgb_at(nv) + 3 * nv + 255) & ~(size_t)255; }
+static inline size_t plan_voxelize_heads_at(size_t nv, size_t batch) { return plan_voxelize_entries_at(nv) + 16 * batch; }
+static inline size_t plan_voxelize_bytes(size_t nv, size_t batch) { return plan_voxelize_heads_at(nv, batch) + 256; }
+
 // ---- the sampled queries: vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes (vrt_query.h) ----------------------------------------------------
 // The work item is (record, sample) -- (ray, sample) or (sensor, sample); a finished item leaves its value in a scratch plane -- 12 bytes
 // an item for a radiance, a 32-byte vrt_irradiance record of four terms for a sensor -- which k_fold_query sums per record in sample

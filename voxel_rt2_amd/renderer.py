@@ -373,6 +373,56 @@ class Renderer(VoxelStore):
         hi = np.asarray(hi_idx, np.int64).astype(np.float32) * dx - np.float32(1.0)
         return lo, hi
 
+    # -- authoring from triangles (include/vrt_api.h, vrt_voxelize_triangles; no counterpart in the reference) ------------------------
+    def voxelize_triangles(self, vertices, faces=None, color=(255, 255, 255), mat=1, lo=None, hi=None, reset=True):
+        """Voxelise triangles (world units) into the box [lo, hi) of array indices -- by default the whole grid -- of the scene as
+        prepare_data() / update_voxels() left it, on the device: every voxel whose closed cube a triangle touches takes that triangle's
+        colour and material, later triangles painting over earlier ones; mat = 0 carves.  vertices: (n, 3, 3), or (V, 3) with faces
+        (F, 3) of vertex indices; color (r, g, b in 0..255) and mat (the int8 material byte): one value or one per triangle.  A torch
+        tensor on the device holding _abi.TRIANGLE records is handed over as it is (faces, color and mat are then not looked at).
+        Voxels written with set_voxel and not yet sent go first.  Returns the result record (lo, hi: the tight box of the written
+        voxels; voxels; invalid) and brings voxel_material / voxel_color in step over that box (sync_voxels_from_device).  reset:
+        start a fresh accumulation."""
+        if not getattr(self, "_prepared", False):
+            raise NativeError("voxelize_triangles edits a prepared scene: call prepare_data() first")
+        if self._voxels_dirty:
+            self.update_voxels(reset=False)
+        self._push()
+        g = self.voxel_grid_res
+        lo, hi = ((0, 0, 0) if lo is None else lo), ((g, g, g) if hi is None else hi)
+        if hasattr(vertices, "data_ptr"):
+            tris = vertices
+        else:
+            v = np.asarray(vertices, np.float32)
+            if faces is not None:
+                v = v.reshape(-1, 3)[np.asarray(faces, np.int64).reshape(-1, 3)]
+            v = v.reshape(-1, 3, 3)
+            tris = np.zeros(len(v), _abi.TRIANGLE)
+            tris["v0"], tris["v1"], tris["v2"] = v[:, 0], v[:, 1], v[:, 2]
+            c = np.broadcast_to(np.asarray(color, np.int64).reshape(-1, 3), (len(v), 3)).astype(np.uint32) & 0xFF
+            m = np.broadcast_to(np.asarray(mat, np.int64).reshape(-1), (len(v),)).astype(np.int8).view(np.uint8).astype(np.uint32)
+            tris["voxel"] = c[:, 0] | c[:, 1] << 8 | c[:, 2] << 16 | m << 24
+        res = self._s.voxelize_triangles(tris, lo, hi)
+        if res["voxels"]:
+            self.sync_voxels_from_device(tuple(int(x) for x in res["lo"]), tuple(int(x) for x in res["hi"]))
+        if reset:
+            self.reset_framebuffer()
+        return res
+
+    def mesh_box(self, vertices):
+        """The box [lo, hi) of array indices that encloses every voxel a mesh with these vertices (world units, any shape (..., 3)) can
+        cover, clamped to the grid: what voxelize_triangles takes as lo, hi.  A vertex on a grid plane counts the cells on both sides.
+        Vertices with a non-finite component are left out (the library skips their triangles); with none left the box is empty."""
+        g = self.voxel_grid_res
+        v = np.asarray(vertices, np.float32).reshape(-1, 3)
+        v = np.clip(v[np.isfinite(v).all(axis=1)], -_abi.TRI_MAX_COORD, _abi.TRI_MAX_COORD)
+        if len(v) == 0:
+            return (0, 0, 0), (0, 0, 0)
+        s = np.rint((v + np.float32(1.0)) * np.float32(g // 2) * np.float32(64.0)).astype(np.int64)   # the library's snap: 64ths of a voxel
+        lo = np.clip((s.min(axis=0) - 1) >> 6, 0, g)
+        hi = np.clip((s.max(axis=0) >> 6) + 1, 0, g)
+        return tuple(int(x) for x in lo), tuple(int(x) for x in np.maximum(hi, lo))
+
     def pick_ray(self, u, v):
         """(origin, direction) of the ray through the centre of pixel (u, v), v = 0 at the bottom: get_cast_dir (pathtracer.py:293-312)
         without the TAA jitter, statement by statement in float32, from the matrices and the position the renderer was last given."""
