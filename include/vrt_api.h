@@ -191,13 +191,57 @@ int vrt_update_voxels(vrt_ctx* ctx, const int32_t lo[3], const int32_t hi[3], co
  * a batch of at most 2^20; grown on demand, kept by the context, freed by vrt_destroy.
  * VRT_E_INVALID: NULL tris, lo or hi; n < 0 or n >= 2^32 - 1; lo > hi or a box outside the grid; on_device not 0 or 1; a non-zero
  * reserved word (host path).  VRT_E_STATE: before vrt_prepare, or after a vrt_upload_voxels that no vrt_prepare has followed.
- * n == 0 or an empty box returns VRT_OK, does nothing and zeroes the result.  Not done here: solid (interior) fill, thin
- * 6-separating voxelisation (the reserved words leave room for a mode), textures.  No counterpart in the reference. */
+ * n == 0 or an empty box returns VRT_OK, does nothing and zeroes the result.  Solid (interior) fill is vrt_fill_triangles, below.
+ * Not done here: thin 6-separating voxelisation (the reserved words leave room for a mode), textures.  No counterpart in the
+ * reference. */
 typedef struct vrt_triangle { float v0[3]; uint32_t voxel; float v1[3]; uint32_t reserved0; float v2[3]; uint32_t reserved1; } vrt_triangle;   /* 48 bytes */
 typedef struct vrt_voxelize_result { int32_t lo[3]; int32_t hi[3]; int64_t voxels; int64_t invalid; } vrt_voxelize_result;   /* 40 bytes */
 #define VRT_TRI_MAX_COORD 8.0f
 int vrt_voxelize_triangles(vrt_ctx* ctx, int64_t n, const vrt_triangle* tris, const int32_t lo[3], const int32_t hi[3],
                            vrt_voxelize_result* result, int on_device);
+/* Author SOLIDS from triangles: the INSIDE of the n caller-supplied triangles, read as a closed mesh, filled with one payload inside
+ * the clip box [lo, hi) of a prepared context, on the device.  vrt_voxelize_triangles writes a surface shell; this writes the volume.
+ * TRIANGLES, SNAP, VALIDITY.  The same vrt_triangle records -- one device array serves both calls -- the same snap and the same
+ * validity rule, reserved words included (host path: VRT_E_INVALID before anything runs; device path: the triangle is invalid).  An
+ * invalid triangle is skipped and counted in result->invalid.  The triangles' own `voxel` words are ignored.
+ * THE PAYLOAD.  `voxel` = r | g << 8 | b << 16 | (uint8_t)mat << 24 is the single payload of the call.  mat == 0 CARVES: inside cells
+ * become empty.  A negative material byte is stored as it is (its texel gets alpha 0, as everywhere).
+ * INSIDE.  Everything after the snap is exact integer arithmetic.  Cell c has the centre q = (64 c_x + 32, 64 c_y + 32, 64 c_z + 32)
+ * in snapped units.  Cell c of the clip box is INSIDE iff an odd number of valid triangles CROSS BELOW it.  Geometrically: triangle k
+ * crosses below c iff the vertical line (along z) through the point q + (eps, eps^2, eps^3), eps positive and infinitesimally small,
+ * meets the triangle strictly below that point.  The perturbed point is generic -- it lies on no edge's projected line and on no
+ * triangle's plane -- so nothing is ever "on" anything.  For any set of triangles that is closed (every edge shared an even number of
+ * times) INSIDE is the ordinary parity of that point, whatever the triangles' orientation.  In integers, which is what is computed:
+ *   e0 = v1 - v0, e1 = v2 - v1, n = e0 x e1 (as for COVERAGE above), sigma = sign(n_z).  n_z == 0: the triangle is edge-on or
+ *   degenerate seen along z and crosses nothing.
+ *   For each directed edge p -> r of v0 -> v1, v1 -> v2, v2 -> v0, with d = r - p: E = d_x (q_y - p_y) - d_y (q_x - p_x), and E' the
+ *   sign of the first non-zero of (E, -d_y, d_x).  The COLUMN (c_x, c_y) is in the triangle iff sigma E' > 0 for all three edges.
+ *   F = n . (q - v0), and F' the sign of the first non-zero of (F, n_x, n_y, n_z).
+ *   Triangle k crosses below c iff the column is in and sigma F' > 0.
+ * Consequences: along z a solid is the half-open interval [entry, exit) of cell centres -- a face through cell centres takes the
+ * cells on its upper side in and leaves those of the face above it out; across a shared edge or vertex exactly one triangle owns a
+ * column; two solids that share a face tile without gap or overlap; a duplicated triangle cancels itself; overlapping closed meshes
+ * XOR -- nested spheres give a hollow ball; an OPEN mesh has a defined result (every cell above an odd number of its triangles),
+ * which depends on the z axis.
+ * Headroom: |q_a - v_a| < 2^17 and |d_a| < 2^18, so |E| < 2^36; |n_a| < 2^37, so |F| < 3 * 2^54 < 2^56: int64 never overflows.
+ * THE CLIP BOX IS EXACT.  Only cells inside [lo, hi) are written.  A triangle below the box still counts for every cell of its
+ * column; a triangle above or beside the box counts for none.  So filling a box in two halves equals filling it whole.
+ * THE RESULT.  Every INSIDE cell of the box takes `voxel`; every other voxel keeps its content.  Afterwards everything vrt_prepare
+ * derives from the voxels is exactly what vrt_upload_voxels(final grid) + vrt_prepare would have left, as for vrt_voxelize_triangles;
+ * histories and g-buffers are NOT touched; launches and queries queued before the call see the old grid, those after it the new one;
+ * the call synchronises with the device once.  `result` (may be NULL) receives the tight index box [lo, hi) of the INSIDE cells (all
+ * six zero if there is none), their count, and the number of invalid triangles.
+ * on_device = 0: host triangles, borrowed for the call, staged in chunks; = 1: device memory, read on the context's stream.  Neither
+ * the chunks nor the scheduling can change a bit: toggles XOR.
+ * Scratch: one toggle bit per voxel of the box (a column along z rounded up to whole 32-bit words), the box arrays (4 bytes a voxel)
+ * and 16 bytes per triangle of a batch of at most 2^20; it shares vrt_voxelize_triangles' allocation, grown on demand, kept by the
+ * context, freed by vrt_destroy.
+ * Errors and empty cases are exactly vrt_voxelize_triangles': VRT_E_INVALID: NULL tris, lo or hi; n < 0 or n >= 2^32 - 1; lo > hi or a
+ * box outside the grid; on_device not 0 or 1; a non-zero reserved word (host path).  VRT_E_STATE: before vrt_prepare, or after a
+ * vrt_upload_voxels that no vrt_prepare has followed.  n == 0 or an empty box returns VRT_OK, does nothing and zeroes the result.
+ * Not done here: a fill axis other than z, thin voxelisation, textures.  No counterpart in the reference. */
+int vrt_fill_triangles(vrt_ctx* ctx, int64_t n, const vrt_triangle* tris, const int32_t lo[3], const int32_t hi[3],
+                       uint32_t voxel, vrt_voxelize_result* result, int on_device);
 /* Ask a PREPARED scene: n caller-supplied rays, in WORLD units, through the reference's next_hit (pathtracer.py:218-244: floor plane,
  * hierarchical DDA, surface lookup) on the context's current grid, floor, voxel_edges and scene parameters, in the mode
  * vrt_set_reference_indexing selected -- a query sees what the frames see.  Ray k gets next_hit(origin, dir, t_max,

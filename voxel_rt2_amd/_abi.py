@@ -112,6 +112,7 @@ def declare(lib, prefix):
     sig("prepare", C.c_int, P)
     sig("update_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
     sig("voxelize_triangles", C.c_int, P, C.c_int64, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, C.c_int)
+    sig("fill_triangles", C.c_int, P, C.c_int64, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, P, C.c_int)
     sig("cast_rays", C.c_int, P, C.c_int64, P, P, C.c_int)
     sig("sweep_boxes", C.c_int, P, C.c_int64, P, P, C.c_int)
     sig("trace_radiance", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)

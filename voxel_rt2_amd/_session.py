@@ -95,6 +95,17 @@ class NativeSession:
         is an array of _abi.TRIANGLE.  Device path: a torch tensor on the device holding the same 48-byte records (any dtype; `n`
         triangles, by default as many as it holds), read on the session's stream.  Returns the result record, a numpy scalar of
         _abi.VOXELIZE_RESULT (lo, hi, voxels, invalid)."""
+        return self._triangles("voxelize_triangles", tris, lo, hi, n)
+
+    def fill_triangles(self, tris, lo, hi, voxel, n=None):
+        """The inside of a triangle mesh filled with the payload `voxel` (r | g << 8 | b << 16 | material byte << 24; material 0 carves)
+        in the box [lo, hi) of a prepared scene (include/vrt_api.h, vrt_fill_triangles).  `tris`, `n` and the returned record are
+        voxelize_triangles': host arrays of _abi.TRIANGLE or a device tensor of the same records, taken without a copy; the record
+        counts and bounds the inside cells."""
+        return self._triangles("fill_triangles", tris, lo, hi, n, C.c_uint32(int(voxel) & 0xFFFFFFFF))
+
+    def _triangles(self, entry, tris, lo, hi, n, *extra):
+        """The two triangle entry points' handling of their arrays; `extra`: arguments between the box and the result record."""
         lo, hi = [int(v) for v in lo], [int(v) for v in hi]
         if len(lo) != 3 or len(hi) != 3:
             raise ValueError("lo and hi are three coordinates each")
@@ -113,7 +124,7 @@ class NativeSession:
         if count == 0:   # (an empty array's pointer may be NULL, which the library refuses whatever n is: it checks box and state all the same)
             none = np.zeros(1, _abi.TRIANGLE)
             ptr, on_device = none.ctypes.data_as(C.c_void_p), 0
-        self._call("voxelize_triangles", C.c_int64(count), ptr, (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), res.ctypes.data_as(C.c_void_p), on_device)
+        self._call(entry, C.c_int64(count), ptr, (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), *extra, res.ctypes.data_as(C.c_void_p), on_device)
         return res[0]
 
     def _query(self, entry, records, out, n, in_name, out_name, extra, noun, what):

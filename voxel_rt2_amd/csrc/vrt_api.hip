@@ -658,6 +658,66 @@ int vrt_voxelize_triangles(vrt_ctx* c, int64_t n, const vrt_triangle* tris, cons
     }
     return rc;
 }
+// Fill the inside of a triangle mesh into the box [lo, hi) of a prepared context (vrt_fill.h): every batch toggles one bit per owned
+// column in a bitmap of the box (launch_fill_batch), one resolve turns the bitmap into box arrays (launch_fill_resolve), and those go
+// through launch_edit -- checks, ordering and the one synchronisation are vrt_voxelize_triangles'.  XOR commutes, so the host path's
+// chunks need no resolve of their own: they are staged one after the other and toggle into the same bitmap.
+int vrt_fill_triangles(vrt_ctx* c, int64_t n, const vrt_triangle* tris, const int32_t lo[3], const int32_t hi[3], uint32_t voxel, vrt_voxelize_result* result,
+                       int on_device) {
+    if (!c || !tris || !lo || !hi) return fail(VRT_E_INVALID, "null argument");
+    if (n < 0 || n >= 4294967295LL) return fail(VRT_E_INVALID, "n must be 0 .. 2^32 - 2");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    EditBox box;
+    for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
+    if (!edit_box_valid(box, c->cfg.grid_res)) return fail(VRT_E_INVALID, "the box must satisfy 0 <= lo <= hi <= grid_res on every axis");
+    if (!c->prepared) return fail(VRT_E_STATE, "vrt_fill_triangles edits a prepared grid: call vrt_prepare first (also after vrt_upload_voxels)");
+    if (!on_device)
+        for (int64_t k = 0; k < n; k++) if (tris[k].reserved0 != 0u || tris[k].reserved1 != 0u) return fail(VRT_E_INVALID, "a triangle's reserved words must be 0");
+    if (result) memset(result, 0, sizeof(*result));
+    const size_t nv = (size_t)edit_box_voxels(box);
+    if (nv == 0 || n == 0) return VRT_OK;
+    if (enter(c) != VRT_OK) return VRT_E_DEVICE;
+    const size_t words = (size_t)fill_words(box);
+    const long long batch = std::min<long long>((long long)n, on_device ? plan_voxelize_batch() : plan_voxelize_chunk());
+    const size_t need = plan_fill_bytes(words, nv, (size_t)batch);
+    if (c->vox_bytes < need) {   // (hipFree waits for the device: no kernel is still using the old one)
+        HIP_TRY(dfree(c, &c->d_vox));
+        c->vox_bytes = 0;
+        HIP_TRY(dmalloc(c, &c->d_vox, need));
+        c->vox_bytes = need;
+    }
+    FillScratch s;
+    s.toggles = (uint32_t*)c->d_vox;
+    s.box_mat = (int8_t*)(c->d_vox + plan_fill_mat_at(words));
+    s.box_rgb = c->d_vox + plan_fill_rgb_at(words, nv);
+    s.entries = (VoxEntry*)(c->d_vox + plan_fill_entries_at(words, nv));
+    s.heads = (unsigned long long*)(c->d_vox + plan_fill_heads_at(words, nv, (size_t)batch));
+    s.res = (VoxResult*)(s.heads + 8);
+    if (!on_device && ensure_cast_stage(c, (size_t)batch * sizeof(vrt_triangle)) != VRT_OK) return VRT_E_DEVICE;
+    c->main_dirty = true;
+    HIP_TRY(launch_fill_begin(c->stream, box, s));
+    for (long long at = 0; at < (long long)n; at += batch) {   // (stream order lets batch k + 1 reuse what batch k has read)
+        const long long m = std::min(batch, (long long)n - at);
+        const vrt_triangle* d_tris = tris + at;
+        if (!on_device) {
+            HIP_TRY(hipMemcpyAsync(c->d_cast_stage, tris + at, (size_t)m * sizeof(vrt_triangle), hipMemcpyHostToDevice, c->stream));
+            d_tris = (const vrt_triangle*)c->d_cast_stage;
+        }
+        HIP_TRY(launch_fill_batch(c->stream, c->cfg.grid_res, c->n_cu, box, m, d_tris, s));
+    }
+    HIP_TRY(launch_fill_resolve(c->stream, c->cfg.grid_res, box, voxel, c->d_mat, c->d_rgb, s));
+    HIP_TRY(launch_edit(c->stream, c->cfg.grid_res, box, s.box_mat, s.box_rgb, c->d_mat, c->d_rgb, c->d_grid, c->d_l0, c->d_l1, c->d_l2, c->d_l3,
+                        c->d_l0c, c->d_l0c_base, c->d_cull));
+    VoxResult r;
+    if (result) HIP_TRY(hipMemcpyAsync(&r, s.res, sizeof(r), hipMemcpyDeviceToHost, c->stream));   // (waited for by the one synchronisation below)
+    const int rc = read_cull_record(c);   // (the wait also ends the loan of the host array)
+    if (rc == VRT_OK && result) {
+        result->voxels = (int64_t)r.voxels;
+        result->invalid = (int64_t)r.invalid;
+        if (r.voxels != 0ULL) for (int a = 0; a < 3; a++) { result->lo[a] = r.lo[a]; result->hi[a] = r.hi[a] + 1; }
+    }
+    return rc;
+}
 int vrt_sky_accumulate_clouds(vrt_ctx* c, int max_samples) {
     if (!c || max_samples <= 0) return fail(VRT_E_INVALID, "bad argument");
     if (!c->prepared || c->scene.use_physical_sky != 1) return fail(VRT_E_STATE, "needs vrt_prepare with use_physical_sky");

@@ -16,6 +16,7 @@
 #include "vrt_cast.h"
 #include "vrt_sweep.h"
 #include "vrt_voxelize.h"
+#include "vrt_fill.h"
 #include "vrt_query.h"
 #include "vrt_denoise.h"
 
@@ -77,6 +78,17 @@ hipError_t launch_voxelize_batch(hipStream_t st, int grid_res, int n_cu, const E
 // stored voxels where nobody owns one, the count and the tight box
 hipError_t launch_voxelize_resolve(hipStream_t st, int grid_res, const EditBox& clip, unsigned long long base, const vrt_triangle* tris, bool final,
                                    const int8_t* mat, const uint8_t* rgb, const VoxScratch& s);
+// vrt_fill_triangles (vrt_fill.h).  The same scratch cut up by plan_fill_*: one toggle bit per voxel of the clip box (fill_words words),
+// the box arrays, the item-list entries of a batch, heads and the result record as above.
+struct FillScratch { uint32_t* toggles; int8_t* box_mat; uint8_t* box_rgb; VoxEntry* entries; unsigned long long* heads; VoxResult* res; };
+// toggle words zeroed, the result record opened
+hipError_t launch_fill_begin(hipStream_t st, const EditBox& clip, const FillScratch& s);
+// one batch of m <= plan_voxelize_batch() triangles (device memory): k_fill_setup, a lane a triangle, counts the items and writes the
+// entries; k_fill_raster, a wave an item, toggles one bit per owned column.  Batches need no order and no resolve between them.
+hipError_t launch_fill_batch(hipStream_t st, int grid_res, int n_cu, const EditBox& clip, long long m, const vrt_triangle* tris, const FillScratch& s);
+// k_fill_resolve, a lane a few voxels of the box, once after every batch: `voxel` where the prefix-XOR of the column says inside, the
+// grid's stored voxel elsewhere; the count and the tight box of the inside cells
+hipError_t launch_fill_resolve(hipStream_t st, int grid_res, const EditBox& clip, uint32_t voxel, const int8_t* mat, const uint8_t* rgb, const FillScratch& s);
 // A sampled query Q (vrt_query.h: RadianceQuery, SensorQuery, ProbeQuery): samples [s0, s0 + count) of n records (device memory) worked into
 // plane[n * count] by the query's item kernel (k_trace_radiance, k_gather_irradiance, k_gather_probes) and folded into out[n] (k_fold_query).
 // n * count <= Q::max_items; staged / oob as for launch_cast_rays; head: one word of device memory, the launch's work counter.

@@ -1834,6 +1834,148 @@ hipError_t launch_voxelize_resolve(hipStream_t st, int grid_res, const EditBox& 
     return hipSuccess;
 }
 
+// ---- vrt_fill_triangles: the inside of a closed mesh filled with voxels (vrt_fill.h holds the arithmetic) ---------------------------------
+// Three kernels around a toggle bitmap of one bit per voxel of the clip box, bits along z; launch_edit then does what it does for any box.
+//   k_fill_setup    k_vox_setup's sibling (that kernel is left as it is): a LANE a triangle, the gate, the snap, sign(n_z), the aligned
+//                   tiles of 16 x 16 columns its clipped xy bounds touch = its work items; entries and item numbers for a wave's 64
+//                   triangles with ONE 64-bit atomic, in the layout k_vox_setup leaves (VoxEntry, entries << 40 | items).
+//   k_fill_raster   a WAVE an item, VRT_FILL_ITEMS_PER_GRAB consecutive items a grab from the work head, the triangle found by binary
+//                   search and its set-up redone only when it changes, as in k_vox_raster.  An item: each lane tests four columns of
+//                   the tile (three edge functions, the bracket in int32) and, for a column the triangle owns, finds the first cell
+//                   above the triangle with one 64-bit division and flips that cell's bit with ONE atomicXor -- a triangle costs an
+//                   atomic per column, not per covered voxel.  XOR commutes, so nothing here depends on order: batches and the host
+//                   path's chunks toggle into the same bitmap and no resolve runs between them.
+//   k_fill_resolve  a lane a few voxels of the box, z fastest: the prefix-XOR of the column's words up to the voxel's own says inside;
+//                   the payload or the grid's stored voxel into the box arrays; count and tight box reduced over the workgroup first.
+// Plain C++ and vector memory operations throughout; the item number is made wave-uniform with readfirstlane as in k_vox_raster.
+__global__ __launch_bounds__(256) void k_fill_setup(int G, EditBox clip, long long m, const vrt_triangle* __restrict__ tris, unsigned long long* __restrict__ heads,
+                                                    VoxEntry* __restrict__ entries, VoxResult* __restrict__ res) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    bool valid = true;
+    uint32_t items = 0u;
+    if (i < m) items = fill_tri_items(tris[i], G, clip, valid);
+    const unsigned long long has = __ballot(items != 0u), bad = __ballot(!valid);
+    unsigned long long incl = items;
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    const unsigned long long total = __shfl(incl, 63, 64);
+    unsigned long long old = 0ULL;
+    if (lane == 0) {
+        if (has) old = atomicAdd(&heads[0], ((unsigned long long)__popcll(has) << 40) + total);
+        if (bad) atomicAdd(&res->invalid, (unsigned long long)__popcll(bad));
+    }
+    old = __shfl(old, 0, 64);
+    if (items != 0u) {   // (slot < m: a batch has no more entries than triangles)
+        VoxEntry e;
+        e.first = (old & VRT_VOX_ITEM_MASK) + incl - items;
+        e.tri = (uint32_t)i;
+        e.items = items;
+        entries[(old >> 40) + (unsigned long long)__popcll(has & ((1ULL << lane) - 1ULL))] = e;
+    }
+}
+__global__ __launch_bounds__(256) void k_fill_raster(int G, EditBox clip, const vrt_triangle* __restrict__ tris, unsigned long long* __restrict__ heads,
+                                                     const VoxEntry* __restrict__ entries, uint32_t* __restrict__ toggles) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long h = heads[0], total = h & VRT_VOX_ITEM_MASK;
+    const long long n_entries = (long long)(h >> 40);
+    for (;;) {
+        unsigned long long g = 0ULL;
+        if (lane == 0) g = atomicAdd(&heads[1], (unsigned long long)VRT_FILL_ITEMS_PER_GRAB);
+        g = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(g >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)g);
+        if (g >= total) return;
+        const unsigned long long g1 = g + VRT_FILL_ITEMS_PER_GRAB < total ? g + VRT_FILL_ITEMS_PER_GRAB : total;
+        long long e = vox_find_entry(entries, n_entries, g);
+        while (g < g1 && e < n_entries) {   // (e < n_entries always: every item below `total` belongs to an entry)
+            const VoxEntry en = entries[e++];
+            FillTri s;
+            fill_setup(tris[en.tri], G, s);
+            const EditCells cells = fill_cells(s, clip), tiles = fill_tiles(cells);
+            const unsigned long long end = en.first + en.items < g1 ? en.first + en.items : g1;
+            for (; g < end; g++) {
+                int tx, ty, tz;
+                edit_cell(tiles, (int)(g - en.first), tx, ty, tz);
+                for (int k = 0; k < 4; k++) {
+                    int cx, cy;
+                    if (!fill_lane_column(s, cells, tx, ty, lane, k, cx, cy)) continue;
+                    uint32_t bit;
+                    const int at = fill_toggle_at(clip, cx, cy, fill_first_cell(s, cx, cy), bit);   // (-1, or below fill_words(clip): the column is in the box)
+                    if (at >= 0) atomicXor(&toggles[at], bit);
+                }
+            }
+        }
+    }
+}
+// k_vox_resolve's shape: VRT_VOX_RESOLVE_PER_THREAD voxels a thread taken 256 apart, count and bounds summed per thread, over the wave with
+// shuffles, over the workgroup's four waves through LDS, one thread a workgroup issuing the atomics.
+__global__ __launch_bounds__(256) void k_fill_resolve(int G, EditBox clip, const uint32_t* __restrict__ toggles, uint32_t voxel, const int8_t* __restrict__ mat,
+                                                      const uint8_t* __restrict__ rgb, int8_t* __restrict__ box_mat, uint8_t* __restrict__ box_rgb, VoxResult* res) {
+    __shared__ int part[4][7];
+    const int nv = edit_box_voxels(clip), first = blockIdx.x * (256 * VRT_VOX_RESOLVE_PER_THREAD) + threadIdx.x;
+    int count = 0, lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int32_t)0x80000000, (int32_t)0x80000000, (int32_t)0x80000000};
+    for (int k = 0; k < VRT_VOX_RESOLVE_PER_THREAD; k++) {
+        const int i = first + k * 256;
+        if (i < nv && fill_resolve_voxel(clip, G, i, toggles, voxel, mat, rgb, box_mat, box_rgb)) {
+            int c[3];
+            edit_box_voxel(clip, i, c[0], c[1], c[2]);
+            count++;
+            for (int a = 0; a < 3; a++) { lo[a] = c[a] < lo[a] ? c[a] : lo[a]; hi[a] = c[a] > hi[a] ? c[a] : hi[a]; }
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        count += __shfl_xor(count, d, 64);
+        for (int a = 0; a < 3; a++) {
+            const int l = __shfl_xor(lo[a], d, 64), u = __shfl_xor(hi[a], d, 64);
+            lo[a] = l < lo[a] ? l : lo[a];
+            hi[a] = u > hi[a] ? u : hi[a];
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        int* p = part[threadIdx.x >> 6];
+        p[0] = count;
+        for (int a = 0; a < 3; a++) { p[1 + a] = lo[a]; p[4 + a] = hi[a]; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) {
+            count += part[w][0];
+            for (int a = 0; a < 3; a++) { lo[a] = part[w][1 + a] < lo[a] ? part[w][1 + a] : lo[a]; hi[a] = part[w][4 + a] > hi[a] ? part[w][4 + a] : hi[a]; }
+        }
+        if (count) {
+            atomicAdd(&res->voxels, (unsigned long long)count);
+            for (int a = 0; a < 3; a++) {   // (a stale load only costs an atomic that changes nothing)
+                if (lo[a] < *(volatile int32_t*)&res->lo[a]) atomicMin(&res->lo[a], lo[a]);
+                if (hi[a] > *(volatile int32_t*)&res->hi[a]) atomicMax(&res->hi[a], hi[a]);
+            }
+        }
+    }
+}
+
+hipError_t launch_fill_begin(hipStream_t st, const EditBox& clip, const FillScratch& s) {
+    hipError_t e = hipMemsetAsync(s.toggles, 0, 4 * (size_t)fill_words(clip), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_vox_begin, dim3(1), dim3(64), 0, st, s.res);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_fill_batch(hipStream_t st, int grid_res, int n_cu, const EditBox& clip, long long m, const vrt_triangle* tris, const FillScratch& s) {
+    hipError_t e = hipMemsetAsync(s.heads, 0, 16, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_fill_setup, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, grid_res, clip, m, tris, s.heads, s.entries, s.res);
+    VRT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_fill_raster, dim3(plan_voxelize_blocks(n_cu)), dim3(256), 0, st, grid_res, clip, tris, s.heads, (const VoxEntry*)s.entries, s.toggles);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_fill_resolve(hipStream_t st, int grid_res, const EditBox& clip, uint32_t voxel, const int8_t* mat, const uint8_t* rgb, const FillScratch& s) {
+    hipLaunchKernelGGL(k_fill_resolve, dim3((edit_box_voxels(clip) + 256 * VRT_VOX_RESOLVE_PER_THREAD - 1) / (256 * VRT_VOX_RESOLVE_PER_THREAD)), dim3(256), 0, st, grid_res, clip,
+                       (const uint32_t*)s.toggles, voxel, mat, rgb, s.box_mat, s.box_rgb, s.res);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
 // A sampled query's chunk -- samples [s0, s0 + count) of n records -- worked into `plane` by the query's item kernel and folded into `out`.
 // n * count is at most Q::max_items (plan_query_chunk); `head`: the launch's work counter, zeroed here on the stream.
 template <class Q>

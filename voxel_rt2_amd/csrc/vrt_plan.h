@@ -261,6 +261,21 @@ static inline size_t plan_voxelize_entries_at(size_t nv) { return (plan_voxelize
 static inline size_t plan_voxelize_heads_at(size_t nv, size_t batch) { return plan_voxelize_entries_at(nv) + 16 * batch; }
 static inline size_t plan_voxelize_bytes(size_t nv, size_t batch) { return plan_voxelize_heads_at(nv, batch) + 256; }
 
+// ---- vrt_fill_triangles -----------------------------------------------------------------------------------------------------------------
+// Chunks and batches are vrt_voxelize_triangles' (plan_voxelize_chunk, plan_voxelize_batch), and so is the persistent grid
+// (plan_voxelize_blocks): the item count is known on the device only.  An item here is a tile of 16 x 16 columns (vrt_fill.h), four
+// column tests and at most four divisions a lane -- an order of magnitude lighter than the surface pass's 16^3 cell, so the tail a
+// grab leaves on one wave matters less and the search for an item's triangle more: a grid-spanning triangle's 256 items are 32 grabs.
+#define VRT_FILL_ITEMS_PER_GRAB 8
+// Bytes of the fill's layout of the context's voxeliser scratch for a box of nv voxels and `words` toggle words (fill_words: one bit a
+// voxel, a column rounded up to whole 32-bit words) and batches of at most `batch` triangles: the toggle words, the box arrays handed
+// to launch_edit (materials padded to 256 bytes), the item-list entries, the two heads and the result record.
+static inline size_t plan_fill_mat_at(size_t words) { return (4 * words + 255) & ~(size_t)255; }
+static inline size_t plan_fill_rgb_at(size_t words, size_t nv) { return plan_fill_mat_at(words) + ((nv + 255) & ~(size_t)255); }
+static inline size_t plan_fill_entries_at(size_t words, size_t nv) { return (plan_fill_rgb_at(words, nv) + 3 * nv + 255) & ~(size_t)255; }
+static inline size_t plan_fill_heads_at(size_t words, size_t nv, size_t batch) { return plan_fill_entries_at(words, nv) + 16 * batch; }
+static inline size_t plan_fill_bytes(size_t words, size_t nv, size_t batch) { return plan_fill_heads_at(words, nv, batch) + 256; }
+
 // ---- the sampled queries: vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes (vrt_query.h) ----------------------------------------------------
 // The work item is (record, sample) -- (ray, sample) or (sensor, sample); a finished item leaves its value in a scratch plane -- 12 bytes
 // an item for a radiance, a 32-byte vrt_irradiance record of four terms for a sensor -- which k_fold_query sums per record in sample

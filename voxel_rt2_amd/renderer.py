@@ -409,6 +409,77 @@ class Renderer(VoxelStore):
             self.reset_framebuffer()
         return res
 
+    def fill_triangles(self, vertices, faces=None, color=(255, 255, 255), mat=1, lo=None, hi=None, shell=False, reset=True):
+        """Fill the INSIDE of a closed triangle mesh (world units) with one colour (r, g, b in 0..255) and material byte, in the box
+        [lo, hi) of array indices -- by default mesh_box(vertices) -- of the scene as prepare_data() / update_voxels() left it, on the
+        device (include/vrt_api.h, vrt_fill_triangles): a voxel is inside iff its centre is, by the parity of the triangles below it,
+        exactly and whatever their orientation; mat = 0 carves the volume out.  vertices, faces: as for voxelize_triangles; a torch
+        tensor on the device holding _abi.TRIANGLE records is handed over as it is (the box is then the whole grid unless given).
+        shell=True follows the fill with voxelize_triangles of the same mesh and payload: solid plus conservative skin, every voxel
+        the surface touches included (host vertices only).  Returns the result record -- the tight box and the count of the voxels
+        written, of fill and skin together with shell=True -- and brings voxel_material / voxel_color in step over that box.  reset:
+        start a fresh accumulation."""
+        if not getattr(self, "_prepared", False):
+            raise NativeError("fill_triangles edits a prepared scene: call prepare_data() first")
+        if self._voxels_dirty:
+            self.update_voxels(reset=False)
+        self._push()
+        g = self.voxel_grid_res
+        c = [int(x) & 0xFF for x in np.asarray(color, np.int64).reshape(3)]
+        voxel = c[0] | c[1] << 8 | c[2] << 16 | int(np.int8(mat).view(np.uint8)) << 24
+        if hasattr(vertices, "data_ptr"):
+            if shell:
+                raise ValueError("shell=True needs the mesh as host vertices: the skin is voxelised with payloads written into the records")
+            tris, box = vertices, ((0, 0, 0), (g, g, g))
+        else:
+            v = np.asarray(vertices, np.float32)
+            if faces is not None:
+                v = v.reshape(-1, 3)[np.asarray(faces, np.int64).reshape(-1, 3)]
+            v = v.reshape(-1, 3, 3)
+            tris = np.zeros(len(v), _abi.TRIANGLE)
+            tris["v0"], tris["v1"], tris["v2"], tris["voxel"] = v[:, 0], v[:, 1], v[:, 2], voxel
+            box = self.mesh_box(v)
+        lo, hi = (box[0] if lo is None else lo), (box[1] if hi is None else hi)
+        if not shell:
+            res = self._s.fill_triangles(tris, lo, hi, voxel)
+            if res["voxels"]:
+                self.sync_voxels_from_device(tuple(int(x) for x in res["lo"]), tuple(int(x) for x in res["hi"]))
+        else:
+            res = self._fill_with_shell(tris, lo, hi, voxel)
+        if reset:
+            self.reset_framebuffer()
+        return res
+
+    def _fill_with_shell(self, tris, lo, hi, voxel):
+        """Fill plus skin, and the record of their union.  The skin's record counts the cells the surface covers, the fill's the cells
+        inside, and many cells are both; to count each once the skin is first written with a payload that no voxel of the box holds, so
+        that the host mirror can tell the skin cells the fill leaves over; then the fill, then the skin with the real payload."""
+        sl = tuple(slice(int(l), int(h)) for l, h in zip(lo, hi))
+        if any(s.stop <= s.start for s in sl) or len(tris) == 0:
+            return self._s.fill_triangles(tris, lo, hi, voxel)
+        held = self.voxel_color[sl].astype(np.uint32)
+        held = np.unique(held[..., 0] | held[..., 1] << 8 | held[..., 2] << 16 | self.voxel_material[sl].view(np.uint8).astype(np.uint32) << 24)
+        mark = next(m for m in (voxel & 0xFF000000 | k for k in range(1 << 24)) if m != voxel and m not in held)   # (the box holds at most 2^24 - 1 others only in theory)
+        marked = tris.copy()
+        marked["voxel"] = mark
+        skin = self._s.voxelize_triangles(marked, lo, hi)
+        res = self._s.fill_triangles(tris, lo, hi, voxel)
+        left = 0
+        if skin["voxels"]:
+            b = tuple(slice(int(l), int(h)) for l, h in zip(skin["lo"], skin["hi"]))
+            self.sync_voxels_from_device(tuple(int(x) for x in skin["lo"]), tuple(int(x) for x in skin["hi"]))
+            col = self.voxel_color[b].astype(np.uint32)
+            left = int(((col[..., 0] | col[..., 1] << 8 | col[..., 2] << 16 | self.voxel_material[b].view(np.uint8).astype(np.uint32) << 24) == mark).sum())
+            self._s.voxelize_triangles(tris, lo, hi)
+            if res["voxels"]:
+                res["lo"], res["hi"] = np.minimum(res["lo"], skin["lo"]), np.maximum(res["hi"], skin["hi"])
+            else:
+                res["lo"], res["hi"] = skin["lo"], skin["hi"]
+            res["voxels"] += left
+        if res["voxels"]:
+            self.sync_voxels_from_device(tuple(int(x) for x in res["lo"]), tuple(int(x) for x in res["hi"]))
+        return res
+
     def mesh_box(self, vertices):
         """The box [lo, hi) of array indices that encloses every voxel a mesh with these vertices (world units, any shape (..., 3)) can
         cover, clamped to the grid: what voxelize_triangles takes as lo, hi.  A vertex on a grid plane counts the cells on both sides.
