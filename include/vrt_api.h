@@ -420,6 +420,37 @@ int vrt_gather_probes(vrt_ctx* ctx, int64_t n, const vrt_probe* probes, int n_sa
  * call synchronises; 1: device memory, queued on the context's stream.  Box rules and error codes are vrt_update_voxels'; the pending
  * accumulation is not forced. */
 int vrt_fetch_voxels(vrt_ctx* ctx, const int32_t lo[3], const int32_t hi[3], void* mat, void* rgb, int on_device);
+/* Ask a PREPARED grid how far each cell of the box [lo, hi) is from the nearest solid voxel, and which voxel that is: the exact
+ * squared Euclidean distance field, on the device.
+ * CELLS AND TARGETS.  Only cells inside the grid exist; they live in the index space of vrt_upload_voxels.  A cell is SOLID iff its
+ * stored material byte is > 0 (signed) -- the bit of the occupancy pyramid's finest level, as for vrt_sweep_boxes.  The TARGETS are
+ * the solid cells of the WHOLE grid; with VRT_DIST_TO_EMPTY in `flags` they are the non-solid cells of the whole grid.  The floor plane
+ * is not a target.  vrt_set_reference_indexing does not change the answer.
+ * DISTANCE.  D(c) = min over targets t of (c_x - t_x)^2 + (c_y - t_y)^2 + (c_z - t_z)^2, an integer: cell centres are one unit apart.
+ * d2[c] = D(c) if a target exists and D(c) <= max_d2, else VRT_DIST_FAR.  A target cell has D = 0.  max_d2 >= 3 (grid_res - 1)^2 means
+ * unbounded: no two cells are further apart.
+ * NEAREST (may be NULL: then nothing is computed for it).  Where d2[c] is not VRT_DIST_FAR, nearest[c] is the linear index
+ * (t_x * grid_res + t_y) * grid_res + t_z of the target that attains D(c); among several such targets the SMALLEST linear index wins,
+ * which is lexicographic order in (x, y, z).  Where d2[c] is VRT_DIST_FAR, nearest[c] is -1.
+ * OUTPUT AND COST.  d2 and nearest are int32[hx][hy][hz] over the cells of the box, C order, z fastest.  Targets outside the box count.
+ * The cost follows the box grown by floor(sqrt(max_d2)) on every side and clipped to the grid, not the whole grid; that is exact, since
+ * a target within max_d2 of a box cell differs from it by at most floor(sqrt(max_d2)) on every axis.
+ * ORDERING AND PURITY are vrt_fetch_voxels': the call is queued on the context's stream, behind every edit queued so far and ahead of
+ * later ones; the pending accumulation is not forced; no history, g-buffer, counter or statistic is touched, and frames rendered
+ * around it are bit for bit the frames rendered without it.  on_device = 0: host arrays, the call returns when they are filled; = 1:
+ * device memory, the work is only queued.
+ * Scratch: a buffer of the context's own (neither the voxeliser's nor the query staging buffer), grown on demand, kept by the context,
+ * freed by vrt_destroy: per voxel of the grown box at most 8 bytes of pass values (4 for the z pass over the box's z range, 4 for the
+ * y pass over the box's y and z range) plus, with `nearest`, at most 2 bytes of chosen coordinates; on the host path 4 bytes per voxel
+ * of the box for each staged result.  Unbounded over a whole 256^3 grid: 168 MB with `nearest`, 134 MB without.
+ * VRT_E_INVALID: NULL ctx, lo, hi or d2; lo > hi or a box outside the grid (vrt_update_voxels' rules); max_d2 < 0 or
+ * max_d2 > VRT_DIST_MAX_D2; unknown flag bits; on_device not 0 or 1.  VRT_E_STATE: before vrt_prepare, or after a vrt_upload_voxels that
+ * no vrt_prepare has followed.  An empty box returns VRT_OK and writes nothing.  No counterpart in the reference. */
+enum { VRT_DIST_TO_EMPTY = 1 };
+#define VRT_DIST_FAR    0x7fffffff
+#define VRT_DIST_MAX_D2 195075            /* 3 * 255^2: every distance a 256^3 grid holds */
+int vrt_distance_field(vrt_ctx* ctx, const int32_t lo[3], const int32_t hi[3], int32_t max_d2, uint32_t flags,
+                       void* d2 /* int32[hx][hy][hz] */, void* nearest /* int32[hx][hy][hz], may be NULL */, int on_device);
 /* Renderer.accumulate_clouds / compute_atmosphere (pathtracer.py:325-329) */
 int vrt_sky_accumulate_clouds(vrt_ctx* ctx, int max_samples);
 int vrt_sky_compute_slice(vrt_ctx* ctx, int slice_idx, int max_slices);

@@ -16,6 +16,7 @@
 #   sweeprate       tools/sweep_rate.py: boxes/s of vrt_sweep_boxes next to vrt_cast_rays on as many rays -> sweep_rate.jsonl under this run's output folder
 #   voxelizerate    tools/voxelize_rate.py: ms a call of vrt_voxelize_triangles next to vrt_update_voxels of the same box -> voxelize_rate.jsonl under this run's output folder
 #   fillrate        tools/fill_rate.py: ms a call of vrt_fill_triangles next to vrt_voxelize_triangles of the same mesh and vrt_update_voxels of the same box -> fill_rate.jsonl under this run's output folder
+#   distancerate    tools/distance_rate.py: ms a call of vrt_distance_field (d2; d2 + nearest) next to vrt_fetch_voxels of the same box -> distance_rate.jsonl under this run's output folder
 #   trace:CASE      rocprofv3 --kernel-trace --stats of bench_scenes.py CASE (CASE = bench: the bench command, config 2)
 #   pmc:CASE        tools/pmc.sh CASE + summary
 #   timeline:CASE[:MODE[:LAG]]  launches and copies in time (tools/timeline.py)
@@ -73,6 +74,9 @@ for l in open('$O/scenes${arg:+_}${arg//,/_}.jsonl'):
     fillrate)
       timeout -k 10 300 python tools/fill_rate.py --out $O/fill_rate.jsonl > $O/fill_rate.out 2> $O/fill_rate.err || { rc=$?; tail -5 $O/fill_rate.err; fail fillrate $rc; }
       tail -1 $O/fill_rate.out ;;
+    distancerate)
+      timeout -k 10 300 python tools/distance_rate.py --out $O/distance_rate.jsonl > $O/distance_rate.out 2> $O/distance_rate.err || { rc=$?; tail -5 $O/distance_rate.err; fail distancerate $rc; }
+      tail -1 $O/distance_rate.out ;;
     trace)
       ( cd /tmp; export TMPDIR=/tmp
         if [ "$arg" == "bench" ]; then timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -o t -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.json 2> $O/trace_bench.err

@@ -29,6 +29,10 @@ TRIANGLE = np.dtype([("v0", np.float32, 3), ("voxel", np.uint32), ("v1", np.floa
                      ("reserved1", np.uint32)])
 VOXELIZE_RESULT = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("voxels", np.int64), ("invalid", np.int64)])
 assert TRIANGLE.itemsize == 48 and VOXELIZE_RESULT.itemsize == 40
+# vrt_distance_field
+DIST_TO_EMPTY = 1
+DIST_FAR = 0x7FFFFFFF
+DIST_MAX_D2 = 195075
 # vrt_path_ray / vrt_radiance (vrt_trace_radiance)
 PATH_RAY = np.dtype([("origin", np.float32, 3), ("stream", np.uint32), ("dir", np.float32, 3), ("reserved", np.uint32)])
 RADIANCE = np.dtype([("rgb", np.float32, 3), ("t", np.float32)])
@@ -119,6 +123,7 @@ def declare(lib, prefix):
     sig("gather_irradiance", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)
     sig("gather_probes", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)
     sig("fetch_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
+    sig("distance_field", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, P, P, C.c_int)
     sig("sky_accumulate_clouds", C.c_int, P, C.c_int)
     sig("sky_compute_slice", C.c_int, P, C.c_int, C.c_int)
     sig("sky_accumulate_clouds_slice", C.c_int, P, C.c_int, C.c_int, C.c_int)

@@ -211,6 +211,45 @@ class NativeSession:
             self._call("fetch_voxels", (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), mat.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p), 0)
         return mat, rgb
 
+    def distance_field(self, lo, hi, max_d2=None, to_empty=False, nearest=False, out=None):
+        """The exact squared distance from every cell of the box [lo, hi) to the nearest solid voxel of the grid (to_empty: to the
+        nearest non-solid cell), and with nearest=True that voxel's linear index (include/vrt_api.h, vrt_distance_field).  max_d2:
+        distances beyond it are _abi.DIST_FAR (nearest -1); None: unbounded.  Host path: returns d2, or (d2, nearest), int32 arrays of
+        shape hi - lo; `out`, if given, is that array or pair, filled in place.  Device path: `out` is a torch int32 tensor on the
+        device of that shape, or a pair of them with nearest=True, taken without a copy; the work is queued on the session's stream and
+        `out` is returned, not yet filled."""
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError("lo and hi are three coordinates each")
+        shape = tuple(max(h - l, 0) for l, h in zip(lo, hi))
+        max_d2 = _abi.DIST_MAX_D2 if max_d2 is None else int(max_d2)
+        flags = C.c_uint32(_abi.DIST_TO_EMPTY if to_empty else 0)
+        parts = (out if nearest else (out,)) if out is not None else None
+        if parts is not None and len(parts) != (2 if nearest else 1):
+            raise ValueError("`out` is one array, or the pair (d2, nearest) with nearest=True")
+        if parts is not None and hasattr(parts[0], "data_ptr"):
+            import torch
+            for t in parts:
+                if not hasattr(t, "data_ptr") or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise ValueError(f"device path: `out` holds contiguous int32 device tensors of shape {list(shape)}")
+            if parts[0].numel():   # (an empty tensor's pointer may be NULL, which the library refuses; it checks box and state all the same)
+                ptrs = [C.c_void_p(t.data_ptr()) for t in parts] + [None] * (2 - len(parts))
+                self._call("distance_field", (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), max_d2, flags, ptrs[0], ptrs[1], 1)
+            else:
+                none = np.zeros(1, np.int32)
+                self._call("distance_field", (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), max_d2, flags, none.ctypes.data_as(C.c_void_p), None, 0)
+            return out
+        if parts is None:
+            parts = tuple(np.empty(shape, np.int32) for _ in range(2 if nearest else 1))
+        for a in parts:
+            if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError(f"`out` holds contiguous int32 arrays of shape {list(shape)}")
+        ptrs = [a.ctypes.data_as(C.c_void_p) for a in parts] + [None] * (2 - len(parts))
+        if parts[0].size == 0:   # (as above)
+            ptrs[0], ptrs[1] = np.zeros(1, np.int32).ctypes.data_as(C.c_void_p), None
+        self._call("distance_field", (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), max_d2, flags, ptrs[0], ptrs[1], 0)
+        return parts if nearest else parts[0]
+
     def upload_materials(self, table):
         table = np.ascontiguousarray(table, dtype=np.float32)
         if table.shape != (128, 14):

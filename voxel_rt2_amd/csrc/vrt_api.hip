@@ -597,6 +597,43 @@ int vrt_fetch_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], void*
     HIP_TRY(sync_stream_only(c, c->stream));
     return VRT_OK;
 }
+// The distance field of the stored voxels over the box [lo, hi) (vrt_distance.h): three line passes on the context's stream, reading
+// d_mat as vrt_fetch_voxels does -- so the same ordering, no enter(), no flush.  The scratch is the call's own buffer: every call runs
+// on the context's stream, where stream order lets the next call reuse it, and the host path's copies out of it are waited for here.
+int vrt_distance_field(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], int32_t max_d2, uint32_t flags, void* d2, void* nearest, int on_device) {
+    if (!c || !lo || !hi || !d2) return fail(VRT_E_INVALID, "null argument");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    EditBox box;
+    for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
+    if (!edit_box_valid(box, c->cfg.grid_res)) return fail(VRT_E_INVALID, "the box must satisfy 0 <= lo <= hi <= grid_res on every axis");
+    if (max_d2 < 0 || max_d2 > VRT_DIST_MAX_D2) return fail(VRT_E_INVALID, "max_d2 must be 0 .. VRT_DIST_MAX_D2");
+    if ((flags & ~(uint32_t)VRT_DIST_TO_EMPTY) != 0u) return fail(VRT_E_INVALID, "unknown flag bits");
+    if (!c->prepared) return fail(VRT_E_STATE, "vrt_distance_field reads a prepared grid: call vrt_prepare first (also after vrt_upload_voxels)");
+    const size_t nv = (size_t)edit_box_voxels(box);
+    if (nv == 0) return VRT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const DistBox p = dist_plan_box(box, c->cfg.grid_res, max_d2, flags);
+    const DistLayout l = plan_distance_layout((size_t)dist_len(p.grown, 0), (size_t)dist_len(p.grown, 1), (size_t)dist_len(box, 0), (size_t)dist_len(box, 1),
+                                              (size_t)dist_len(box, 2), nearest != nullptr, !on_device);
+    if (c->dist_bytes < l.bytes) {   // (hipFree waits for the device: no kernel is still using the old one)
+        HIP_TRY(dfree(c, &c->d_dist));
+        c->dist_bytes = 0;
+        HIP_TRY(dmalloc(c, &c->d_dist, l.bytes));
+        c->dist_bytes = l.bytes;
+    }
+    const DistScratch s{(int*)(c->d_dist + l.a_at), (int*)(c->d_dist + l.b_at), c->d_dist + l.cz_at, c->d_dist + l.cy_at};
+    if (on_device) {
+        HIP_TRY(launch_distance_field(c->stream, c->cfg.grid_res, p, c->d_mat, s, (int*)d2, (int*)nearest));
+        return VRT_OK;
+    }
+    int* d_d2 = (int*)(c->d_dist + l.d2_at);
+    int* d_nearest = nearest ? (int*)(c->d_dist + l.nearest_at) : nullptr;
+    HIP_TRY(launch_distance_field(c->stream, c->cfg.grid_res, p, c->d_mat, s, d_d2, d_nearest));
+    HIP_TRY(hipMemcpyAsync(d2, d_d2, 4 * nv, hipMemcpyDeviceToHost, c->stream));
+    if (nearest) HIP_TRY(hipMemcpyAsync(nearest, d_nearest, 4 * nv, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(sync_stream_only(c, c->stream));
+    return VRT_OK;
+}
 // Voxelise triangles into the box [lo, hi) of a prepared context (vrt_voxelize.h): ownership of the box's voxels is settled batch by
 // batch on the device (launch_voxelize_batch), resolved into box arrays (launch_voxelize_resolve), and those go through launch_edit
 // like any other box -- ordered and synchronised exactly as vrt_update_voxels.  The host path stages plan_voxelize_chunk() triangles

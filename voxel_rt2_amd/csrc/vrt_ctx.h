@@ -119,6 +119,8 @@ struct vrt_ctx {
     size_t cast_stage_bytes = 0;
     uint8_t* d_vox = nullptr;         // vrt_voxelize_triangles: ownership words, box arrays, item list, heads and result record (plan_voxelize_bytes; grown on demand); vrt_fill_triangles lays it out its own way (plan_fill_bytes)
     size_t vox_bytes = 0;
+    uint8_t* d_dist = nullptr;        // vrt_distance_field: the passes' values and chosen coordinates, and on the host path the staged results (plan_distance_layout; grown on demand)
+    size_t dist_bytes = 0;
     uint8_t* d_radiance_plane = nullptr;   // vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes: a work counter (256 bytes) and the scratch plane of VRT_RADIANCE_ITEMS item values (allocated on first use)
     float* d_mats = nullptr;
     Counters* d_counters = nullptr;

@@ -17,6 +17,7 @@
 #include "vrt_sweep.h"
 #include "vrt_voxelize.h"
 #include "vrt_fill.h"
+#include "vrt_distance.h"
 #include "vrt_query.h"
 #include "vrt_denoise.h"
 
@@ -89,7 +90,12 @@ hipError_t launch_fill_batch(hipStream_t st, int grid_res, int n_cu, const EditB
 // k_fill_resolve, a lane a few voxels of the box, once after every batch: `voxel` where the prefix-XOR of the column says inside, the
 // grid's stored voxel elsewhere; the count and the tight box of the inside cells
 hipError_t launch_fill_resolve(hipStream_t st, int grid_res, const EditBox& clip, uint32_t voxel, const int8_t* mat, const uint8_t* rgb, const FillScratch& s);
-// A sampled query Q (vrt_query.h: RadianceQuery, SensorQuery, ProbeQuery): samples [s0, s0 + count) of n records (device memory) worked into
+// vrt_distance_field (vrt_distance.h).  The call's scratch cut up by plan_distance_layout: pass z's and pass y's values and, where
+// `nearest` is asked for, the coordinates they chose (cz, cy: not touched otherwise).
+struct DistScratch { int* a; int* b; uint8_t* cz; uint8_t* cy; };
+// k_dist_z, k_dist_y, k_dist_x, one after the other on `st`: d2 (and nearest, unless NULL) of the cells of p.box (not empty), device memory
+hipError_t launch_distance_field(hipStream_t st, int grid_res, const DistBox& p, const int8_t* mat, const DistScratch& s, int* d2, int* nearest);
+// A sampled query Q (vrt_query.h:RadianceQuery, SensorQuery, ProbeQuery): samples [s0, s0 + count) of n records (device memory) worked into
 // plane[n * count] by the query's item kernel (k_trace_radiance, k_gather_irradiance, k_gather_probes) and folded into out[n] (k_fold_query).
 // n * count <= Q::max_items; staged / oob as for launch_cast_rays; head: one word of device memory, the launch's work counter.
 template <class Q>

@@ -20,6 +20,7 @@
 //   k_gather_irradiance                                   vrt_gather_irradiance: a sun sample and a hemisphere path per (sensor, sample)
 //   k_gather_probes                                       vrt_gather_probes: a sun sample and a sphere path per (probe, sample)
 //   k_fold_query<Q>                                       the ordered sums of any of the three (vrt_query.h)
+//   k_dist_z / k_dist_y / k_dist_x                        vrt_distance_field: the three line passes of the exact distance transform
 //
 // k_render is a persistent-thread kernel: the grid is sized to the device's residency, each wave
 // keeps 64 path records in registers and pulls pixels (8x8 tiles, tile-major order) from a global
@@ -1974,6 +1975,97 @@ hipError_t launch_fill_resolve(hipStream_t st, int grid_res, const EditBox& clip
                        (const uint32_t*)s.toggles, voxel, mat, rgb, s.box_mat, s.box_rgb, s.res);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
+}
+
+// ---- vrt_distance_field: three separable line passes through LDS (vrt_distance.h holds the arithmetic, vrt_plan.h the tile shapes) ----------
+// Memory is z-fastest everywhere, so every pass puts adjacent lanes on adjacent z (pass x: on adjacent cells of the (y, z) plane, which
+// is contiguous) and every global access is a coalesced segment.  A line is staged once and read by every output element of it.
+//   k_dist_z   VRT_DIST_Z_LINES consecutive lines (x, y) of the grown box a workgroup: their material bytes, read straight from d_mat,
+//              become 0 (target) or cap in LDS, one line after the other; a thread works elements 256 apart, so a wave's lanes sit on
+//              consecutive z of one line (or of neighbouring lines where the box is narrow) and read consecutive LDS words.
+//   k_dist_y   a tile of VRT_DIST_LANES adjacent z at one x a workgroup, staged as [y][lane]: a lane walks its own line with stride
+//              VRT_DIST_LANES words, so the 32 lanes of a group read 32 consecutive words -- no bank conflict inside a group.
+//   k_dist_x   the same over adjacent cells of the (y, z) plane, lines along x; writes d2 (dist_final) and, with NEAR, assembles `nearest`.
+// NEAR = false compiles the coordinates out: no cz / cy store, no load, and the scan stops one step earlier (dist_line_element).
+// Lanes of a wave scan as long as their slowest neighbour; neighbours see nearly the same distances, so little is lost.
+template <bool NEAR>
+__global__ __launch_bounds__(256) void k_dist_z(DistBox p, int G, const int8_t* __restrict__ mat, int* __restrict__ A, uint8_t* __restrict__ cz) {
+    __shared__ int f[VRT_DIST_Z_LINES * VRT_DIST_Z_PITCH];
+    const int gyn = dist_len(p.grown, 1), gzn = dist_len(p.grown, 2), bzn = dist_len(p.box, 2);
+    const int lines = dist_len(p.grown, 0) * gyn;
+    const int L0 = blockIdx.x * VRT_DIST_Z_LINES;
+    const int nl = min(VRT_DIST_Z_LINES, lines - L0);
+    for (int idx = threadIdx.x; idx < nl * gzn; idx += 256) {
+        const int l = idx / gzn, k = idx - l * gzn, L = L0 + l;
+        const int x = p.grown.lo[0] + L / gyn, y = p.grown.lo[1] + L % gyn;
+        f[l * VRT_DIST_Z_PITCH + k] = dist_seed(mat[edit_grid_index(G, x, y, p.grown.lo[2] + k)], p);
+    }
+    __syncthreads();
+    const int off = p.box.lo[2] - p.grown.lo[2];
+    for (int idx = threadIdx.x; idx < nl * bzn; idx += 256) {
+        const int l = idx / bzn, zi = idx - l * bzn;
+        const DistPick b = dist_line_element<NEAR>(f + l * VRT_DIST_Z_PITCH, 1, gzn, off + zi, p.grown.lo[2]);
+        const size_t o = (size_t)L0 * bzn + idx;   // dist_a_index: lines are consecutive in A
+        A[o] = b.v;
+        if (NEAR) cz[o] = (uint8_t)b.c;
+    }
+}
+template <bool NEAR>
+__global__ __launch_bounds__(256) void k_dist_y(DistBox p, const int* __restrict__ A, int* __restrict__ B, uint8_t* __restrict__ cy) {
+    extern __shared__ int f[];   // [gyn][VRT_DIST_LANES]
+    const int lane = threadIdx.x % VRT_DIST_LANES, grp = threadIdx.x / VRT_DIST_LANES;
+    const int gyn = dist_len(p.grown, 1), byn = dist_len(p.box, 1), bzn = dist_len(p.box, 2);
+    const int xi = blockIdx.y, zi = blockIdx.x * VRT_DIST_LANES + lane;
+    const bool ok = zi < bzn;
+    for (int j = grp; j < gyn; j += VRT_DIST_GROUPS) f[j * VRT_DIST_LANES + lane] = ok ? A[dist_a_index(p, xi, j, zi)] : p.cap;
+    __syncthreads();
+    if (!ok) return;
+    const int off = p.box.lo[1] - p.grown.lo[1];
+    for (int yo = grp; yo < byn; yo += VRT_DIST_GROUPS) {
+        const DistPick b = dist_line_element<NEAR>(f + lane, VRT_DIST_LANES, gyn, off + yo, p.grown.lo[1]);
+        const size_t o = dist_b_index(p, xi, yo, zi);
+        B[o] = b.v;
+        if (NEAR) cy[o] = (uint8_t)b.c;
+    }
+}
+template <bool NEAR>
+__global__ __launch_bounds__(256) void k_dist_x(DistBox p, int G, const int* __restrict__ B, const uint8_t* __restrict__ cz, const uint8_t* __restrict__ cy,
+                                                int* __restrict__ d2, int* __restrict__ nearest) {
+    extern __shared__ int f[];   // [gxn][VRT_DIST_LANES]
+    const int lane = threadIdx.x % VRT_DIST_LANES, grp = threadIdx.x / VRT_DIST_LANES;
+    const int gxn = dist_len(p.grown, 0), bxn = dist_len(p.box, 0), bzn = dist_len(p.box, 2);
+    const int plane = dist_len(p.box, 1) * bzn;
+    const int pi = blockIdx.x * VRT_DIST_LANES + lane;
+    const bool ok = pi < plane;
+    for (int j = grp; j < gxn; j += VRT_DIST_GROUPS) f[j * VRT_DIST_LANES + lane] = ok ? B[(size_t)j * plane + pi] : p.cap;
+    __syncthreads();
+    if (!ok) return;
+    const int off = p.box.lo[0] - p.grown.lo[0];
+    const int yo = pi / bzn, zi = pi - yo * bzn;
+    for (int xo = grp; xo < bxn; xo += VRT_DIST_GROUPS) {
+        const DistPick b = dist_line_element<NEAR>(f + lane, VRT_DIST_LANES, gxn, off + xo, p.grown.lo[0]);
+        const size_t o = (size_t)xo * plane + pi;
+        const int v = dist_final(b.v, p.max_d2);
+        d2[o] = v;
+        if (NEAR) nearest[o] = v == VRT_DIST_FAR_VALUE ? -1 : dist_assemble(p, G, b.c, yo, zi, cy, cz);
+    }
+}
+template <bool NEAR>
+static hipError_t launch_distance_passes(hipStream_t st, int grid_res, const DistBox& p, const int8_t* mat, const DistScratch& s, int* d2, int* nearest) {
+    const int gxn = dist_len(p.grown, 0), gyn = dist_len(p.grown, 1), byn = dist_len(p.box, 1), bzn = dist_len(p.box, 2);
+    hipLaunchKernelGGL(k_dist_z<NEAR>, dim3((gxn * gyn + VRT_DIST_Z_LINES - 1) / VRT_DIST_Z_LINES), dim3(256), 0, st, p, grid_res, mat, s.a, s.cz);
+    VRT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_dist_y<NEAR>, dim3((bzn + VRT_DIST_LANES - 1) / VRT_DIST_LANES, gxn), dim3(256), (size_t)gyn * VRT_DIST_LANES * sizeof(int), st, p,
+                       (const int*)s.a, s.b, s.cy);
+    VRT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_dist_x<NEAR>, dim3((byn * bzn + VRT_DIST_LANES - 1) / VRT_DIST_LANES), dim3(256), (size_t)gxn * VRT_DIST_LANES * sizeof(int), st, p,
+                       grid_res, (const int*)s.b, (const uint8_t*)s.cz, (const uint8_t*)s.cy, d2, nearest);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_distance_field(hipStream_t st, int grid_res, const DistBox& p, const int8_t* mat, const DistScratch& s, int* d2, int* nearest) {
+    if (edit_box_voxels(p.box) == 0 || grid_res > VRT_DIST_LINE) return hipErrorInvalidValue;
+    return nearest ? launch_distance_passes<true>(st, grid_res, p, mat, s, d2, nearest) : launch_distance_passes<false>(st, grid_res, p, mat, s, d2, nullptr);
 }
 
 // A sampled query's chunk -- samples [s0, s0 + count) of n records -- worked into `plane` by the query's item kernel and folded into `out`.

@@ -276,6 +276,32 @@ static inline size_t plan_fill_entries_at(size_t words, size_t nv) { return (pla
 static inline size_t plan_fill_heads_at(size_t words, size_t nv, size_t batch) { return plan_fill_entries_at(words, nv) + 16 * batch; }
 static inline size_t plan_fill_bytes(size_t words, size_t nv, size_t batch) { return plan_fill_heads_at(words, nv, batch) + 256; }
 
+// ---- vrt_distance_field (vrt_distance.h) ------------------------------------------------------------------------------------------------
+// Tile shapes.  Pass z: a workgroup of 256 threads stages VRT_DIST_Z_LINES whole lines (consecutive in memory: z fastest, then y) in LDS,
+// padded to 257 words a line, and a thread works output elements 256 apart.  Passes y and x: a workgroup stages a tile of
+// VRT_DIST_LANES adjacent lines -- adjacent in memory, so every row of the tile is one coalesced segment -- as [entry][lane], at most
+// 256 x 32 x 4 = 32 KB; its 256 threads are VRT_DIST_LANES lanes x VRT_DIST_GROUPS groups, a group working every eighth output entry.
+#define VRT_DIST_Z_LINES 8
+#define VRT_DIST_Z_PITCH 257
+#define VRT_DIST_LANES 32
+#define VRT_DIST_GROUPS 8
+// The scratch of one call, cut up: A int32[gx][gy][bz] (pass z's result), B int32[gx][by][bz] (pass y's); with `nearest` the chosen
+// coordinates cz uint8[gx][gy][bz] and cy uint8[gx][by][bz]; on the host path the staged results d2 and nearest int32[bx][by][bz].
+// gx, gy: the grown box's extent; bx, by, bz: the box's.  At most 10 bytes per voxel of the grown box plus 8 per voxel of the box.
+struct DistLayout { size_t a_at, b_at, cz_at, cy_at, d2_at, nearest_at, bytes; };
+static inline DistLayout plan_distance_layout(size_t gx, size_t gy, size_t bx, size_t by, size_t bz, bool nearest, bool staged) {
+    const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    DistLayout l;
+    l.a_at = 0;
+    l.b_at = up(l.a_at + 4 * gx * gy * bz);
+    l.cz_at = up(l.b_at + 4 * gx * by * bz);
+    l.cy_at = up(l.cz_at + (nearest ? gx * gy * bz : 0));
+    l.d2_at = up(l.cy_at + (nearest ? gx * by * bz : 0));
+    l.nearest_at = up(l.d2_at + (staged ? 4 * bx * by * bz : 0));
+    l.bytes = up(l.nearest_at + (staged && nearest ? 4 * bx * by * bz : 0)) + 256;
+    return l;
+}
+
 // ---- the sampled queries: vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes (vrt_query.h) ----------------------------------------------------
 // The work item is (record, sample) -- (ray, sample) or (sensor, sample); a finished item leaves its value in a scratch plane -- 12 bytes
 // an item for a radiance, a 32-byte vrt_irradiance record of four terms for a sensor -- which k_fold_query sums per record in sample

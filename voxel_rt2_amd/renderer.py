@@ -480,6 +480,123 @@ class Renderer(VoxelStore):
             self.sync_voxels_from_device(tuple(int(x) for x in res["lo"]), tuple(int(x) for x in res["hi"]))
         return res
 
+    # -- distances (include/vrt_api.h, vrt_distance_field; no counterpart in the reference) --------------------------------------------
+    @staticmethod
+    def _max_d2(radius):
+        """floor(radius^2) of a radius in voxels (may be fractional); None: unbounded"""
+        if radius is None:
+            return _abi.DIST_MAX_D2
+        if not radius >= 0:
+            raise ValueError("radius must not be negative")
+        return min(int(np.floor(float(radius) * float(radius))), _abi.DIST_MAX_D2)
+
+    def distance_field(self, lo, hi, radius=None, to_empty=False, nearest=False, signed=False):
+        """The exact squared distance, in voxels, from every cell of the box [lo, hi) of array indices to the nearest solid voxel of the
+        whole grid (to_empty: to the nearest non-solid cell), on the scene as prepare_data() / update_voxels() left it: an int32 array
+        of shape hi - lo; beyond `radius` voxels (d2 > floor(radius^2); None: no bound) it holds _abi.DIST_FAR.  nearest=True returns
+        (d2, nearest): the linear array index (x * G + y) * G + z of the voxel that attains the distance, the smallest among equals,
+        -1 where d2 is DIST_FAR.  signed=True makes both calls and returns +d2 (to the nearest solid) in non-solid cells and -d2 (to the
+        nearest non-solid cell) in solid ones, DIST_FAR keeping its sign, with the nearest of whichever applies.  Cells outside the
+        grid do not exist: they are neither solid nor empty."""
+        if not getattr(self, "_prepared", False):
+            raise NativeError("distance_field asks a prepared scene: call prepare_data() first")
+        self._push()
+        md = self._max_d2(radius)
+        if not signed:
+            return self._s.distance_field(lo, hi, md, to_empty=to_empty, nearest=nearest)
+        out, inn = (self._s.distance_field(lo, hi, md, to_empty=e, nearest=True) for e in (False, True))
+        outside = out[0] > 0                                   # a solid cell is its own nearest solid
+        d2 = np.where(outside, out[0], -inn[0]).astype(np.int32)
+        return (d2, np.where(outside, out[1], inn[1]).astype(np.int32)) if nearest else d2
+
+    def _box_on_device(self, lo, hi, md, to_empty, nearest):
+        """(d2, nearest or None, mat, rgb) of the box as torch tensors on the device, computed and waited for"""
+        import torch
+        shape = tuple(int(h) - int(l) for l, h in zip(lo, hi))
+        d2 = torch.empty(shape, dtype=torch.int32, device="cuda")
+        near = torch.empty(shape, dtype=torch.int32, device="cuda") if nearest else None
+        mat, rgb = torch.empty(shape, dtype=torch.int8, device="cuda"), torch.empty(shape + (3,), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()                               # (allocations are torch's; the library writes on the session's stream)
+        self._s.distance_field(lo, hi, md, to_empty=to_empty, nearest=nearest, out=(d2, near) if nearest else d2)
+        self._s.fetch_voxels(lo, hi, mat.data_ptr(), rgb.data_ptr(), on_device=True)
+        self._s.sync()
+        return d2, near, mat, rgb
+
+    def _edit_from_device(self, lo, hi, mat, rgb, reset):
+        import torch
+        mat, rgb = mat.contiguous(), rgb.contiguous()
+        torch.cuda.synchronize()                               # (written on torch's stream, read on the session's)
+        self._s.update_voxels(lo, hi, mat.data_ptr(), rgb.data_ptr(), on_device=True)   # (waits for the edit: the tensors may go)
+        self.sync_voxels_from_device(tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        if reset:
+            self.reset_framebuffer()
+
+    def grow_voxels(self, lo, hi, radius, color=None, mat=None, reset=True):
+        """Grow the solids by `radius` voxels inside the box [lo, hi) of array indices, on the device: every non-solid cell of the box
+        whose squared distance to the nearest solid voxel of the grid is <= floor(radius^2) becomes solid (distance_field and
+        fetch_voxels into device tensors, torch.where, update_voxels from device memory).  color (r, g, b in 0..255) and mat: the new
+        voxels' payload; with None the colour / material of the cell's nearest solid voxel -- the smallest linear index among equally
+        near ones -- is inherited.  Solids outside the box count as sources; only cells of the box are written.  Cells outside the grid
+        do not exist.  Returns the number of cells that became solid and brings voxel_material / voxel_color in step over the box.
+        reset: start a fresh accumulation."""
+        import torch
+        if not getattr(self, "_prepared", False):
+            raise NativeError("grow_voxels edits a prepared scene: call prepare_data() first")
+        if self._voxels_dirty:
+            self.update_voxels(reset=False)
+        self._push()
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if any(h <= l for l, h in zip(lo, hi)):
+            return 0
+        md = self._max_d2(radius)
+        inherit = color is None or mat is None
+        d2, near, bm, bc = self._box_on_device(lo, hi, md, False, inherit)
+        grow = (bm <= 0) & (d2 <= md)
+        new_m = torch.full_like(bm, int(np.int8(mat))) if mat is not None else None
+        new_c = torch.tensor([int(x) & 0xFF for x in np.asarray(color, np.int64).reshape(3)], dtype=torch.uint8, device="cuda").expand(bc.shape) if color is not None else None
+        if inherit:                                            # the nearest solid lies within floor(radius) of the box: fetch that much
+            g, r = self.voxel_grid_res, int(np.floor(np.sqrt(md)))
+            while (r + 1) * (r + 1) <= md:
+                r += 1
+            glo, ghi = [max(l - r, 0) for l in lo], [min(h + r, g) for h in hi]
+            gs = [h - l for l, h in zip(glo, ghi)]
+            gm, gc = torch.empty(gs, dtype=torch.int8, device="cuda"), torch.empty(gs + [3], dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            self._s.fetch_voxels(glo, ghi, gm.data_ptr(), gc.data_ptr(), on_device=True)
+            self._s.sync()
+            n = torch.where(grow, near, torch.zeros_like(near)).long()
+            x, y, z = n // (g * g), (n // g) % g, n % g
+            at = torch.where(grow, ((x - glo[0]) * gs[1] + (y - glo[1])) * gs[2] + (z - glo[2]), torch.zeros_like(n)).reshape(-1)
+            if new_m is None:
+                new_m = gm.reshape(-1)[at].reshape(bm.shape)
+            if new_c is None:
+                new_c = gc.reshape(-1, 3)[at].reshape(bc.shape)
+        count = int(grow.sum().item())
+        self._edit_from_device(lo, hi, torch.where(grow, new_m, bm), torch.where(grow[..., None], new_c, bc), reset)
+        return count
+
+    def shrink_voxels(self, lo, hi, radius, reset=True):
+        """Shrink the solids by `radius` voxels inside the box [lo, hi) of array indices, on the device: every solid cell of the box whose
+        squared distance to the nearest non-solid cell of the grid is <= floor(radius^2) becomes empty (material 0, colour 0).  Cells
+        outside the grid do not exist, so they are not empty either: a solid pressed against the grid's wall is not eroded from that
+        side.  Non-solid cells outside the box count as sources; only cells of the box are written.  Returns the number of cells that
+        became empty and brings voxel_material / voxel_color in step over the box.  reset: start a fresh accumulation."""
+        import torch
+        if not getattr(self, "_prepared", False):
+            raise NativeError("shrink_voxels edits a prepared scene: call prepare_data() first")
+        if self._voxels_dirty:
+            self.update_voxels(reset=False)
+        self._push()
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if any(h <= l for l, h in zip(lo, hi)):
+            return 0
+        md = self._max_d2(radius)
+        d2, _, bm, bc = self._box_on_device(lo, hi, md, True, False)
+        gone = (bm > 0) & (d2 <= md)
+        count = int(gone.sum().item())
+        self._edit_from_device(lo, hi, torch.where(gone, torch.zeros_like(bm), bm), torch.where(gone[..., None], torch.zeros_like(bc), bc), reset)
+        return count
+
     def mesh_box(self, vertices):
         """The box [lo, hi) of array indices that encloses every voxel a mesh with these vertices (world units, any shape (..., 3)) can
         cover, clamped to the grid: what voxelize_triangles takes as lo, hi.  A vertex on a grid plane counts the cells on both sides.
