@@ -25,7 +25,7 @@ def lib():
     if _lib is None:
         src = os.path.join(HERE, "emul", "edit_emul.cpp")
         csrc = os.path.join(ROOT, "voxel_rt2_amd", "csrc")
-        deps = [src] + [os.path.join(csrc, f) for f in ("vrt_edit.h", "vrt_trace.h", "vrt_types.h")]
+        deps = [src, os.path.join(HERE, "emul", "edit_emul.h"), os.path.join(ROOT, "include", "vrt_api.h")] + [os.path.join(csrc, f) for f in ("vrt_voxelize.h", "vrt_edit.h", "vrt_trace.h", "vrt_types.h")]
         if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
             subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unused-function", "-Wno-unknown-pragmas",
                             "-o", _SO, src], check=True, capture_output=True)

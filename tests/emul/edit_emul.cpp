@@ -1,19 +1,9 @@
 // edit_emul.cpp -- TEST TOOLING: the loops of the k_edit_* kernels (voxel_rt2_amd/csrc/vrt_kernels.hip, launch_edit) run on the host over
-// the functions of voxel_rt2_amd/csrc/vrt_edit.h, index by index, in the order launch_edit queues them.
+// the functions of voxel_rt2_amd/csrc/vrt_edit.h, index by index, in the order launch_edit queues them (the loops: edit_emul.h).
 // tests/test_voxel_edit_host.py compiles this with g++ and calls it through ctypes.
-#include "../../voxel_rt2_amd/csrc/vrt_edit.h"
+#include "edit_emul.h"
 
 using namespace vrt;
-
-template <int G>
-static void apply(const EditBox& box, const int8_t* box_mat, const uint8_t* box_rgb, int8_t* mat, uint8_t* rgb, uint32_t* grid,
-                  unsigned long long* l0, unsigned long long* l1, unsigned long long* l2, unsigned long long* l3) {
-    for (int i = 0; i < edit_box_voxels(box); i++) edit_store_voxel<G>(box, i, box_mat, box_rgb, mat, rgb, grid);
-    for (int i = 0; i < edit_cell_count(edit_cells(box, 2)); i++) edit_rebuild_fine(box, i, mat, l0, G);
-    for (int i = 0; i < edit_cell_count(edit_cells(box, 4)); i++) edit_rebuild_coarse(box, 4, i, l0, l1, G);
-    for (int i = 0; i < edit_cell_count(edit_cells(box, 6)); i++) edit_rebuild_coarse(box, 6, i, l1, l2, G);
-    if (G == 256) for (int i = 0; i < edit_cell_count(edit_cells(box, 8)); i++) edit_rebuild_coarse(box, 8, i, l2, l3, G);
-}
 
 extern "C" {
 
@@ -24,8 +14,7 @@ int edit_apply(int G, const int* lo, const int* hi, const int8_t* box_mat, const
     for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
     if ((G != 128 && G != 256) || !edit_box_valid(box, G)) return -1;
     if (edit_box_voxels(box) == 0) return 0;
-    if (G == 256) apply<256>(box, box_mat, box_rgb, mat, rgb, grid, l0, l1, l2, l3);
-    else apply<128>(box, box_mat, box_rgb, mat, rgb, grid, l0, l1, l2, l3);
+    emul_edit(G, box, box_mat, box_rgb, mat, rgb, grid, l0, l1, l2, l3);
     return 0;
 }
 // how many words of the level with cells of (1 << shift) voxels a box touches (the size of the k_edit_* grids)

@@ -1,5 +1,5 @@
 // fill_emul.cpp -- TEST TOOLING: the loops of the k_fill_* kernels (voxel_rt2_amd/csrc/vrt_kernels.hip) and of vrt_fill_triangles
-// (vrt_api.hip) run on the host over the functions of voxel_rt2_amd/csrc/vrt_fill.h: the set-up pass triangle by triangle, the
+// (vrt_scene_ops.hip) run on the host over the functions of voxel_rt2_amd/csrc/vrt_fill.h: the set-up pass triangle by triangle, the
 // rasterise pass grab by grab with the 64 lanes of a wave one after the other, ONE resolve voxel by voxel after every batch, then
 // launch_edit's loops (vrt_edit.h) -- in batches whose size the caller chooses.  tests/fill.py compiles this with g++ and calls it
 // through ctypes.
@@ -8,19 +8,10 @@
 #include <cstring>
 #include <vector>
 #include "../../voxel_rt2_amd/csrc/vrt_fill.h"
+#include "edit_emul.h"
 #include "../../voxel_rt2_amd/csrc/vrt_plan.h"
 
 using namespace vrt;
-
-template <int G>
-static void edit(const EditBox& box, const int8_t* box_mat, const uint8_t* box_rgb, int8_t* mat, uint8_t* rgb, uint32_t* grid,
-                 unsigned long long* l0, unsigned long long* l1, unsigned long long* l2, unsigned long long* l3) {   // launch_edit
-    for (int i = 0; i < edit_box_voxels(box); i++) edit_store_voxel<G>(box, i, box_mat, box_rgb, mat, rgb, grid);
-    for (int i = 0; i < edit_cell_count(edit_cells(box, 2)); i++) edit_rebuild_fine(box, i, mat, l0, G);
-    for (int i = 0; i < edit_cell_count(edit_cells(box, 4)); i++) edit_rebuild_coarse(box, 4, i, l0, l1, G);
-    for (int i = 0; i < edit_cell_count(edit_cells(box, 6)); i++) edit_rebuild_coarse(box, 6, i, l1, l2, G);
-    if (G == 256) for (int i = 0; i < edit_cell_count(edit_cells(box, 8)); i++) edit_rebuild_coarse(box, 8, i, l2, l3, G);
-}
 
 // k_fill_setup + k_fill_raster over one batch
 static void batch(int G, const EditBox& clip, long long m, const vrt_triangle* tris, int grab, std::vector<uint32_t>& toggles, long long& invalid) {
@@ -65,34 +56,18 @@ extern "C" {
 // a time.  result: a vrt_voxelize_result.
 int fill_emul_call(int G, long long n, const vrt_triangle* tris, const int* lo, const int* hi, unsigned voxel, long long chunk, int grab, int8_t* mat, uint8_t* rgb,
                    uint32_t* grid, unsigned long long* l0, unsigned long long* l1, unsigned long long* l2, unsigned long long* l3, vrt_voxelize_result* result) {
-    if (!tris || !lo || !hi || (G != 128 && G != 256) || chunk < 1 || grab < 1) return -1;
-    if (n < 0 || n >= 4294967295LL) return -1;
     EditBox box;
-    for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
-    if (!edit_box_valid(box, G)) return -1;
-    for (long long k = 0; k < n; k++) if (tris[k].reserved0 != 0u || tris[k].reserved1 != 0u) return -1;
-    if (result) memset(result, 0, sizeof(*result));
+    if (const int go = emul_tri_checks(G, n, tris, lo, hi, chunk, grab, box, result); go <= 0) return go;
     const int nv = edit_box_voxels(box);
-    if (nv == 0 || n == 0) return 0;
     std::vector<uint32_t> toggles((size_t)fill_words(box), 0u);
     std::vector<int8_t> box_mat((size_t)nv, (int8_t)0x55);
     std::vector<uint8_t> box_rgb((size_t)nv * 3, (uint8_t)0x55);
-    long long invalid = 0, voxels = 0;
-    int blo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, bhi[3] = {-1, -1, -1};
-    for (long long at = 0; at < n; at += chunk) batch(G, box, chunk < n - at ? chunk : n - at, tris + at, grab, toggles, invalid);
-    for (int i = 0; i < nv; i++) {   // k_fill_resolve
-        if (!fill_resolve_voxel(box, G, i, toggles.data(), voxel, mat, rgb, box_mat.data(), box_rgb.data())) continue;
-        int c[3];
-        edit_box_voxel(box, i, c[0], c[1], c[2]);
-        voxels++;
-        for (int a = 0; a < 3; a++) { if (c[a] < blo[a]) blo[a] = c[a]; if (c[a] > bhi[a]) bhi[a] = c[a]; }
-    }
-    if (G == 256) edit<256>(box, box_mat.data(), box_rgb.data(), mat, rgb, grid, l0, l1, l2, l3);
-    else edit<128>(box, box_mat.data(), box_rgb.data(), mat, rgb, grid, l0, l1, l2, l3);
-    if (result) {
-        result->voxels = voxels; result->invalid = invalid;
-        if (voxels) for (int a = 0; a < 3; a++) { result->lo[a] = blo[a]; result->hi[a] = bhi[a] + 1; }
-    }
+    EmulTally tally;
+    for (long long at = 0; at < n; at += chunk) batch(G, box, chunk < n - at ? chunk : n - at, tris + at, grab, toggles, tally.invalid);
+    for (int i = 0; i < nv; i++)   // k_fill_resolve
+        if (fill_resolve_voxel(box, G, i, toggles.data(), voxel, mat, rgb, box_mat.data(), box_rgb.data())) tally.add(box, i);
+    emul_edit(G, box, box_mat.data(), box_rgb.data(), mat, rgb, grid, l0, l1, l2, l3);   // launch_edit
+    tally.store(result);
     return 0;
 }
 // fill_column_in / fill_first_cell for one triangle and n columns (int32[n][2]): in[i] = 1 / 0 (-1 throughout for an invalid triangle),

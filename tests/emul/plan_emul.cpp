@@ -44,5 +44,10 @@ int plan_wait(unsigned target, unsigned lane_last_seq, int gate_present, int sig
 int plan_blocks(int all_blocks, int grid_div) { return plan_partial_blocks(all_blocks, grid_div); }
 int plan_set(unsigned pipe_seq, int n_sets) { return plan_set_of(pipe_seq, n_sets); }
 int plan_lane(unsigned pipe_seq, int n_streams) { return plan_lane_of(pipe_seq, n_streams); }
+// out: {mat_at, rgb_at, entries_at, heads_at, bytes} of the triangle edits' scratch
+void plan_tri(long long head_bytes, long long nv, long long batch, long long* out) {
+    const TriLayout l = plan_tri_layout((size_t)head_bytes, (size_t)nv, (size_t)batch);
+    out[0] = (long long)l.mat_at; out[1] = (long long)l.rgb_at; out[2] = (long long)l.entries_at; out[3] = (long long)l.heads_at; out[4] = (long long)l.bytes;
+}
 
 }  // extern "C"

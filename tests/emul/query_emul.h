@@ -1,6 +1,6 @@
 // query_emul.h -- TEST TOOLING: what the host builds of the three scene queries share (cast_emul.cpp, radiance_emul.cpp, sensor_emul.cpp).
 // The staged view of the pyramid, the scene record the tests fill and its conversion to what the device functions read, the choice of
-// view, the block loop of a sampled query -- driven the way vrt_api.hip (sampled_query) and the kernels of vrt_kernels.hip drive it,
+// view, the block loop of a sampled query -- driven the way vrt_scene_ops.hip (sampled_query) and the kernels of vrt_kernels.hip drive it,
 // through the same traits (voxel_rt2_amd/csrc/vrt_query.h) -- and the small scene of the stand-alone programs.
 #pragma once
 #include <cstring>
@@ -69,7 +69,7 @@ static void frame_params_base(FrameParams& fp) {
 }
 
 // What every query reads of a scene record (CastScene of cast_emul.cpp, RadScene) -- of the frame parameters the floor (height, colour,
-// material) and voxel_edges, as query_inputs (vrt_api.hip) lists them; of the scene the pyramid, the texels, the culling box.
+// material) and voxel_edges, as query_inputs (vrt_scene_ops.hip) lists them; of the scene the pyramid, the texels, the culling box.
 template <class Scene>
 static void scene_common(const Scene& s, FrameParams& fp, SceneData& sc) {
     frame_params_base(fp);
@@ -121,7 +121,7 @@ static void scene_sampled(const RadScene& s, FrameParams& fp, SceneData& sc) {
     sc.sky.res = s.sky_res; sc.sky.fres = s.sky_res > 0 ? (float)(1.0 / (double)s.sky_res) : 0.0f;
 }
 
-// A sampled query's chunk loop over one block of n records (sampled_query, vrt_api.hip), the item kernels' numbering and k_fold_query's
+// A sampled query's chunk loop over one block of n records (sampled_query, vrt_scene_ops.hip), the item kernels' numbering and k_fold_query's
 // fold.  per: whole samples a chunk (0: plan_query_chunk's).  item(in, sample, out): the value of one (record, sample) item -- zero for
 // an invalid record -- and whatever the item kernel writes to the output record directly.
 template <class Q, class ItemFn>

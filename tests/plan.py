@@ -28,6 +28,7 @@ def lib():
         _lib.plan_wait.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_int]
         _lib.plan_set.argtypes = _lib.plan_lane.argtypes = [C.c_uint, C.c_int]
         _lib.plan_variant.argtypes = [C.POINTER(C.c_int)]
+        _lib.plan_tri.argtypes = [C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(C.c_longlong)]
     return _lib
 
 

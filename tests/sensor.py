@@ -361,7 +361,7 @@ def blocks(n):
 
 
 def chunks(n_sensors, n_samples):
-    """[(s0, count)] as sampled_query (vrt_api.hip) cuts a block's samples: plan_query_chunk whole samples at a time."""
+    """[(s0, count)] as sampled_query (vrt_scene_ops.hip) cuts a block's samples: plan_query_chunk whole samples at a time."""
     per = lib().sensor_emul_chunk(n_sensors, n_samples)
     return [(s0, min(per, n_samples - s0)) for s0 in range(0, n_samples, max(per, 1))]
 

@@ -17,8 +17,8 @@ on the host path and on the device path.  The families (tests/fill.py), each the
   halves           the box in two calls along z == the box at once;  carve: mat = 0 out of a solid block;  negative: a negative byte
 Then: 256^3, a real chunk boundary on the host path and a real batch boundary on the device path (a closed cube's twelve triangles
 straddle it), a grid-spanning pair of triangles under a full-grid box, ordering against queries, launches in flight,
-vrt_update_voxels and vrt_voxelize_triangles on the same stream, the error codes, the facade (shell=True included) and
-examples/fill_mesh.py."""
+vrt_update_voxels and vrt_voxelize_triangles on the same stream, the scratch buffer taken in turns with the surface pass, the error
+codes, the facade (shell=True included) and examples/fill_mesh.py."""
 import ctypes as C
 import os
 import runpy
@@ -26,6 +26,7 @@ import runpy
 import numpy as np
 import pytest
 
+import distance as D
 import edit as E
 import fill as FL
 import orc
@@ -265,6 +266,60 @@ def test_queries_launches_and_other_edits_are_ordered_against_the_call():
     finally:
         for s in (e, u, f):
             s.close()
+
+
+@pytest.mark.parametrize("path", ["host", "device"])
+def test_fill_and_surface_pass_take_turns_in_the_shared_scratch(path):
+    """The two triangle edits cut one buffer of the context up with one layout (plan_tri_layout), whose head region is toggle words for
+    one and ownership words for the other.  On a fresh 128^3 context per path: a fill into 5 x 7 x 40 (nv = 1400, no multiple of 256; two
+    toggle words a column), a surface pass into 24^3 (the buffer grows, the head is laid out the other way), a fill into 9 x 5 x 33 (the
+    larger buffer under the first layout again), a vrt_update_voxels of a 3^3 host box, and a vrt_distance_field over the union.  After
+    every step the whole grid and the step's result equal what the host emulations leave for the same steps, byte for byte."""
+    import torch
+    device = path == "device"
+    mat0, rgb0, _ = R.scene("sunlit")
+    fill1 = (FL.mesh(128, [(40.3, 50.4, 31.2), (44.6, 51.1, 45.7), (41.2, 56.5, 52.3), (43.1, 53.3, 68.6)], FL.TET), (40, 50, 30), (45, 57, 70))
+    surface = (V.triangles(128, [[(45.2, 53.1, 41.3), (66.7, 55.4, 47.9), (50.3, 74.8, 62.2)], [(67.5, 75.5, 40.5), (44.5, 75.5, 63.5), (67.5, 52.5, 63.5)],
+                                 [(30.0, 60.2, 50.1), (90.0, 61.7, 52.4), (55.1, 64.9, 90.0)]]), (44, 52, 40), (68, 76, 64))
+    fill2 = (FL.mesh(128, [(38.4, 54.3, 29.1), (46.5, 55.2, 36.6), (39.7, 58.6, 48.2), (45.2, 56.1, 60.3)], FL.TET), (38, 54, 28), (47, 59, 61))
+    box = E._pattern((43, 55, 50), (46, 58, 53), seed=5, m=23)
+    lo, hi = (38, 50, 28), (68, 76, 70)
+    for (_, l, h), shape in ((fill1, (5, 7, 40)), (surface, (24, 24, 24)), (fill2, (9, 5, 33)), ((None,) + box[:2], (3, 3, 3))):
+        assert tuple(b - a for a, b in zip(l, h)) == shape and all(lo[a] <= l[a] and h[a] <= hi[a] for a in range(3))
+    keep = []
+
+    def given(tris):
+        if not device:
+            return tris
+        keep.append(torch.from_numpy(np.ascontiguousarray(tris).view(np.uint8).reshape(-1).copy()).cuda())
+        torch.cuda.synchronize()                      # the tensor is written on torch's stream, read on the context's
+        return keep[-1]
+    hg, s = E.HostGrid(mat0, rgb0), fresh("sunlit", mat0, rgb0)
+    try:
+        def step(label, got, rc_want):
+            rc, want = rc_want
+            assert rc == 0 and want["voxels"] > 0 and V.same_result(got, want), f"{path} path, {label}: result {got} != {want}"
+            assert_grid(s, hg.mat, hg.rgb, f"{path} path, {label}")
+        step("fill into 5 x 7 x 40", s.fill_triangles(given(fill1[0]), *fill1[1:], FL.PAY), FL.emul_call(hg, *fill1, FL.PAY))
+        step("surface pass into 24^3", s.voxelize_triangles(given(surface[0]), *surface[1:]), V.emul_call(hg, *surface, once=device))
+        step("fill into 9 x 5 x 33", s.fill_triangles(given(fill2[0]), *fill2[1:], FL.PAY), FL.emul_call(hg, *fill2, FL.PAY))
+        s.update_voxels(*box)
+        assert hg.apply(*box) == 0
+        assert_grid(s, hg.mat, hg.rgb, f"{path} path, update of a 3^3 box")
+        rc, d2, near = D.emul_call(hg.mat, lo, hi, 400)
+        assert rc == 0 and (d2 == 0).any() and (d2 > 0).any()
+        if device:
+            out = tuple(torch.full(d2.shape, 0x5A5A5A5A, dtype=torch.int32, device="cuda") for _ in range(2))
+            torch.cuda.synchronize()
+            s.distance_field(lo, hi, 400, nearest=True, out=out)
+            s.sync()
+            got = tuple(t.cpu().numpy() for t in out)
+        else:
+            got = s.distance_field(lo, hi, 400, nearest=True)
+        D.check(*got, (d2, near), f"{path} path, distance field over the union")
+        assert_grid(s, hg.mat, hg.rgb, f"{path} path, after the distance field")
+    finally:
+        s.close()
 
 
 def test_error_codes_empty_calls_and_a_null_result():

@@ -1,6 +1,7 @@
 """The launch pipeline's decisions (voxel_rt2_amd/csrc/vrt_plan.h: render kernel variant, shape, deferral depth, fused sample count,
 timer period, dispatch gate, workgroups, set and lane of a launch) as plain functions, compiled for the host (tests/emul/plan_emul.cpp).  The expected
 values are literals: what the library decided before the decisions were lifted out of vrt_accumulate.  No GPU."""
+import ctypes as C
 import itertools
 
 import pytest
@@ -164,3 +165,24 @@ def test_render_variant_every_combination():
             assert got == {k for k, on in want.items() if on}, (W, H, depth, render, cull_knob, fused, restir, instrumented, timed, oob, cull_active, dense, emits)
             n += 1
     assert n == 5 * 4 * 3 * 3 * 2 ** 7
+
+
+def test_tri_layout():
+    """plan_tri_layout, the one layout of the scratch vrt_voxelize_triangles and vrt_fill_triangles share: regions in order and apart, each
+    as large as what it holds and aligned for what is stored there, and the buffer no more than 255 bytes larger than the two layouts
+    it replaces asked for (written out here as they stood)."""
+    up = lambda v: (v + 255) & ~255
+    n = 0
+    for head, nv, batch in itertools.product((4, 252, 256, 4 * 315), (1, 255, 256, 315, 128 ** 3), (1, 3, 1 << 18, 1 << 20)):
+        out = (C.c_longlong * 5)()
+        lib().plan_tri(head, nv, batch, out)
+        mat_at, rgb_at, entries_at, heads_at, size = out
+        key = (head, nv, batch)
+        assert 0 < mat_at < rgb_at < entries_at < heads_at < size, key
+        assert mat_at >= head and rgb_at - mat_at >= nv and entries_at - rgb_at >= 3 * nv and heads_at - entries_at >= 16 * batch, key
+        assert entries_at % 16 == 0 and heads_at % 8 == 0 and size - heads_at >= 256, key
+        assert size <= up(up(head) + up(nv) + 3 * nv) + 16 * batch + 256 + 255, key          # the fill's layout, head = 4 * words
+        if head == 4 * nv:
+            assert size <= up(4 * nv + up(nv) + 3 * nv) + 16 * batch + 256 + 255, key         # the surface pass's
+        n += 1
+    assert n == 4 * 5 * 4

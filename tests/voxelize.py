@@ -36,7 +36,7 @@ def lib():
     global _lib
     if _lib is None:
         csrc = os.path.join(ROOT, "voxel_rt2_amd", "csrc")
-        deps = [_SRC, os.path.join(ROOT, "include", "vrt_api.h")] + [os.path.join(csrc, f) for f in ("vrt_voxelize.h", "vrt_edit.h", "vrt_trace.h", "vrt_types.h", "vrt_plan.h")]
+        deps = [_SRC, os.path.join(HERE, "emul", "edit_emul.h"), os.path.join(ROOT, "include", "vrt_api.h")] + [os.path.join(csrc, f) for f in ("vrt_voxelize.h", "vrt_edit.h", "vrt_trace.h", "vrt_types.h", "vrt_plan.h")]
         if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
             subprocess.run(GCC + ["-fPIC", "-shared", "-o", _SO, _SRC], check=True, capture_output=True)
         _lib = C.CDLL(_SO)

@@ -6,7 +6,9 @@ labels renumbered in order of appearance (a function's labels carry its number i
 
     python tools/asm_diff.py [REV] [name-substring ...]         REV: default HEAD~1
 
-Prints one line per function that differs or that only one side has, then the counts; exit status 1 if a function both have differs."""
+Prints one line per function that differs or that only one side has, then the counts; exit status 1 if a function both have differs.
+A function that holds the same multiset of instruction lines in another order (the scheduler swapping independent instructions) is
+reported apart from one whose instructions differ; both count for the exit status."""
 import os
 import re
 import subprocess
@@ -66,7 +68,7 @@ def main():
         subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)
         a, b = functions(listing(old, os.path.join(tmp, "a.s"))), functions(listing(ROOT, os.path.join(tmp, "b.s")))
     pick = lambda n: not args or any(s in n for s in args)
-    same = differ = 0
+    same = reordered = differ = 0
     for n in sorted(set(a) | set(b)):
         if not pick(n):
             continue
@@ -74,11 +76,14 @@ def main():
             print(f"only in {'this tree' if n in b else rev}: {n[:150]}")
         elif normal(a[n]) == normal(b[n]):
             same += 1
+        elif sorted(normal(a[n])) == sorted(normal(b[n])):   # (labels are numbered in order of appearance: a moved BLOCK is not this)
+            reordered += 1
+            print(f"SAME INSTRUCTIONS, DIFFERENT ORDER ({len(a[n])} instructions): {n[:150]}")
         else:
             differ += 1
             print(f"DIFFERS ({len(a[n])} -> {len(b[n])} instructions): {n[:150]}")
-    print(f"{same} functions identical to {rev}'s, {differ} differ")
-    return 1 if differ else 0
+    print(f"{same} functions identical to {rev}'s, {reordered} hold the same instructions in another order, {differ} differ")
+    return 1 if differ or reordered else 0
 
 
 if __name__ == "__main__":

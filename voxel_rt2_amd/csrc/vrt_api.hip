@@ -1,5 +1,7 @@
-// vrt_api.hip -- the C ABI of include/vrt_api.h: context creation and teardown, uploads, the sky entry points, the fetches, the stats.
-// (The context itself: vrt_ctx.h.  vrt_accumulate and everything that sequences launches: vrt_pipeline.hip, #included below.)
+// vrt_api.hip -- the C ABI of include/vrt_api.h: context creation and teardown, uploads, the sky entry points, the fetches, the probes,
+// the stats.
+// (The context itself: vrt_ctx.h.  vrt_accumulate and everything that sequences launches: vrt_pipeline.hip; the calls on a prepared scene --
+// the box edit, the queries, vrt_fetch_voxels, the distance field, the triangle edits: vrt_scene_ops.hip.  Both #included below.)
 //
 // Replaces the host side of the reference's Renderer (renderer/pathtracer.py:28-136 field
 // allocation, 139-150 / 246-287 setters, 314-329 prepare + sky steps, 664-668 reset, 1310-1323
@@ -107,6 +109,7 @@ static void sun_of(const vrt_ctx* c, f3& dir, f3& col, float& cosm) {
 }
 
 #include "vrt_pipeline.hip"
+#include "vrt_scene_ops.hip"
 
 extern "C" {
 
@@ -377,10 +380,7 @@ int vrt_prepare(vrt_ctx* c) {
         float box[8];
         HIP_TRY(hipMemcpyAsync(box, c->d_cull, sizeof(box), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));   // (source and destination are on this stack frame)
-        c->cull_active = box[6] != 0.0f;
-        // at least half of the 4x4x4 bricks hold a voxel: a dense grid (shadow rays end after a step or two: launch_render_pool)
-        c->dense_grid = box[7] >= 0.5f;
-        if (c->knobs.dense >= 0) c->dense_grid = c->knobs.dense != 0;   // A/B
+        note_cull_record(c, box);
     }
     if (c->scene.use_physical_sky == 1) {
         SkyPrecompute sp = make_sky(c);
@@ -395,365 +395,6 @@ int vrt_prepare(vrt_ctx* c) {
     }
     c->prepared = true;
     return VRT_OK;
-}
-// The culling record's host side behind an edit, as vrt_prepare reads it behind its own k_cull_box: is there anything to cull, is the
-// grid dense.  One synchronisation: source and destination of the copy are on this stack frame.
-static int read_cull_record(vrt_ctx* c) {
-    float box[8];
-    HIP_TRY(hipMemcpyAsync(box, c->d_cull, sizeof(box), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(sync_guarded(c, c->stream));
-    c->cull_active = box[6] != 0.0f;
-    // at least half of the 4x4x4 bricks hold a voxel: a dense grid (shadow rays end after a step or two: launch_render_pool)
-    c->dense_grid = box[7] >= 0.5f;
-    if (c->knobs.dense >= 0) c->dense_grid = c->knobs.dense != 0;   // A/B
-    return VRT_OK;
-}
-// Replace the voxels of the box [lo, hi) of a prepared context and bring what vrt_prepare derives from the voxels up to date, at the
-// box's cost (launch_edit).  Ordered like vrt_upload_voxels: the pending accumulation first, the work on the context's stream --
-// behind every render launch queued so far, whose pass is on it -- and main_dirty holds later launches back until it is done.
-int vrt_update_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], const void* mat, const void* rgb, int on_device) {
-    if (!c || !lo || !hi || !mat || !rgb) return fail(VRT_E_INVALID, "null argument");
-    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
-    EditBox box;
-    for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
-    if (!edit_box_valid(box, c->cfg.grid_res)) return fail(VRT_E_INVALID, "the box must satisfy 0 <= lo <= hi <= grid_res on every axis");
-    if (!c->prepared) return fail(VRT_E_STATE, "vrt_update_voxels edits a prepared grid: call vrt_prepare first (also after vrt_upload_voxels)");
-    const size_t nv = (size_t)edit_box_voxels(box);
-    if (nv == 0) return VRT_OK;
-    if (enter(c) != VRT_OK) return VRT_E_DEVICE;
-    const int8_t* box_mat = (const int8_t*)mat;
-    const uint8_t* box_rgb = (const uint8_t*)rgb;
-    if (!on_device) {
-        const size_t rgb_at = (nv + 255) & ~(size_t)255, need = rgb_at + 3 * nv;
-        if (c->edit_stage_bytes < need) {   // (hipFree waits for the device: no kernel is still reading the old one)
-            HIP_TRY(dfree(c, &c->d_edit_stage));
-            c->edit_stage_bytes = 0;
-            HIP_TRY(dmalloc(c, &c->d_edit_stage, need));
-            c->edit_stage_bytes = need;
-        }
-        c->main_dirty = true;
-        HIP_TRY(hipMemcpyAsync(c->d_edit_stage, mat, nv, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->d_edit_stage + rgb_at, rgb, 3 * nv, hipMemcpyHostToDevice, c->stream));
-        box_mat = (const int8_t*)c->d_edit_stage;
-        box_rgb = c->d_edit_stage + rgb_at;
-    }
-    c->main_dirty = true;
-    HIP_TRY(launch_edit(c->stream, c->cfg.grid_res, box, box_mat, box_rgb, c->d_mat, c->d_rgb, c->d_grid, c->d_l0, c->d_l1, c->d_l2, c->d_l3,
-                        c->d_l0c, c->d_l0c_base, c->d_cull));
-    return read_cull_record(c);   // (the wait also ends the loan of the host arrays)
-}
-// ---- asking the scene: vrt_cast_rays, vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes, vrt_fetch_voxels ------------------------------
-// All READ scene data (pyramid, texels, stored voxels), on the context's stream: behind every edit queued so far, ahead of every
-// later one.  Render launches read the same data on their own streams and nothing here writes what they or their passes touch, so
-// neither main_dirty nor the pending accumulation is concerned: no enter(), no flush.
-static int ensure_cast_stage(vrt_ctx* c, size_t need) {
-    if (c->cast_stage_bytes >= need) return VRT_OK;
-    HIP_TRY(dfree(c, &c->d_cast_stage));   // (hipFree waits for the device: no kernel is still using the old one)
-    c->cast_stage_bytes = 0;
-    HIP_TRY(dmalloc(c, &c->d_cast_stage, need));
-    c->cast_stage_bytes = need;
-    return VRT_OK;
-}
-extern "C++" {   // (templates below)
-// What every query reads.  Of the frame parameters: the floor (floor_height, floor_color, floor_material) and voxel_edges; the sampled
-// queries also the background, the light (light_dir, light_color, light_cos_max, light_weight), the sky switch (use_sky), max_depth and
-// the seed.  Of the scene: the pyramid, the texels and the culling box; the sampled queries also the materials and the sky tables.
-// Nothing else: not the camera (matrices, camera_pos, taa_jitter, camera_is_moving, render_scale, max_accum_frames), not the pixel grid
-// (W, H, inv_res, row0 / row1, the stripe fields), not exposure, not the frame counter -- the host emulation hands the same functions a
-// record with exactly the listed fields set and every other field poisoned, and gets the same bytes (tests/emul/query_emul.h), and the
-// device answers the oracle's records from contexts in every frame state (tests/test_gpu_query_states.py).
-struct QueryInputs { FrameParams fp; SceneData sc; };
-static QueryInputs query_inputs(vrt_ctx* c) {
-    QueryInputs q{make_frame_params(c), make_scene_data(c)};
-    // the scene's box, whatever the render launches count: culled rays are misses either way (cast_row); not with the reference's
-    // indexing, where a ray clear of every solid voxel can still "hit" outside the grid (plan_render_variant)
-    q.sc.cull = c->d_cull + (c->cull_active && !c->ref_oob && c->knobs.cull != 0 ? 0 : 8);
-    return q;
-}
-// A query's host path: the caller's n records, `block` at a time, copied to the staging buffer, worked on by queue(m, d_in, d_out) --
-// which queues on the context's stream -- and copied back; then the wait.
-template <class In, class Out, class Queue>
-static int staged_query(vrt_ctx* c, long long n, long long block, const In* in, Out* out, Queue queue) {
-    if (ensure_cast_stage(c, (size_t)block * (sizeof(In) + sizeof(Out))) != VRT_OK) return VRT_E_DEVICE;
-    In* d_in = (In*)c->d_cast_stage;
-    Out* d_out = (Out*)(c->d_cast_stage + (size_t)block * sizeof(In));
-    for (long long at = 0; at < n; at += block) {   // (stream order lets block k + 1 reuse what block k's copy back has read)
-        const long long m = std::min(block, n - at);
-        HIP_TRY(hipMemcpyAsync(d_in, in + at, (size_t)m * sizeof(In), hipMemcpyHostToDevice, c->stream));
-        if (queue(m, (const In*)d_in, d_out) != VRT_OK) return VRT_E_DEVICE;
-        HIP_TRY(hipMemcpyAsync(out + at, d_out, (size_t)m * sizeof(Out), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host arrays)
-    return VRT_OK;
-}
-// The scratch plane of vrt_trace_radiance, vrt_gather_irradiance and vrt_gather_probes: a work counter (256 bytes) and VRT_RADIANCE_ITEMS
-// item values of the first, VRT_SENSOR_ITEMS records of the second or VRT_PROBE_ITEMS items of the third -- the same bytes; all run on the
-// context's stream, whose order lets them share it.
-static_assert((size_t)VRT_SENSOR_ITEMS * sizeof(vrt_irradiance) <= (size_t)VRT_RADIANCE_ITEMS * sizeof(f3), "the sensor plane must fit the radiance plane");
-static_assert(sizeof(vrt_irradiance) == VRT_SENSOR_ITEM_BYTES && sizeof(vrt_sensor) == 32, "record sizes of include/vrt_api.h");
-static_assert((size_t)VRT_PROBE_ITEMS * sizeof(ProbeItem) <= (size_t)VRT_RADIANCE_ITEMS * sizeof(f3), "the probe plane must fit the radiance plane");
-static_assert(sizeof(ProbeItem) == VRT_PROBE_ITEM_BYTES && sizeof(vrt_probe) == 16 && sizeof(vrt_sh_probe) == 128, "record sizes of include/vrt_api.h");
-static_assert(VRT_PROBE_ITEMS >= (1 << 18), "one sample of a full block (plan_query_rays) must fit the probe plane");
-// A sampled query (vrt_query.h) reads what vrt_cast_rays reads plus the materials and the sky tables, and is ordered the same way.
-// Blocks of records (plan_query_rays), a block's samples in chunks of whole samples (plan_query_chunk): one item launch and one fold
-// launch a chunk, all on the context's stream, where stream order lets every chunk reuse the scratch plane.  name, noun: the entry
-// point's, for its messages.
-template <class Q>
-static int sampled_query(vrt_ctx* c, const char* name, const char* noun, int64_t n, const typename Q::In* in, int n_samples, uint32_t first_frame,
-                         typename Q::Out* out, int on_device) {
-    if (!c || !in || !out) return fail(VRT_E_INVALID, "null argument");
-    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
-    if (n_samples < 1 || n_samples > VRT_RADIANCE_MAX_SAMPLES) return fail(VRT_E_INVALID, "n_samples must be 1 .. VRT_RADIANCE_MAX_SAMPLES");
-    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
-    if (!c->prepared) return fail(VRT_E_STATE, std::string(name) + " asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
-    if (n == 0) return VRT_OK;
-    if constexpr (Q::has_reserved)
-        if (!on_device)
-            for (int64_t k = 0; k < n; k++) if (in[k].reserved != 0u) return fail(VRT_E_INVALID, std::string("a ") + noun + "'s `reserved` field must be 0");
-    HIP_TRY(hipSetDevice(c->device));
-    const QueryInputs q = query_inputs(c);
-    if (!c->d_radiance_plane) HIP_TRY(dmalloc(c, &c->d_radiance_plane, 256 + (size_t)VRT_RADIANCE_ITEMS * sizeof(f3)));   // [0]: the work counter
-    auto queue = [&](long long m, const typename Q::In* d_in, typename Q::Out* d_out) -> int {
-        const int per = plan_query_chunk(Q::max_items, m, n_samples);
-        for (int s0 = 0; s0 < n_samples; s0 += per) {
-            const int count = std::min(per, n_samples - s0);
-            const bool staged = plan_cast_staged(m * count, c->knobs.cast_view);   // on the items of THIS launch: a short last chunk chooses for itself
-            HIP_TRY(launch_sampled_query<Q>(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, q.fp, q.sc, m, s0, count, n_samples, first_frame, d_in,
-                                            (typename Q::Item*)(c->d_radiance_plane + 256), d_out, (unsigned*)c->d_radiance_plane));
-        }
-        return VRT_OK;
-    };
-    const long long block = plan_query_rays((long long)n);
-    if (!on_device) return staged_query(c, (long long)n, block, in, out, queue);
-    for (long long at = 0; at < (long long)n; at += block)
-        if (queue(std::min(block, (long long)n - at), in + at, out + at) != VRT_OK) return VRT_E_DEVICE;
-    return VRT_OK;
-}
-}  // extern "C++"
-int vrt_cast_rays(vrt_ctx* c, int64_t n, const vrt_ray* rays, vrt_ray_hit* hits, int on_device) {
-    if (!c || !rays || !hits) return fail(VRT_E_INVALID, "null argument");
-    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
-    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
-    if (!c->prepared) return fail(VRT_E_STATE, "vrt_cast_rays asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
-    if (n == 0) return VRT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    const QueryInputs q = query_inputs(c);
-    const bool staged = plan_cast_staged((long long)n, c->knobs.cast_view);   // on the whole batch, however the host path cuts it
-    auto queue = [&](long long m, const vrt_ray* d_rays, vrt_ray_hit* d_hits) -> int {
-        HIP_TRY(launch_cast_rays(c->stream, c->cfg.grid_res, staged, c->ref_oob, c->n_cu, q.fp, q.sc, m, d_rays, d_hits));
-        return VRT_OK;
-    };
-    if (on_device) return queue((long long)n, rays, hits);
-    return staged_query(c, (long long)n, std::min<long long>(plan_cast_chunk(), (long long)n), rays, hits, queue);
-}
-static_assert(sizeof(vrt_box_sweep) == 48 && sizeof(vrt_sweep_hit) == 32, "record sizes of include/vrt_api.h");
-int vrt_sweep_boxes(vrt_ctx* c, int64_t n, const vrt_box_sweep* boxes, vrt_sweep_hit* hits, int on_device) {
-    if (!c || !boxes || !hits) return fail(VRT_E_INVALID, "null argument");
-    if (n < 0) return fail(VRT_E_INVALID, "n must not be negative");
-    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
-    if (!c->prepared) return fail(VRT_E_STATE, "vrt_sweep_boxes asks a prepared scene: call vrt_prepare first (also after vrt_upload_voxels)");
-    if (n == 0) return VRT_OK;
-    if (!on_device)
-        for (int64_t k = 0; k < n; k++) if (boxes[k].reserved != 0u) return fail(VRT_E_INVALID, "a box's `reserved` field must be 0");
-    HIP_TRY(hipSetDevice(c->device));
-    QueryInputs q = query_inputs(c);
-    // the scene's box in either indexing mode: only cells inside the grid exist for a sweep, so no box "meets" anything outside it
-    q.sc.cull = c->d_cull + (c->knobs.cull != 0 ? 0 : 8);
-    auto queue = [&](long long m, const vrt_box_sweep* d_boxes, vrt_sweep_hit* d_hits) -> int {
-        HIP_TRY(launch_sweep_boxes(c->stream, c->cfg.grid_res, c->n_cu, q.fp.floor_height, q.sc, m, d_boxes, d_hits));
-        return VRT_OK;
-    };
-    if (on_device) return queue((long long)n, boxes, hits);
-    return staged_query(c, (long long)n, std::min<long long>(plan_sweep_chunk(), (long long)n), boxes, hits, queue);
-}
-int vrt_trace_radiance(vrt_ctx* c, int64_t n, const vrt_path_ray* rays, int n_samples, uint32_t first_frame, vrt_radiance* out, int on_device) {
-    return sampled_query<RadianceQuery>(c, "vrt_trace_radiance", "ray", n, rays, n_samples, first_frame, out, on_device);
-}
-int vrt_gather_irradiance(vrt_ctx* c, int64_t n, const vrt_sensor* sensors, int n_samples, uint32_t first_frame, vrt_irradiance* out, int on_device) {
-    return sampled_query<SensorQuery>(c, "vrt_gather_irradiance", "sensor", n, sensors, n_samples, first_frame, out, on_device);
-}
-int vrt_gather_probes(vrt_ctx* c, int64_t n, const vrt_probe* probes, int n_samples, uint32_t first_frame, vrt_sh_probe* out, int on_device) {
-    return sampled_query<ProbeQuery>(c, "vrt_gather_probes", "probe", n, probes, n_samples, first_frame, out, on_device);
-}
-int vrt_fetch_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], void* mat, void* rgb, int on_device) {
-    if (!c || !lo || !hi || !mat || !rgb) return fail(VRT_E_INVALID, "null argument");
-    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
-    EditBox box;
-    for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
-    if (!edit_box_valid(box, c->cfg.grid_res)) return fail(VRT_E_INVALID, "the box must satisfy 0 <= lo <= hi <= grid_res on every axis");
-    if (!c->prepared) return fail(VRT_E_STATE, "vrt_fetch_voxels reads a prepared grid: call vrt_prepare first (also after vrt_upload_voxels)");
-    const size_t nv = (size_t)edit_box_voxels(box);
-    if (nv == 0) return VRT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    if (on_device) {
-        HIP_TRY(launch_fetch_voxels(c->stream, c->cfg.grid_res, box, c->d_mat, c->d_rgb, (int8_t*)mat, (uint8_t*)rgb));
-        return VRT_OK;
-    }
-    const size_t rgb_at = (nv + 255) & ~(size_t)255;
-    if (ensure_cast_stage(c, rgb_at + 3 * nv) != VRT_OK) return VRT_E_DEVICE;
-    HIP_TRY(launch_fetch_voxels(c->stream, c->cfg.grid_res, box, c->d_mat, c->d_rgb, (int8_t*)c->d_cast_stage, c->d_cast_stage + rgb_at));
-    HIP_TRY(hipMemcpyAsync(mat, c->d_cast_stage, nv, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(rgb, c->d_cast_stage + rgb_at, 3 * nv, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(sync_stream_only(c, c->stream));
-    return VRT_OK;
-}
-// The distance field of the stored voxels over the box [lo, hi) (vrt_distance.h): three line passes on the context's stream, reading
-// d_mat as vrt_fetch_voxels does -- so the same ordering, no enter(), no flush.  The scratch is the call's own buffer: every call runs
-// on the context's stream, where stream order lets the next call reuse it, and the host path's copies out of it are waited for here.
-int vrt_distance_field(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], int32_t max_d2, uint32_t flags, void* d2, void* nearest, int on_device) {
-    if (!c || !lo || !hi || !d2) return fail(VRT_E_INVALID, "null argument");
-    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
-    EditBox box;
-    for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
-    if (!edit_box_valid(box, c->cfg.grid_res)) return fail(VRT_E_INVALID, "the box must satisfy 0 <= lo <= hi <= grid_res on every axis");
-    if (max_d2 < 0 || max_d2 > VRT_DIST_MAX_D2) return fail(VRT_E_INVALID, "max_d2 must be 0 .. VRT_DIST_MAX_D2");
-    if ((flags & ~(uint32_t)VRT_DIST_TO_EMPTY) != 0u) return fail(VRT_E_INVALID, "unknown flag bits");
-    if (!c->prepared) return fail(VRT_E_STATE, "vrt_distance_field reads a prepared grid: call vrt_prepare first (also after vrt_upload_voxels)");
-    const size_t nv = (size_t)edit_box_voxels(box);
-    if (nv == 0) return VRT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    const DistBox p = dist_plan_box(box, c->cfg.grid_res, max_d2, flags);
-    const DistLayout l = plan_distance_layout((size_t)dist_len(p.grown, 0), (size_t)dist_len(p.grown, 1), (size_t)dist_len(box, 0), (size_t)dist_len(box, 1),
-                                              (size_t)dist_len(box, 2), nearest != nullptr, !on_device);
-    if (c->dist_bytes < l.bytes) {   // (hipFree waits for the device: no kernel is still using the old one)
-        HIP_TRY(dfree(c, &c->d_dist));
-        c->dist_bytes = 0;
-        HIP_TRY(dmalloc(c, &c->d_dist, l.bytes));
-        c->dist_bytes = l.bytes;
-    }
-    const DistScratch s{(int*)(c->d_dist + l.a_at), (int*)(c->d_dist + l.b_at), c->d_dist + l.cz_at, c->d_dist + l.cy_at};
-    if (on_device) {
-        HIP_TRY(launch_distance_field(c->stream, c->cfg.grid_res, p, c->d_mat, s, (int*)d2, (int*)nearest));
-        return VRT_OK;
-    }
-    int* d_d2 = (int*)(c->d_dist + l.d2_at);
-    int* d_nearest = nearest ? (int*)(c->d_dist + l.nearest_at) : nullptr;
-    HIP_TRY(launch_distance_field(c->stream, c->cfg.grid_res, p, c->d_mat, s, d_d2, d_nearest));
-    HIP_TRY(hipMemcpyAsync(d2, d_d2, 4 * nv, hipMemcpyDeviceToHost, c->stream));
-    if (nearest) HIP_TRY(hipMemcpyAsync(nearest, d_nearest, 4 * nv, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(sync_stream_only(c, c->stream));
-    return VRT_OK;
-}
-// Voxelise triangles into the box [lo, hi) of a prepared context (vrt_voxelize.h): ownership of the box's voxels is settled batch by
-// batch on the device (launch_voxelize_batch), resolved into box arrays (launch_voxelize_resolve), and those go through launch_edit
-// like any other box -- ordered and synchronised exactly as vrt_update_voxels.  The host path stages plan_voxelize_chunk() triangles
-// at a time in the query staging buffer and resolves each chunk's owners while its triangles are still there; the device path
-// resolves once, over the caller's array.
-static_assert(sizeof(vrt_triangle) == 48 && sizeof(vrt_voxelize_result) == 40 && sizeof(VoxResult) == 40 && sizeof(VoxEntry) == 16, "record sizes of include/vrt_api.h");
-int vrt_voxelize_triangles(vrt_ctx* c, int64_t n, const vrt_triangle* tris, const int32_t lo[3], const int32_t hi[3], vrt_voxelize_result* result, int on_device) {
-    if (!c || !tris || !lo || !hi) return fail(VRT_E_INVALID, "null argument");
-    if (n < 0 || n >= 4294967295LL) return fail(VRT_E_INVALID, "n must be 0 .. 2^32 - 2");
-    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
-    EditBox box;
-    for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
-    if (!edit_box_valid(box, c->cfg.grid_res)) return fail(VRT_E_INVALID, "the box must satisfy 0 <= lo <= hi <= grid_res on every axis");
-    if (!c->prepared) return fail(VRT_E_STATE, "vrt_voxelize_triangles edits a prepared grid: call vrt_prepare first (also after vrt_upload_voxels)");
-    if (!on_device)
-        for (int64_t k = 0; k < n; k++) if (tris[k].reserved0 != 0u || tris[k].reserved1 != 0u) return fail(VRT_E_INVALID, "a triangle's reserved words must be 0");
-    if (result) memset(result, 0, sizeof(*result));
-    const size_t nv = (size_t)edit_box_voxels(box);
-    if (nv == 0 || n == 0) return VRT_OK;
-    if (enter(c) != VRT_OK) return VRT_E_DEVICE;
-    const long long batch = std::min<long long>((long long)n, on_device ? plan_voxelize_batch() : plan_voxelize_chunk());
-    const size_t need = plan_voxelize_bytes(nv, (size_t)batch);
-    if (c->vox_bytes < need) {   // (hipFree waits for the device: no kernel is still using the old one)
-        HIP_TRY(dfree(c, &c->d_vox));
-        c->vox_bytes = 0;
-        HIP_TRY(dmalloc(c, &c->d_vox, need));
-        c->vox_bytes = need;
-    }
-    VoxScratch s;
-    s.owner = (uint32_t*)c->d_vox;
-    s.box_mat = (int8_t*)(c->d_vox + plan_voxelize_mat_at(nv));
-    s.box_rgb = c->d_vox + plan_voxelize_rgb_at(nv);
-    s.entries = (VoxEntry*)(c->d_vox + plan_voxelize_entries_at(nv));
-    s.heads = (unsigned long long*)(c->d_vox + plan_voxelize_heads_at(nv, (size_t)batch));
-    s.res = (VoxResult*)(s.heads + 8);
-    if (!on_device && ensure_cast_stage(c, (size_t)batch * sizeof(vrt_triangle)) != VRT_OK) return VRT_E_DEVICE;
-    c->main_dirty = true;
-    HIP_TRY(launch_voxelize_begin(c->stream, nv, s));
-    for (long long at = 0; at < (long long)n; at += batch) {   // (stream order lets batch k + 1 reuse what batch k has read)
-        const long long m = std::min(batch, (long long)n - at);
-        const vrt_triangle* d_tris = tris + at;
-        if (!on_device) {
-            HIP_TRY(hipMemcpyAsync(c->d_cast_stage, tris + at, (size_t)m * sizeof(vrt_triangle), hipMemcpyHostToDevice, c->stream));
-            d_tris = (const vrt_triangle*)c->d_cast_stage;
-        }
-        HIP_TRY(launch_voxelize_batch(c->stream, c->cfg.grid_res, c->n_cu, box, (unsigned long long)at, m, d_tris, s));
-        if (!on_device) HIP_TRY(launch_voxelize_resolve(c->stream, c->cfg.grid_res, box, (unsigned long long)at, d_tris, at + m >= (long long)n, c->d_mat, c->d_rgb, s));
-    }
-    if (on_device) HIP_TRY(launch_voxelize_resolve(c->stream, c->cfg.grid_res, box, 0ULL, tris, true, c->d_mat, c->d_rgb, s));
-    HIP_TRY(launch_edit(c->stream, c->cfg.grid_res, box, s.box_mat, s.box_rgb, c->d_mat, c->d_rgb, c->d_grid, c->d_l0, c->d_l1, c->d_l2, c->d_l3,
-                        c->d_l0c, c->d_l0c_base, c->d_cull));
-    VoxResult r;
-    if (result) HIP_TRY(hipMemcpyAsync(&r, s.res, sizeof(r), hipMemcpyDeviceToHost, c->stream));   // (waited for by the one synchronisation below)
-    const int rc = read_cull_record(c);   // (the wait also ends the loan of the host array)
-    if (rc == VRT_OK && result) {
-        result->voxels = (int64_t)r.voxels;
-        result->invalid = (int64_t)r.invalid;
-        if (r.voxels != 0ULL) for (int a = 0; a < 3; a++) { result->lo[a] = r.lo[a]; result->hi[a] = r.hi[a] + 1; }
-    }
-    return rc;
-}
-// Fill the inside of a triangle mesh into the box [lo, hi) of a prepared context (vrt_fill.h): every batch toggles one bit per owned
-// column in a bitmap of the box (launch_fill_batch), one resolve turns the bitmap into box arrays (launch_fill_resolve), and those go
-// through launch_edit -- checks, ordering and the one synchronisation are vrt_voxelize_triangles'.  XOR commutes, so the host path's
-// chunks need no resolve of their own: they are staged one after the other and toggle into the same bitmap.
-int vrt_fill_triangles(vrt_ctx* c, int64_t n, const vrt_triangle* tris, const int32_t lo[3], const int32_t hi[3], uint32_t voxel, vrt_voxelize_result* result,
-                       int on_device) {
-    if (!c || !tris || !lo || !hi) return fail(VRT_E_INVALID, "null argument");
-    if (n < 0 || n >= 4294967295LL) return fail(VRT_E_INVALID, "n must be 0 .. 2^32 - 2");
-    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
-    EditBox box;
-    for (int a = 0; a < 3; a++) { box.lo[a] = lo[a]; box.hi[a] = hi[a]; }
-    if (!edit_box_valid(box, c->cfg.grid_res)) return fail(VRT_E_INVALID, "the box must satisfy 0 <= lo <= hi <= grid_res on every axis");
-    if (!c->prepared) return fail(VRT_E_STATE, "vrt_fill_triangles edits a prepared grid: call vrt_prepare first (also after vrt_upload_voxels)");
-    if (!on_device)
-        for (int64_t k = 0; k < n; k++) if (tris[k].reserved0 != 0u || tris[k].reserved1 != 0u) return fail(VRT_E_INVALID, "a triangle's reserved words must be 0");
-    if (result) memset(result, 0, sizeof(*result));
-    const size_t nv = (size_t)edit_box_voxels(box);
-    if (nv == 0 || n == 0) return VRT_OK;
-    if (enter(c) != VRT_OK) return VRT_E_DEVICE;
-    const size_t words = (size_t)fill_words(box);
-    const long long batch = std::min<long long>((long long)n, on_device ? plan_voxelize_batch() : plan_voxelize_chunk());
-    const size_t need = plan_fill_bytes(words, nv, (size_t)batch);
-    if (c->vox_bytes < need) {   // (hipFree waits for the device: no kernel is still using the old one)
-        HIP_TRY(dfree(c, &c->d_vox));
-        c->vox_bytes = 0;
-        HIP_TRY(dmalloc(c, &c->d_vox, need));
-        c->vox_bytes = need;
-    }
-    FillScratch s;
-    s.toggles = (uint32_t*)c->d_vox;
-    s.box_mat = (int8_t*)(c->d_vox + plan_fill_mat_at(words));
-    s.box_rgb = c->d_vox + plan_fill_rgb_at(words, nv);
-    s.entries = (VoxEntry*)(c->d_vox + plan_fill_entries_at(words, nv));
-    s.heads = (unsigned long long*)(c->d_vox + plan_fill_heads_at(words, nv, (size_t)batch));
-    s.res = (VoxResult*)(s.heads + 8);
-    if (!on_device && ensure_cast_stage(c, (size_t)batch * sizeof(vrt_triangle)) != VRT_OK) return VRT_E_DEVICE;
-    c->main_dirty = true;
-    HIP_TRY(launch_fill_begin(c->stream, box, s));
-    for (long long at = 0; at < (long long)n; at += batch) {   // (stream order lets batch k + 1 reuse what batch k has read)
-        const long long m = std::min(batch, (long long)n - at);
-        const vrt_triangle* d_tris = tris + at;
-        if (!on_device) {
-            HIP_TRY(hipMemcpyAsync(c->d_cast_stage, tris + at, (size_t)m * sizeof(vrt_triangle), hipMemcpyHostToDevice, c->stream));
-            d_tris = (const vrt_triangle*)c->d_cast_stage;
-        }
-        HIP_TRY(launch_fill_batch(c->stream, c->cfg.grid_res, c->n_cu, box, m, d_tris, s));
-    }
-    HIP_TRY(launch_fill_resolve(c->stream, c->cfg.grid_res, box, voxel, c->d_mat, c->d_rgb, s));
-    HIP_TRY(launch_edit(c->stream, c->cfg.grid_res, box, s.box_mat, s.box_rgb, c->d_mat, c->d_rgb, c->d_grid, c->d_l0, c->d_l1, c->d_l2, c->d_l3,
-                        c->d_l0c, c->d_l0c_base, c->d_cull));
-    VoxResult r;
-    if (result) HIP_TRY(hipMemcpyAsync(&r, s.res, sizeof(r), hipMemcpyDeviceToHost, c->stream));   // (waited for by the one synchronisation below)
-    const int rc = read_cull_record(c);   // (the wait also ends the loan of the host array)
-    if (rc == VRT_OK && result) {
-        result->voxels = (int64_t)r.voxels;
-        result->invalid = (int64_t)r.invalid;
-        if (r.voxels != 0ULL) for (int a = 0; a < 3; a++) { result->lo[a] = r.lo[a]; result->hi[a] = r.hi[a] + 1; }
-    }
-    return rc;
 }
 int vrt_sky_accumulate_clouds(vrt_ctx* c, int max_samples) {
     if (!c || max_samples <= 0) return fail(VRT_E_INVALID, "bad argument");

@@ -1,5 +1,6 @@
 // vrt_ctx.h -- private to vrt_api.hip's translation unit: the context, error reporting, device allocation, and the waits that know
-// about the dispatch gate.  (vrt_api.hip: the entry points; vrt_pipeline.hip: launch sequencing; vrt_plan.h: its decisions.)
+// about the dispatch gate.  (vrt_api.hip: the entry points; vrt_pipeline.hip: launch sequencing; vrt_plan.h: its decisions;
+// vrt_scene_ops.hip: the calls on a prepared scene.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -117,7 +118,7 @@ struct vrt_ctx {
     size_t edit_stage_bytes = 0;
     uint8_t* d_cast_stage = nullptr;  // vrt_cast_rays / vrt_fetch_voxels, host path: rays in and records out, or the box arrays on their way out (grown on demand)
     size_t cast_stage_bytes = 0;
-    uint8_t* d_vox = nullptr;         // vrt_voxelize_triangles: ownership words, box arrays, item list, heads and result record (plan_voxelize_bytes; grown on demand); vrt_fill_triangles lays it out its own way (plan_fill_bytes)
+    uint8_t* d_vox = nullptr;         // vrt_voxelize_triangles / vrt_fill_triangles: the head region (ownership words or toggle words), box arrays, item list, heads and result record (plan_tri_layout; grown on demand)
     size_t vox_bytes = 0;
     uint8_t* d_dist = nullptr;        // vrt_distance_field: the passes' values and chosen coordinates, and on the host path the staged results (plan_distance_layout; grown on demand)
     size_t dist_bytes = 0;

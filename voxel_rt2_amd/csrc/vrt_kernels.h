@@ -64,32 +64,28 @@ hipError_t launch_fetch_voxels(hipStream_t st, int grid_res, const EditBox& box,
 // the grid n_cu x the kernel's residency at most (plan_sweep_blocks).  Of sc the two finest pyramid levels and the culling box are read.
 hipError_t launch_sweep_boxes(hipStream_t st, int grid_res, int n_cu, float floor_height, const SceneData& sc, long long n, const vrt_box_sweep* boxes,
                               vrt_sweep_hit* hits);
-// vrt_voxelize_triangles (vrt_voxelize.h).  The context's scratch, cut up by plan_voxelize_*: one ownership word per voxel of the clip
-// box, the box arrays launch_edit takes, the item-list entries of a batch, heads[0] the set-up pass's counter (entries << 40 | items),
+// vrt_voxelize_triangles (vrt_voxelize.h) and vrt_fill_triangles (vrt_fill.h).  The context's scratch, cut up by plan_tri_layout: `words`,
+// the head region the raster kernel writes -- one ownership word per voxel of the clip box, or one toggle bit per voxel (fill_words
+// words) -- the box arrays launch_edit takes, the item-list entries of a batch, heads[0] the set-up pass's counter (entries << 40 | items),
 // heads[1] the rasterise pass's work head, and the result record (lo = INT32_MAX / hi = INT32_MIN while nothing is written; hi INCLUSIVE).
 struct VoxResult { int32_t lo[3], hi[3]; unsigned long long voxels, invalid; };
-struct VoxScratch { uint32_t* owner; int8_t* box_mat; uint8_t* box_rgb; VoxEntry* entries; unsigned long long* heads; VoxResult* res; };
-// ownership zeroed over the box's nv voxels, the result record opened
-hipError_t launch_voxelize_begin(hipStream_t st, size_t nv, const VoxScratch& s);
+struct TriScratch { uint32_t* words; int8_t* box_mat; uint8_t* box_rgb; VoxEntry* entries; unsigned long long* heads; VoxResult* res; };
+// the head region's head_bytes zeroed, the result record opened
+hipError_t launch_tri_begin(hipStream_t st, size_t head_bytes, const TriScratch& s);
 // one batch of m <= plan_voxelize_batch() triangles (device memory), global numbers base .. base + m - 1: k_vox_setup, a lane a triangle,
 // counts the items and writes the entries; k_vox_raster, a wave an item, raises the ownership words
 hipError_t launch_voxelize_batch(hipStream_t st, int grid_res, int n_cu, const EditBox& clip, unsigned long long base, long long m, const vrt_triangle* tris,
-                                 const VoxScratch& s);
+                                 const TriScratch& s);
 // k_vox_resolve, a lane a few voxels of the box: payloads of the owners among tris (global numbers from base), and with `final` the grid's
 // stored voxels where nobody owns one, the count and the tight box
 hipError_t launch_voxelize_resolve(hipStream_t st, int grid_res, const EditBox& clip, unsigned long long base, const vrt_triangle* tris, bool final,
-                                   const int8_t* mat, const uint8_t* rgb, const VoxScratch& s);
-// vrt_fill_triangles (vrt_fill.h).  The same scratch cut up by plan_fill_*: one toggle bit per voxel of the clip box (fill_words words),
-// the box arrays, the item-list entries of a batch, heads and the result record as above.
-struct FillScratch { uint32_t* toggles; int8_t* box_mat; uint8_t* box_rgb; VoxEntry* entries; unsigned long long* heads; VoxResult* res; };
-// toggle words zeroed, the result record opened
-hipError_t launch_fill_begin(hipStream_t st, const EditBox& clip, const FillScratch& s);
+                                   const int8_t* mat, const uint8_t* rgb, const TriScratch& s);
 // one batch of m <= plan_voxelize_batch() triangles (device memory): k_fill_setup, a lane a triangle, counts the items and writes the
 // entries; k_fill_raster, a wave an item, toggles one bit per owned column.  Batches need no order and no resolve between them.
-hipError_t launch_fill_batch(hipStream_t st, int grid_res, int n_cu, const EditBox& clip, long long m, const vrt_triangle* tris, const FillScratch& s);
+hipError_t launch_fill_batch(hipStream_t st, int grid_res, int n_cu, const EditBox& clip, long long m, const vrt_triangle* tris, const TriScratch& s);
 // k_fill_resolve, a lane a few voxels of the box, once after every batch: `voxel` where the prefix-XOR of the column says inside, the
 // grid's stored voxel elsewhere; the count and the tight box of the inside cells
-hipError_t launch_fill_resolve(hipStream_t st, int grid_res, const EditBox& clip, uint32_t voxel, const int8_t* mat, const uint8_t* rgb, const FillScratch& s);
+hipError_t launch_fill_resolve(hipStream_t st, int grid_res, const EditBox& clip, uint32_t voxel, const int8_t* mat, const uint8_t* rgb, const TriScratch& s);
 // vrt_distance_field (vrt_distance.h).  The call's scratch cut up by plan_distance_layout: pass z's and pass y's values and, where
 // `nearest` is asked for, the coordinates they chose (cz, cy: not touched otherwise).
 struct DistScratch { int* a; int* b; uint8_t* cz; uint8_t* cy; };

@@ -1697,13 +1697,15 @@ __global__ __launch_bounds__(256) void k_vox_begin(VoxResult* res) {
         res->voxels = 0ULL; res->invalid = 0ULL;
     }
 }
-__global__ __launch_bounds__(256) void k_vox_setup(int G, EditBox clip, long long m, const vrt_triangle* __restrict__ tris, unsigned long long* __restrict__ heads,
-                                                   VoxEntry* __restrict__ entries, VoxResult* __restrict__ res) {
+// The set-up pass of both triangle edits: tri_items is the call's item count of one triangle (vox_tri_items, fill_tri_items).
+template <uint32_t (*tri_items)(const vrt_triangle&, int, const EditBox&, bool&)>
+static __device__ __forceinline__ void tri_setup(int G, const EditBox& clip, long long m, const vrt_triangle* __restrict__ tris,
+                                                 unsigned long long* __restrict__ heads, VoxEntry* __restrict__ entries, VoxResult* __restrict__ res) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
     bool valid = true;
     uint32_t items = 0u;
-    if (i < m) items = vox_tri_items(tris[i], G, clip, valid);
+    if (i < m) items = tri_items(tris[i], G, clip, valid);
     const unsigned long long has = __ballot(items != 0u), bad = __ballot(!valid);
     unsigned long long incl = items;
     for (int d = 1; d < 64; d <<= 1) {
@@ -1724,6 +1726,10 @@ __global__ __launch_bounds__(256) void k_vox_setup(int G, EditBox clip, long lon
         e.items = items;
         entries[(old >> 40) + (unsigned long long)__popcll(has & ((1ULL << lane) - 1ULL))] = e;
     }
+}
+__global__ __launch_bounds__(256) void k_vox_setup(int G, EditBox clip, long long m, const vrt_triangle* __restrict__ tris, unsigned long long* __restrict__ heads,
+                                                   VoxEntry* __restrict__ entries, VoxResult* __restrict__ res) {
+    tri_setup<vox_tri_items>(G, clip, m, tris, heads, entries, res);
 }
 __global__ __launch_bounds__(256) void k_vox_raster(int G, EditBox clip, unsigned long long base, const vrt_triangle* __restrict__ tris,
                                                     unsigned long long* __restrict__ heads, const VoxEntry* __restrict__ entries, uint32_t* __restrict__ owner) {
@@ -1760,26 +1766,14 @@ __global__ __launch_bounds__(256) void k_vox_raster(int G, EditBox clip, unsigne
     }
 }
 // VRT_VOX_RESOLVE_PER_THREAD voxels a thread, a workgroup's 256 x that many consecutive voxels taken 256 apart so that a wave's loads and
-// stores stay neighbours.  Count and bounds are summed per thread, then over the wave with shuffles, then over the workgroup's four waves
-// through LDS, and one thread a workgroup issues the atomics -- the bounds' only where they would move the record (a plain load first):
-// one atomic per wave on seven words that every wave shares made the written voxels, not the box, set this kernel's time.
+// stores stay neighbours.  Count and bounds are summed per thread, then by tri_tally -- which both resolves end on -- over the wave with
+// shuffles, then over the workgroup's four waves through LDS, and one thread a workgroup issues the atomics -- the bounds' only where they
+// would move the record (a plain load first): one atomic per wave on seven words that every wave shares made the written voxels, not the
+// box, set this kernel's time.  Every thread of the workgroup calls tri_tally (a barrier inside); `final`, the same for all of them: the
+// surface pass's resolves before the last tally nothing (tested in here, where it leaves k_vox_resolve's machine code what it was).
 #define VRT_VOX_RESOLVE_PER_THREAD 8
-__global__ __launch_bounds__(256) void k_vox_resolve(int G, EditBox clip, const uint32_t* __restrict__ owner, unsigned long long base,
-                                                     const vrt_triangle* __restrict__ tris, int final, const int8_t* __restrict__ mat,
-                                                     const uint8_t* __restrict__ rgb, int8_t* __restrict__ box_mat, uint8_t* __restrict__ box_rgb,
-                                                     VoxResult* res) {
+static __device__ __forceinline__ void tri_tally(bool final, int count, int lo[3], int hi[3], VoxResult* res) {
     __shared__ int part[4][7];
-    const int nv = edit_box_voxels(clip), first = blockIdx.x * (256 * VRT_VOX_RESOLVE_PER_THREAD) + threadIdx.x;
-    int count = 0, lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int32_t)0x80000000, (int32_t)0x80000000, (int32_t)0x80000000};
-    for (int k = 0; k < VRT_VOX_RESOLVE_PER_THREAD; k++) {
-        const int i = first + k * 256;
-        if (i < nv && vox_resolve_voxel(clip, G, i, owner, base, tris, final != 0, mat, rgb, box_mat, box_rgb) && final) {
-            int c[3];
-            edit_box_voxel(clip, i, c[0], c[1], c[2]);
-            count++;
-            for (int a = 0; a < 3; a++) { lo[a] = c[a] < lo[a] ? c[a] : lo[a]; hi[a] = c[a] > hi[a] ? c[a] : hi[a]; }
-        }
-    }
     if (!final) return;
     for (int d = 32; d >= 1; d >>= 1) {
         count += __shfl_xor(count, d, 64);
@@ -1809,27 +1803,51 @@ __global__ __launch_bounds__(256) void k_vox_resolve(int G, EditBox clip, const 
         }
     }
 }
+__global__ __launch_bounds__(256) void k_vox_resolve(int G, EditBox clip, const uint32_t* __restrict__ owner, unsigned long long base,
+                                                     const vrt_triangle* __restrict__ tris, int final, const int8_t* __restrict__ mat,
+                                                     const uint8_t* __restrict__ rgb, int8_t* __restrict__ box_mat, uint8_t* __restrict__ box_rgb,
+                                                     VoxResult* res) {
+    const int nv = edit_box_voxels(clip), first = blockIdx.x * (256 * VRT_VOX_RESOLVE_PER_THREAD) + threadIdx.x;
+    int count = 0, lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int32_t)0x80000000, (int32_t)0x80000000, (int32_t)0x80000000};
+    for (int k = 0; k < VRT_VOX_RESOLVE_PER_THREAD; k++) {
+        const int i = first + k * 256;
+        if (i < nv && vox_resolve_voxel(clip, G, i, owner, base, tris, final != 0, mat, rgb, box_mat, box_rgb) && final) {
+            int c[3];
+            edit_box_voxel(clip, i, c[0], c[1], c[2]);
+            count++;
+            for (int a = 0; a < 3; a++) { lo[a] = c[a] < lo[a] ? c[a] : lo[a]; hi[a] = c[a] > hi[a] ? c[a] : hi[a]; }
+        }
+    }
+    tri_tally(final != 0, count, lo, hi, res);
+}
 
-hipError_t launch_voxelize_begin(hipStream_t st, size_t nv, const VoxScratch& s) {
-    hipError_t e = hipMemsetAsync(s.owner, 0, 4 * nv, st);
+hipError_t launch_tri_begin(hipStream_t st, size_t head_bytes, const TriScratch& s) {
+    hipError_t e = hipMemsetAsync(s.words, 0, head_bytes, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_vox_begin, dim3(1), dim3(64), 0, st, s.res);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }
-hipError_t launch_voxelize_batch(hipStream_t st, int grid_res, int n_cu, const EditBox& clip, unsigned long long base, long long m, const vrt_triangle* tris,
-                                 const VoxScratch& s) {
+// What a batch of either call begins with: the two heads zeroed and the call's set-up kernel over the batch's m triangles.
+template <class Setup>
+static hipError_t launch_tri_setup(hipStream_t st, Setup k_setup, int grid_res, const EditBox& clip, long long m, const vrt_triangle* tris, const TriScratch& s) {
     hipError_t e = hipMemsetAsync(s.heads, 0, 16, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_vox_setup, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, grid_res, clip, m, tris, s.heads, s.entries, s.res);
+    hipLaunchKernelGGL(k_setup, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, grid_res, clip, m, tris, s.heads, s.entries, s.res);
     VRT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_vox_raster, dim3(plan_voxelize_blocks(n_cu)), dim3(256), 0, st, grid_res, clip, base, tris, s.heads, (const VoxEntry*)s.entries, s.owner);
+    return hipSuccess;
+}
+hipError_t launch_voxelize_batch(hipStream_t st, int grid_res, int n_cu, const EditBox& clip, unsigned long long base, long long m, const vrt_triangle* tris,
+                                 const TriScratch& s) {
+    hipError_t e = launch_tri_setup(st, k_vox_setup, grid_res, clip, m, tris, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_vox_raster, dim3(plan_voxelize_blocks(n_cu)), dim3(256), 0, st, grid_res, clip, base, tris, s.heads, (const VoxEntry*)s.entries, s.words);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }
 hipError_t launch_voxelize_resolve(hipStream_t st, int grid_res, const EditBox& clip, unsigned long long base, const vrt_triangle* tris, bool final,
-                                   const int8_t* mat, const uint8_t* rgb, const VoxScratch& s) {
-    hipLaunchKernelGGL(k_vox_resolve, dim3((edit_box_voxels(clip) + 256 * VRT_VOX_RESOLVE_PER_THREAD - 1) / (256 * VRT_VOX_RESOLVE_PER_THREAD)), dim3(256), 0, st, grid_res, clip, (const uint32_t*)s.owner, base, tris,
+                                   const int8_t* mat, const uint8_t* rgb, const TriScratch& s) {
+    hipLaunchKernelGGL(k_vox_resolve, dim3((edit_box_voxels(clip) + 256 * VRT_VOX_RESOLVE_PER_THREAD - 1) / (256 * VRT_VOX_RESOLVE_PER_THREAD)), dim3(256), 0, st, grid_res, clip, (const uint32_t*)s.words, base, tris,
                        final ? 1 : 0, mat, rgb, s.box_mat, s.box_rgb, s.res);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
@@ -1837,9 +1855,9 @@ hipError_t launch_voxelize_resolve(hipStream_t st, int grid_res, const EditBox& 
 
 // ---- vrt_fill_triangles: the inside of a closed mesh filled with voxels (vrt_fill.h holds the arithmetic) ---------------------------------
 // Three kernels around a toggle bitmap of one bit per voxel of the clip box, bits along z; launch_edit then does what it does for any box.
-//   k_fill_setup    k_vox_setup's sibling (that kernel is left as it is): a LANE a triangle, the gate, the snap, sign(n_z), the aligned
-//                   tiles of 16 x 16 columns its clipped xy bounds touch = its work items; entries and item numbers for a wave's 64
-//                   triangles with ONE 64-bit atomic, in the layout k_vox_setup leaves (VoxEntry, entries << 40 | items).
+//   k_fill_setup    k_vox_setup's body (tri_setup) over this call's item count: a LANE a triangle, the gate, the snap, sign(n_z), the
+//                   aligned tiles of 16 x 16 columns its clipped xy bounds touch = its work items; entries and item numbers for a
+//                   wave's 64 triangles with ONE 64-bit atomic, in the same layout (VoxEntry, entries << 40 | items).
 //   k_fill_raster   a WAVE an item, VRT_FILL_ITEMS_PER_GRAB consecutive items a grab from the work head, the triangle found by binary
 //                   search and its set-up redone only when it changes, as in k_vox_raster.  An item: each lane tests four columns of
 //                   the tile (three edge functions, the bracket in int32) and, for a column the triangle owns, finds the first cell
@@ -1851,31 +1869,7 @@ hipError_t launch_voxelize_resolve(hipStream_t st, int grid_res, const EditBox& 
 // Plain C++ and vector memory operations throughout; the item number is made wave-uniform with readfirstlane as in k_vox_raster.
 __global__ __launch_bounds__(256) void k_fill_setup(int G, EditBox clip, long long m, const vrt_triangle* __restrict__ tris, unsigned long long* __restrict__ heads,
                                                     VoxEntry* __restrict__ entries, VoxResult* __restrict__ res) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    bool valid = true;
-    uint32_t items = 0u;
-    if (i < m) items = fill_tri_items(tris[i], G, clip, valid);
-    const unsigned long long has = __ballot(items != 0u), bad = __ballot(!valid);
-    unsigned long long incl = items;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
-    }
-    const unsigned long long total = __shfl(incl, 63, 64);
-    unsigned long long old = 0ULL;
-    if (lane == 0) {
-        if (has) old = atomicAdd(&heads[0], ((unsigned long long)__popcll(has) << 40) + total);
-        if (bad) atomicAdd(&res->invalid, (unsigned long long)__popcll(bad));
-    }
-    old = __shfl(old, 0, 64);
-    if (items != 0u) {   // (slot < m: a batch has no more entries than triangles)
-        VoxEntry e;
-        e.first = (old & VRT_VOX_ITEM_MASK) + incl - items;
-        e.tri = (uint32_t)i;
-        e.items = items;
-        entries[(old >> 40) + (unsigned long long)__popcll(has & ((1ULL << lane) - 1ULL))] = e;
-    }
+    tri_setup<fill_tri_items>(G, clip, m, tris, heads, entries, res);
 }
 __global__ __launch_bounds__(256) void k_fill_raster(int G, EditBox clip, const vrt_triangle* __restrict__ tris, unsigned long long* __restrict__ heads,
                                                      const VoxEntry* __restrict__ entries, uint32_t* __restrict__ toggles) {
@@ -1909,11 +1903,9 @@ __global__ __launch_bounds__(256) void k_fill_raster(int G, EditBox clip, const 
         }
     }
 }
-// k_vox_resolve's shape: VRT_VOX_RESOLVE_PER_THREAD voxels a thread taken 256 apart, count and bounds summed per thread, over the wave with
-// shuffles, over the workgroup's four waves through LDS, one thread a workgroup issuing the atomics.
+// k_vox_resolve's shape: VRT_VOX_RESOLVE_PER_THREAD voxels a thread taken 256 apart, count and bounds summed per thread, then tri_tally.
 __global__ __launch_bounds__(256) void k_fill_resolve(int G, EditBox clip, const uint32_t* __restrict__ toggles, uint32_t voxel, const int8_t* __restrict__ mat,
                                                       const uint8_t* __restrict__ rgb, int8_t* __restrict__ box_mat, uint8_t* __restrict__ box_rgb, VoxResult* res) {
-    __shared__ int part[4][7];
     const int nv = edit_box_voxels(clip), first = blockIdx.x * (256 * VRT_VOX_RESOLVE_PER_THREAD) + threadIdx.x;
     int count = 0, lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int32_t)0x80000000, (int32_t)0x80000000, (int32_t)0x80000000};
     for (int k = 0; k < VRT_VOX_RESOLVE_PER_THREAD; k++) {
@@ -1925,54 +1917,19 @@ __global__ __launch_bounds__(256) void k_fill_resolve(int G, EditBox clip, const
             for (int a = 0; a < 3; a++) { lo[a] = c[a] < lo[a] ? c[a] : lo[a]; hi[a] = c[a] > hi[a] ? c[a] : hi[a]; }
         }
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-        count += __shfl_xor(count, d, 64);
-        for (int a = 0; a < 3; a++) {
-            const int l = __shfl_xor(lo[a], d, 64), u = __shfl_xor(hi[a], d, 64);
-            lo[a] = l < lo[a] ? l : lo[a];
-            hi[a] = u > hi[a] ? u : hi[a];
-        }
-    }
-    if ((threadIdx.x & 63) == 0) {
-        int* p = part[threadIdx.x >> 6];
-        p[0] = count;
-        for (int a = 0; a < 3; a++) { p[1 + a] = lo[a]; p[4 + a] = hi[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) {
-            count += part[w][0];
-            for (int a = 0; a < 3; a++) { lo[a] = part[w][1 + a] < lo[a] ? part[w][1 + a] : lo[a]; hi[a] = part[w][4 + a] > hi[a] ? part[w][4 + a] : hi[a]; }
-        }
-        if (count) {
-            atomicAdd(&res->voxels, (unsigned long long)count);
-            for (int a = 0; a < 3; a++) {   // (a stale load only costs an atomic that changes nothing)
-                if (lo[a] < *(volatile int32_t*)&res->lo[a]) atomicMin(&res->lo[a], lo[a]);
-                if (hi[a] > *(volatile int32_t*)&res->hi[a]) atomicMax(&res->hi[a], hi[a]);
-            }
-        }
-    }
+    tri_tally(true, count, lo, hi, res);
 }
 
-hipError_t launch_fill_begin(hipStream_t st, const EditBox& clip, const FillScratch& s) {
-    hipError_t e = hipMemsetAsync(s.toggles, 0, 4 * (size_t)fill_words(clip), st);
+hipError_t launch_fill_batch(hipStream_t st, int grid_res, int n_cu, const EditBox& clip, long long m, const vrt_triangle* tris, const TriScratch& s) {
+    hipError_t e = launch_tri_setup(st, k_fill_setup, grid_res, clip, m, tris, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_vox_begin, dim3(1), dim3(64), 0, st, s.res);
+    hipLaunchKernelGGL(k_fill_raster, dim3(plan_voxelize_blocks(n_cu)), dim3(256), 0, st, grid_res, clip, tris, s.heads, (const VoxEntry*)s.entries, s.words);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }
-hipError_t launch_fill_batch(hipStream_t st, int grid_res, int n_cu, const EditBox& clip, long long m, const vrt_triangle* tris, const FillScratch& s) {
-    hipError_t e = hipMemsetAsync(s.heads, 0, 16, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fill_setup, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, grid_res, clip, m, tris, s.heads, s.entries, s.res);
-    VRT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_fill_raster, dim3(plan_voxelize_blocks(n_cu)), dim3(256), 0, st, grid_res, clip, tris, s.heads, (const VoxEntry*)s.entries, s.toggles);
-    VRT_LAUNCH_CHECK();
-    return hipSuccess;
-}
-hipError_t launch_fill_resolve(hipStream_t st, int grid_res, const EditBox& clip, uint32_t voxel, const int8_t* mat, const uint8_t* rgb, const FillScratch& s) {
+hipError_t launch_fill_resolve(hipStream_t st, int grid_res, const EditBox& clip, uint32_t voxel, const int8_t* mat, const uint8_t* rgb, const TriScratch& s) {
     hipLaunchKernelGGL(k_fill_resolve, dim3((edit_box_voxels(clip) + 256 * VRT_VOX_RESOLVE_PER_THREAD - 1) / (256 * VRT_VOX_RESOLVE_PER_THREAD)), dim3(256), 0, st, grid_res, clip,
-                       (const uint32_t*)s.toggles, voxel, mat, rgb, s.box_mat, s.box_rgb, s.res);
+                       (const uint32_t*)s.words, voxel, mat, rgb, s.box_mat, s.box_rgb, s.res);
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

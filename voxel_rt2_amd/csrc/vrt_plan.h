@@ -253,13 +253,24 @@ static inline long long plan_voxelize_batch() { return 1 << 20; }
 // Workgroups of the rasterise launch: a persistent grid of four waves a workgroup, eight workgroups a CU -- the item count is known
 // on the device only, and a wave that finds the head exhausted ends at once.
 static inline int plan_voxelize_blocks(int n_cu) { return (n_cu > 0 ? n_cu : 1) * 8; }
-// Bytes of the context's voxeliser scratch for a box of nv voxels and batches of at most `batch` triangles: ownership words, the box
-// arrays handed to launch_edit (materials padded to 256 bytes), the item-list entries, the two heads and the result record.
-static inline size_t plan_voxelize_mat_at(size_t nv) { return 4 * nv; }
-static inline size_t plan_voxelize_rgb_at(size_t nv) { return plan_voxelize_mat_at(nv) + ((nv + 255) & ~(size_t)255); }
-static inline size_t plan_voxelize_entries_at(size_t nv) { return (plan_voxelize_rgb_at(nv) + 3 * nv + 255) & ~(size_t)255; }
-static inline size_t plan_voxelize_heads_at(size_t nv, size_t batch) { return plan_voxelize_entries_at(nv) + 16 * batch; }
-static inline size_t plan_voxelize_bytes(size_t nv, size_t batch) { return plan_voxelize_heads_at(nv, batch) + 256; }
+// The context's triangle-edit scratch (vrt_ctx::d_vox), cut up for a box of nv voxels, a head region of head_bytes and batches of at most
+// `batch` triangles.  The head is what the call's raster kernel writes: vrt_voxelize_triangles' ownership words (4 * nv bytes) or
+// vrt_fill_triangles' toggle words (4 * fill_words: one bit a voxel, a column rounded up to whole 32-bit words).  Behind it the box
+// arrays handed to launch_edit (head and materials padded to 256 bytes), the item-list entries (16 bytes a triangle, on a multiple of
+// 16), and 256 bytes for the two heads and the result record.  (The surface pass used to put box_mat at 4 * nv unrounded, and both
+// calls the entries on a multiple of 256: this moves the regions by at most 255 bytes, never makes the buffer more than 255 bytes
+// larger, and changes no result -- nothing but these offsets says where a region is.)
+struct TriLayout { size_t mat_at, rgb_at, entries_at, heads_at, bytes; };
+static inline TriLayout plan_tri_layout(size_t head_bytes, size_t nv, size_t batch) {
+    const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    TriLayout l;
+    l.mat_at = up(head_bytes);
+    l.rgb_at = l.mat_at + up(nv);
+    l.entries_at = (l.rgb_at + 3 * nv + 15) & ~(size_t)15;
+    l.heads_at = l.entries_at + 16 * batch;
+    l.bytes = l.heads_at + 256;
+    return l;
+}
 
 // ---- vrt_fill_triangles -----------------------------------------------------------------------------------------------------------------
 // Chunks and batches are vrt_voxelize_triangles' (plan_voxelize_chunk, plan_voxelize_batch), and so is the persistent grid
@@ -267,14 +278,6 @@ static inline size_t plan_voxelize_bytes(size_t nv, size_t batch) { return plan_
 // column tests and at most four divisions a lane -- an order of magnitude lighter than the surface pass's 16^3 cell, so the tail a
 // grab leaves on one wave matters less and the search for an item's triangle more: a grid-spanning triangle's 256 items are 32 grabs.
 #define VRT_FILL_ITEMS_PER_GRAB 8
-// Bytes of the fill's layout of the context's voxeliser scratch for a box of nv voxels and `words` toggle words (fill_words: one bit a
-// voxel, a column rounded up to whole 32-bit words) and batches of at most `batch` triangles: the toggle words, the box arrays handed
-// to launch_edit (materials padded to 256 bytes), the item-list entries, the two heads and the result record.
-static inline size_t plan_fill_mat_at(size_t words) { return (4 * words + 255) & ~(size_t)255; }
-static inline size_t plan_fill_rgb_at(size_t words, size_t nv) { return plan_fill_mat_at(words) + ((nv + 255) & ~(size_t)255); }
-static inline size_t plan_fill_entries_at(size_t words, size_t nv) { return (plan_fill_rgb_at(words, nv) + 3 * nv + 255) & ~(size_t)255; }
-static inline size_t plan_fill_heads_at(size_t words, size_t nv, size_t batch) { return plan_fill_entries_at(words, nv) + 16 * batch; }
-static inline size_t plan_fill_bytes(size_t words, size_t nv, size_t batch) { return plan_fill_heads_at(words, nv, batch) + 256; }
 
 // ---- vrt_distance_field (vrt_distance.h) ------------------------------------------------------------------------------------------------
 // Tile shapes.  Pass z: a workgroup of 256 threads stages VRT_DIST_Z_LINES whole lines (consecutive in memory: z fastest, then y) in LDS,
