@@ -4,7 +4,10 @@ for the device alone (hipcc -S, the library's flags) from this tree and from REV
 folder), cuts both listings into functions and compares every function both have, instruction for instruction: comments dropped, block
 labels renumbered in order of appearance (a function's labels carry its number in the file, which moves when functions are added).
 
-    python tools/asm_diff.py [REV] [name-substring ...]         REV: default HEAD~1
+    python tools/asm_diff.py [REV] [--rename REGEX=REPL ...] [name-substring ...]         REV: default HEAD~1
+
+--rename: a kernel of this tree whose name changed (a template parameter added with a default, say) is paired with REV's by rewriting this
+tree's demangled names with re.sub(REGEX, REPL, name) first, e.g. --rename '(k_render_pool<[^>]*), false>=\1>'.
 
 Prints one line per function that differs or that only one side has, then the counts; exit status 1 if a function both have differs.
 A function that holds the same multiset of instruction lines in another order (the scheduler swapping independent instructions) is
@@ -55,11 +58,17 @@ def normal(body):
 
     def label(m):
         return seen.setdefault(m.group(0), f".L{len(seen)}")
-    return [re.sub(r"\.L[A-Za-z_]*\d+(_\d+)?", label, ln) for ln in body]
+    # (the kernel descriptor's directive repeats the function's own symbol: dropped, so that a renamed kernel can compare equal)
+    return [re.sub(r"\.L[A-Za-z_]*\d+(_\d+)?", label, re.sub(r"^\.amdhsa_kernel \S+", ".amdhsa_kernel", ln)) for ln in body]
 
 
 def main():
     args = sys.argv[1:]
+    renames = []
+    while "--rename" in args:
+        i = args.index("--rename")
+        renames.append(args[i + 1].split("=", 1))
+        del args[i:i + 2]
     rev = args.pop(0) if args and not subprocess.run(["git", "-C", ROOT, "rev-parse", "--verify", "-q", args[0] + "^{commit}"], capture_output=True).returncode else "HEAD~1"
     with tempfile.TemporaryDirectory() as tmp:
         old = os.path.join(tmp, "rev")
@@ -67,6 +76,8 @@ def main():
         tar = subprocess.run(["git", "-C", ROOT, "archive", rev, "voxel_rt2_amd/csrc", "include"], check=True, capture_output=True).stdout
         subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)
         a, b = functions(listing(old, os.path.join(tmp, "a.s"))), functions(listing(ROOT, os.path.join(tmp, "b.s")))
+    for pat, repl in renames:
+        b = {re.sub(pat, repl, n): body for n, body in b.items()}
     pick = lambda n: not args or any(s in n for s in args)
     same = reordered = differ = 0
     for n in sorted(set(a) | set(b)):

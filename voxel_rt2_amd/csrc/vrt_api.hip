@@ -210,6 +210,9 @@ void vrt_destroy(vrt_ctx* c) {
     if (c->stream && flush_deferred(c, false) != VRT_OK) { (void)hipGetLastError(); c->deferred.clear(); }
     drain_all(c);
     resolve_events(c);
+#if defined(VRT_DEV_KNOBS)   // development build: what the A/B runs and tests/test_gpu_prepass.py read (the shipped library reports nothing)
+    if (getenv("VRT_PREPASS_REPORT")) fprintf(stderr, "vrt: pre-passes queued %u told %u of %u render launches\n", c->prepass_queued, c->prepass_told, c->passes_n[0]);
+#endif
     for (PlaneSet& p : c->sets) {
         if (p.ev_r) hipEventDestroy(p.ev_r);
         if (p.ev_t) hipEventDestroy(p.ev_t);

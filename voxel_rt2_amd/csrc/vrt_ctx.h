@@ -154,7 +154,8 @@ struct vrt_ctx {
     const float* last_gb_depth = nullptr;
     mat4 prev_view{}, prev_proj{};
     uint32_t frame = 0;
-    unsigned launch_seq = 0;  // render launches so far (selects which of the two work counters a launch uses)
+    unsigned prepass_queued = 0, prepass_told = 0;   // pre-passes queued so far, and those the launch was told of (plan_prepass)
+    LaunchSeq launch_seq;     // .next: render launches so far (selects which work counters a launch uses, and its records' tag); .reserved: a pre-pass holds that number (vrt_plan.h)
 
     // ---- the launch pipeline (vrt_pipeline.hip) ----
     // Overlapped launches (vrt_accumulate): n_sets copies of everything a render launch writes and its temporal pass reads,
@@ -300,7 +301,7 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 // flight will raise the word to, and later launches raise it further (atomic max), so no wait can be lost.
 static void release_gate(vrt_ctx* c) {
     if (!c->drain_signal) return;
-    __atomic_store_n(c->drain_signal, (uint32_t)c->launch_seq, __ATOMIC_RELEASE);
+    __atomic_store_n(c->drain_signal, (uint32_t)c->launch_seq.next, __ATOMIC_RELEASE);
     c->gate_releases++;
 }
 // Before a blocking wait for work that may sit behind a gated launch: polls `query` (hipErrorNotReady: not yet) for at most the

@@ -388,7 +388,7 @@ __device__ __forceinline__ int lane_rank(unsigned long long m) {  // set bits of
 // WAVES path pools of SLOTS slots per workgroup: 4 x 128 with two workgroups per CU (two waves per SIMD) by default; the whole l1
 // level of a 256^3 grid leaves room for one workgroup of 8 x 128 per CU; a DENSE 128^3 grid runs one workgroup of 12 x 96 per CU
 // -- three waves per SIMD at 168 registers (k_render_pool_dense12 below).
-template <int G, bool RESTIR, bool INSTR, bool BLACK_SUN, bool CULL, bool D12 = false>   // D12: twelve waves, and SHADE's shadow rays with the branchy descent
+template <int G, bool RESTIR, bool INSTR, bool BLACK_SUN, bool CULL, bool D12 = false, bool SERVED = false>   // D12: twelve waves, and SHADE's shadow rays with the branchy descent; SERVED: below
 // 208 registers per wave (the attribute counts half of the unified file): two waves per SIMD then leave the 96 that
 // k_temporal runs in beside them (see there).  The allocator would take 238; the cap costs 28 bytes of scratch.
 // The ReSTIR instantiation (no overlapped launches, so nothing runs beside it) takes the two-wave maximum of 256.
@@ -654,7 +654,9 @@ __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const Sc
                             bool known = false;
                             PrimaryRecord rec;
                             rec.x = rec.y = rec.z = rec.dx = rec.dy = rec.dz = rec.ft = rec.w = 0u;
-                            if (prim_cache && sample > 0) {
+                            // (SERVED: k_primary_records has run for this launch, so sample 0 may find its record too; one that is
+                            // missing or does not check out is set up and walked below, and leaves its record, as ever)
+                            if (prim_cache && (SERVED || sample > 0)) {
                                 rec = primary_record_load(&prim_cache[(v - fp.row0) * fp.W + u]);
                                 known = primary_record_valid(rec, prim_tag);
                             }
@@ -668,7 +670,7 @@ __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const Sc
                                 if (prim_cache && sample == 0 && st != SLOT_RAY) primary_record_store(&prim_cache[(v - fp.row0) * fp.W + u], primary_record(s, prim_tag));
                             }
                             state[slot] = (uint32_t)st;
-                            VRT_SUB_CLOCK(sample > 0 ? 2 : 3);
+                            VRT_SUB_CLOCK(known ? 2 : 3);
                         }
                     }
                 }
@@ -685,9 +687,12 @@ __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const Sc
     if (INSTR) flush_stats(ts, sc.counters);
 }
 // (the register attribute takes a literal, hence one kernel per budget around the shared body)
-template <int G, bool INSTR, bool BLACK_SUN, bool CULL>
+// SERVED: the instantiation for launches with a pre-pass (k_primary_records, below).  A template parameter, not a kernel argument: as
+// an argument the test reached the code of every launch, and the one-sample calls, which have no pre-pass, ran 1.0 % slower
+// (DESIGN.md section 7); this way a launch without a pre-pass runs the machine code it ran before there was one.
+template <int G, bool INSTR, bool BLACK_SUN, bool CULL, bool SERVED = false>
 __global__ __launch_bounds__(64 * pool_shape<G>(false).waves, VRT_POOL_MIN_WAVES) __attribute__((amdgpu_num_vgpr(VRT_POOL_HALF_VGPRS))) void k_render_pool(FrameParams fp, SceneData sc, PixelBuffers out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache) {
-    render_pool_body<G, false, INSTR, BLACK_SUN, CULL>(fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, drain_value, prim_cache);
+    render_pool_body<G, false, INSTR, BLACK_SUN, CULL, false, SERVED>(fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, drain_value, prim_cache);
 }
 // A DENSE grid under an emitting sun: the shadow rays of SHADE with the branchy descent (shadow_branchy_of, vrt_trace.h), and
 // THREE waves per SIMD: one workgroup of twelve waves per CU, 96 slots per pool (12 x 10.4 KB of pools
@@ -703,6 +708,28 @@ __global__ __launch_bounds__(64 * pool_shape<G>(true).waves, 3) __attribute__((a
 template <int G, bool INSTR, bool CULL>
 __global__ __launch_bounds__(64 * pool_shape<G>(false).waves, VRT_POOL_MIN_WAVES) __attribute__((amdgpu_num_vgpr(128))) void k_render_pool_restir(FrameParams fp, SceneData sc, PixelBuffers out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache) {
     render_pool_body<G, true, INSTR, false, CULL>(fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, drain_value, prim_cache);
+}
+
+// The camera-ray records of a launch, made AHEAD of it (primary_record_walk, vrt_pool.h) by a kernel small enough to run beside two
+// pooled workgroups per CU: one wave a workgroup, one workgroup an 8x8 tile of the rows the launch renders (BEGIN's own gating), no
+// LDS -- the pyramid is read through global memory, 260 KiB that stay in cache -- and at most the 96 registers that two pooled waves
+// of 208 leave free on a SIMD (the attribute counts half of the unified file, as VRT_TEMPORAL_HALF_VGPRS does).  Queued on the
+// launch's own lane behind that lane's previous launch, it runs while the launches of the other lanes hold the heavy slots, in issue
+// slots their waves leave idle; the launch then begins sample 0 from the record (the SERVED instantiation) instead of setting the ray up and
+// walking it between bounce rays.  Nothing waits for it but stream order, and a record that is not there is walked as ever.
+#ifndef VRT_PRIMARY_HALF_VGPRS
+#define VRT_PRIMARY_HALF_VGPRS 48
+#endif
+template <int G, bool CULL>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(VRT_PRIMARY_HALF_VGPRS))) void k_primary_records(FrameParams fp, SceneData sc, PrimaryRecord* prim_cache, uint32_t tag) {
+    const int tiles_x = (fp.W + 7) >> 3;
+    const unsigned tile = blockIdx.x, in = threadIdx.x;
+    const int u = (int)(tile % (unsigned)tiles_x) * 8 + (int)(in & 7u);
+    const int v = launch_tile_row(fp, (int)(tile / (unsigned)tiles_x)) + (int)(in >> 3);
+    if (!(u < fp.W && v < fp.row1 && launch_renders_row(fp, v) && !outside_render_area(fp, (float)u, (float)v))) return;
+    GlobalPyramid<G> P;
+    P.p = sc.pyr;
+    primary_record_store(&prim_cache[(v - fp.row0) * fp.W + u], primary_record_walk<G, CULL>(fp, P, sc.cull, u, v, tag));
 }
 
 // ---- spatial reuse ---------------------------------------------------------------------------
@@ -1484,8 +1511,12 @@ hipError_t launch_render(hipStream_t st, int grid_res, bool restir, bool instr, 
 // scratch size.  (restir: the reservoir needs the light sample whatever the sun's colour.)
 typedef void (*pool_kernel_fn)(FrameParams, SceneData, PixelBuffers, unsigned*, unsigned*, int, uint32_t*, uint32_t*, uint32_t, PrimaryRecord*);
 struct PoolKernel { pool_kernel_fn fn; PoolShape shape; };
-static PoolKernel pool_kernel(int grid_res, const RenderVariant& v) {
+static PoolKernel pool_kernel(int grid_res, const RenderVariant& v, bool served = false) {
     PoolKernel k{nullptr, {0, 0}};
+    if (served && !v.instr && !v.restir && !v.dense12) {   // (plan_prepass names no other launch; same geometry and residency as the plain instantiation)
+        VRT_BY_GRID(grid_res, VRT_BY_2(v.black_sun, v.cull, k = (PoolKernel{k_render_pool<G, false, A, B, true>, pool_shape<G>(false)})));
+        return k;
+    }
     VRT_BY_GRID(grid_res, VRT_BY_2(v.instr, v.cull,
         k = (v.restir ? PoolKernel{k_render_pool_restir<G, A, B>, pool_shape<G>(false)}
            : v.dense12 ? PoolKernel{k_render_pool_dense12<G, A, B>, pool_shape<G>(true)}
@@ -1500,12 +1531,21 @@ hipError_t query_render_pool(int grid_res, const RenderVariant& v, int* blocks_p
 }
 hipError_t launch_render_pool(hipStream_t st, int grid_res, const RenderVariant& v, int n_blocks, const FrameParams& fp, const SceneData& sc,
                               const PixelBuffers& out, unsigned* work_counters, unsigned launch_seq, int n_samples, uint32_t* cold,
-                              uint32_t* drain_signal, PrimaryRecord* prim_cache) {
+                              uint32_t* drain_signal, PrimaryRecord* prim_cache, bool prim_served) {
     unsigned* work_counter = work_counters + (launch_seq & 15u) * (VRT_WORK_HEADS * VRT_WORK_HEAD_STRIDE);
     unsigned* next_counter = work_counters + ((launch_seq + 8u) & 15u) * (VRT_WORK_HEADS * VRT_WORK_HEAD_STRIDE);
-    const PoolKernel k = pool_kernel(grid_res, v);
+    const PoolKernel k = pool_kernel(grid_res, v, prim_served);
     // the signal carries launch_seq + 1 of the latest launch that has begun to drain
     hipLaunchKernelGGL(k.fn, dim3(n_blocks), dim3(64 * k.shape.waves), 0, st, fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, launch_seq + 1u, prim_cache);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_primary_records(hipStream_t st, int grid_res, const RenderVariant& v, const FrameParams& fp, const SceneData& sc, PrimaryRecord* prim_cache,
+                                  unsigned launch_seq) {
+    const int tiles = ((fp.W + 7) >> 3) * launch_tile_rows(fp);
+    if (tiles <= 0) return hipSuccess;
+    // the tag the launch itself will look for (launch_render_pool): launch_seq + 1
+    VRT_BY_GRID(grid_res, VRT_BY_2(v.cull, false, hipLaunchKernelGGL((k_primary_records<G, A>), dim3(tiles), dim3(64), 0, st, fp, sc, prim_cache, launch_seq + 1u)));
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

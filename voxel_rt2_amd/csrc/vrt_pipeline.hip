@@ -163,6 +163,7 @@ static bool ensure_overlap(vrt_ctx* c, size_t items, bool heavy) {
 // the roles were rolled back -- after a failed call on a ReSTIR context the caller must vrt_reset().
 static void abort_pipeline(vrt_ctx* c) {
     const std::string keep = g_err;
+    plan_seq_abort(c->launch_seq);   // a pre-pass queued for a launch that did not follow: its tag is never handed out again
     release_gate(c);
     c->drain_signalled = false;
     // the launches that WERE queued are accumulated all the same (the failed one has left no slice behind)
@@ -341,18 +342,39 @@ static bool pipeline_nearly_empty(vrt_ctx* c) {
     return running < c->knobs.full_below;
 }
 
-// An overlapped launch into copy `set` on render stream `lane` comes behind what it depends on.
-static int order_overlapped_launch(vrt_ctx* c, int set, int lane) {
+// The camera-ray table of `lane` (allocated on first use; null if there is no memory for it: the launch then shares nothing).
+static PrimaryRecord* lane_prim_cache(vrt_ctx* c, int lane) {
+    Lane& l = c->lanes[lane];
+    if (!l.prim_cache && dalloc(c, &l.prim_cache, c->npix) != hipSuccess) { (void)hipGetLastError(); (void)dfree(c, &l.prim_cache); }
+    return l.prim_cache;
+}
+
+// An overlapped launch into copy `set` on render stream `lane` comes behind what it depends on.  pre: the launch's pre-pass
+// (plan_prepass) goes in here; *served: it was queued and the launch is to be told.
+static int order_overlapped_launch(vrt_ctx* c, int set, int lane, const Prepass& pre, const RenderVariant& v, const FrameParams& fp, const SceneData& sc, bool* served) {
     hipStream_t rs = lane_stream(c, lane);
+    *served = false;
     if (c->main_dirty) {  // uploads / prepare / sky kernels queued on the main stream come first (where it is a lane itself: in stream order)
         HIP_TRY(hipEventRecord(c->ev_main, c->stream));
         for (int s = 0; s < c->n_streams; s++) HIP_TRY(hipStreamWaitEvent(c->lanes[s].stream, c->ev_main, 0));
         c->main_dirty = false;
     }
+    // The pre-pass reads the scene and writes the lane's record table, which the lane's previous launch has done with in stream
+    // order: it is queued HERE, behind the scene and in front of every wait that holds the launch itself back -- for the copy it
+    // writes, for the slots it takes -- so that it runs beside the launches of the other lanes.  It carries the number the launch
+    // takes below; from here on that number belongs to this launch whether or not it gets queued (plan_seq_abort).
+    if (pre.queue) {
+        if (PrimaryRecord* prim = lane_prim_cache(c, lane)) {
+            HIP_TRY(launch_primary_records(rs, c->cfg.grid_res, v, fp, sc, prim, plan_seq_reserve(c->launch_seq)));
+            *served = pre.tell;
+            c->prepass_queued++;
+            if (pre.tell) c->prepass_told++;
+        }
+    }
     const PlaneSet& p = c->sets[set];
     if (p.ev_t_valid) HIP_TRY(hipStreamWaitEvent(rs, c->sets[p.ev_t_of].ev_t, 0));  // the pass that last read this copy
     // the dispatch gate (vrt_ctx::drain_signal): when the launch whose workgroup slots this one will take starts to drain
-    const unsigned target = plan_gate_target(c->launch_seq, c->prev_launch_full, c->grid_div, c->knobs.gate_extra, c->last_full_seq);
+    const unsigned target = plan_gate_target(c->launch_seq.next, c->prev_launch_full, c->grid_div, c->knobs.gate_extra, c->last_full_seq);
     if (plan_gate_wait(target, c->lanes[lane].last_seq, c->drain_signal != nullptr, c->drain_signalled))
         HIP_TRY(hipStreamWaitValue32(rs, c->drain_signal, target, hipStreamWaitValueGte, 0xFFFFFFFFu));
     return VRT_OK;
@@ -502,15 +524,17 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
         hipStream_t rs = overlapped ? lane_stream(c, lane) : c->stream;
         bool lone = !overlapped;   // every workgroup slot
         if (overlapped && c->grid_div > 1) lone = pipeline_nearly_empty(c);
+        const SceneData sc = make_scene_data(c);
+        bool prim_served = false;
         if (overlapped) {
-            if (order_overlapped_launch(c, set, lane) != VRT_OK) return VRT_E_DEVICE;
+            const Prepass pre = plan_prepass(v, overlapped, lone, c->grid_div, c->knobs.prepass);
+            if (order_overlapped_launch(c, set, lane, pre, v, fp, sc, &prim_served) != VRT_OK) return VRT_E_DEVICE;
         } else if (c->last_set != 0) {
             if (restore_single_set(c) != VRT_OK) return VRT_E_DEVICE;
         }
         if (c->pending.size() > 192) resolve_completed(c);
         // (an asynchronous fetch may still be reading the HDR buffer this launch renders into; the passes below check theirs)
         if (!planes && wait_cbuf_readers(c, c->cidx) != VRT_OK) return VRT_E_DEVICE;
-        const SceneData sc = make_scene_data(c);
         const PixelBuffers out = pixel_buffers_of(c, set, g, planes);
         if (c->cam.render_scale != 1.0f) {
             // a pass that renders part of the frame: the reference's g-buffer is ONE array, so the pixels it leaves out
@@ -518,22 +542,18 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
             HIP_TRY(hipMemcpyAsync(c->d_gb_normal[c->cur], c->last_gb_normal, c->npix * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
             HIP_TRY(hipMemcpyAsync(c->d_gb_depth[c->cur], c->last_gb_depth, c->npix * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
         }
-        const unsigned seq = c->launch_seq++;
+        const unsigned seq = plan_seq_take(c->launch_seq);
         const bool timed = c->since_reset++ % plan_timer_period(c->knobs.time_every, restir, items, c->knobs.deep_items) == 0u;   // this launch and its passes carry timers
         c->passes_n[0]++;
         Timer t;
         if (timer_begin(c, &t, timed, 0, rs) != VRT_OK) return VRT_E_DEVICE;
         // test hook (tests/test_gpu_pipeline.py): launch number VRT_TEST_FAIL_LAUNCH (read at vrt_create) is reported as failed instead of queued
         if (c->knobs.fail_launch >= 0 && (unsigned)c->knobs.fail_launch == seq) return fail(VRT_E_DEVICE, "injected launch failure (VRT_TEST_FAIL_LAUNCH)");
-        PrimaryRecord* prim = nullptr;  // fused samples share their camera rays through this table (vrt_pool.h)
-        if (v.share_primary) {
-            Lane& l = c->lanes[lane];
-            if (!l.prim_cache && dalloc(c, &l.prim_cache, c->npix) != hipSuccess) { (void)hipGetLastError(); (void)dfree(c, &l.prim_cache); }
-            prim = l.prim_cache;
-        }
+        // fused samples share their camera rays through this table (vrt_pool.h)
+        PrimaryRecord* const prim = v.share_primary ? lane_prim_cache(c, lane) : nullptr;
         const int all_blocks = v.dense12 ? c->render_blocks_d12 : c->render_blocks;
         const int blocks = lone ? all_blocks : plan_partial_blocks(all_blocks, c->grid_div);
-        if (pooled) HIP_TRY(launch_render_pool(rs, c->cfg.grid_res, v, blocks, fp, sc, out, c->d_work, seq, g, c->lanes[lane].pool_scratch, c->drain_signal, prim));
+        if (pooled) HIP_TRY(launch_render_pool(rs, c->cfg.grid_res, v, blocks, fp, sc, out, c->d_work, seq, g, c->lanes[lane].pool_scratch, c->drain_signal, prim, prim_served));
         else HIP_TRY(launch_render(rs, c->cfg.grid_res, restir, v.instr, c->render_blocks, fp, sc, out, c->d_work, seq, g, c->knobs.chunk));
         c->drain_signalled = pooled && c->drain_signal != nullptr;
         c->prev_launch_full = blocks == all_blocks;

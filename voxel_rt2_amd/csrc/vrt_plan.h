@@ -25,7 +25,8 @@
 // A build with -DVRT_DEV_KNOBS (build_variants/libvrt_dev.so: `python -m voxel_rt2_amd.build --variant dev -DVRT_DEV_KNOBS`,
 // loaded by tests/test_gpu_pipeline.py and the A/B runs of tools/) adds the development switches: the fault-injection hook
 // VRT_TEST_FAIL_LAUNCH and the A/B switches VRT_CULL, VRT_DENSE, VRT_DEEP_ITEMS, VRT_DEEPER_ITEMS, VRT_STREAMS, VRT_GRID_DIV,
-// VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER, VRT_PASS_STREAM, VRT_CTX_LANE, VRT_CAST_VIEW.
+// VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER, VRT_PASS_STREAM, VRT_CTX_LANE, VRT_CAST_VIEW,
+// VRT_PREPASS.
 struct Knobs {
     int render = -1;               // -1: the library's choice, 0: fused, 1: pool; -2: a value VRT_RENDER does not know
     bool overlap = true;
@@ -41,6 +42,7 @@ struct Knobs {
     int max_fused = VRT_MAX_FUSED, full_below = 2, chunk = 0, fail_launch = -1, gate_extra = 0, time_every = 0;
     int defer4 = VRT_DEFER_4DEEP, defer8 = 1;   // render launches whose accumulation runs as one pass, per pipeline depth (VRT_DEFER: both)
     int cast_view = -1;            // -1: by the batch size (plan_cast_staged), 0: k_cast_rays on the pyramid in global memory, 1: coarse levels staged in LDS
+    int prepass = 1;               // plan_prepass: 0: no launch has a pre-pass, 1: those the rule names, 2: the same, queued, but the launch is not told (A/B: what co-residency costs)
 };
 static Knobs read_knobs() {
     Knobs k;
@@ -64,9 +66,10 @@ static Knobs read_knobs() {
     if (const char* e = getenv("VRT_OVERLAP_SINGLE")) k.overlap_single = atoi(e) != 0;
     if (const char* e = getenv("VRT_TIME_EVERY")) { const int v = atoi(e); if (v >= 1 && v <= 1024) k.time_every = v; }   // 0 (default): by launch size
     if (const char* e = getenv("VRT_GATE_EXTRA")) { const int v = atoi(e); if (v >= 0 && v <= 4) k.gate_extra = v; }
-    if (const char* e = getenv("VRT_FULL_BELOW")) { const int v = atoi(e); if (v >= 1 && v <= 3) k.full_below = v; }
+    if (const char* e = getenv("VRT_FULL_BELOW")) { const int v = atoi(e); if (v >= 0 && v <= 3) k.full_below = v; }   // 0: no overlapped launch takes every slot, whatever the host's timing (tests)
     if (const char* e = getenv("VRT_DEFER")) { const int v = atoi(e); if (v >= 0 && v <= VRT_MAX_DEFER) k.defer4 = k.defer8 = v < 1 ? 1 : v; }   // 0, 1: a pass per launch
     if (const char* e = getenv("VRT_CHUNK")) { const int v = atoi(e); if (v >= 64 && v <= 4096) k.chunk = v / 64 * 64; }
+    if (const char* e = getenv("VRT_PREPASS")) { const int v = atoi(e); if (v >= 0 && v <= 2) k.prepass = v; }
     if (const char* e = getenv("VRT_CAST_VIEW")) k.cast_view = strcmp(e, "staged") == 0 ? 1 : strcmp(e, "global") == 0 ? 0 : -1;
 #endif
     return k;
@@ -104,6 +107,30 @@ static inline RenderVariant plan_render_variant(const RenderInputs& in) {
     v.share_primary = v.pooled && in.fused > 1 && (!v.instr || in.count_as_timed);   // (counting the reference's work: every camera ray is walked)
     return v;
 }
+
+// Whether a launch is preceded by the pre-pass that leaves its camera-ray records (k_primary_records, vrt_kernels.hip), and whether
+// the launch is told so.  The pre-pass is a lean kernel for the wave slot that two pooled waves of 208 registers leave empty on a
+// SIMD; it is queued on the launch's own lane, where it runs while the launches of the other lanes hold the heavy slots.  So only
+// launches that have such neighbours and such a slot: overlapped ones of half the slots (grid_div 2: the four-deep pipeline and the
+// queue-lean shapes, with or without the context's stream as a lane) that do not find the pipeline empty (`lone`: they take every
+// slot), whose samples share the record table, and not the twelve-wave geometry (its three waves leave no registers).  Launches
+// that count the reference's work walk every camera ray themselves.  Everything else -- lone launches, the two-deep 4K mode, the
+// eight-deep small-launch mode, ReSTIR, one-sample calls -- is queued as it was.  knob: Knobs::prepass.
+struct Prepass { bool queue, tell; };
+static inline Prepass plan_prepass(const RenderVariant& v, bool overlapped, bool lone, int grid_div, int knob) {
+    Prepass p;
+    p.queue = knob != 0 && overlapped && !lone && grid_div == 2 && v.pooled && v.share_primary && !v.instr && !v.dense12 && !v.restir;
+    p.tell = p.queue && knob != 2;
+    return p;
+}
+// The launch numbers.  A launch takes the next number when it is queued (plan_seq_take); its records carry the number as their tag
+// (+ 1), and a tag must never come to mean two launches -- a launch with another camera would take the first one's records for its
+// own.  A pre-pass is queued AHEAD of its launch and is handed the number the launch will take (plan_seq_reserve); if the launch is
+// then not queued after all (a queue operation between the two failed: abort_pipeline), plan_seq_abort burns the number.
+struct LaunchSeq { unsigned next = 0; bool reserved = false; };
+static inline unsigned plan_seq_reserve(LaunchSeq& s) { s.reserved = true; return s.next; }
+static inline unsigned plan_seq_take(LaunchSeq& s) { s.reserved = false; return s.next++; }
+static inline void plan_seq_abort(LaunchSeq& s) { if (s.reserved) { s.next++; s.reserved = false; } }
 
 // How deep a launch of `items` work items (pixels x fused samples) wants the pipeline.  A launch lasts at least as long as its
 // deepest path takes alone (about 0.2 ms at 8 bounces), whatever its size, and a workgroup slot its wave has left stays empty

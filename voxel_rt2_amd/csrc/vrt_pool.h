@@ -87,10 +87,20 @@ VRT_DEV uint32_t normal_code(f3 n) {
 VRT_DEV float normal_comp(uint32_t c) { return dm_u2f(((c & 1u) << 31) | ((c & 2u) ? 0x3f800000u : 0u)); }
 VRT_DEV f3 normal_decode(uint32_t c) { return mk3(normal_comp(c), normal_comp(c >> 2), normal_comp(c >> 4)); }
 
+// The three words a walk's progress is kept in: PF_T, PF_CELL_XY, PF_CELL_Z (with the LOD and the unflipped normal code).  The ONE
+// place each is packed: a slot (walk_store) and a camera-ray record made without a slot (walk_pack, primary_record_walk) hold the same
+// words.  (One function per word, and walk_store packs and stores word by word as it always did: with the three packed first and stored
+// afterwards the pooled kernels came out scheduled differently around every walk_store.)
+VRT_DEV uint32_t walk_word_t(const RayWalk& w) { return dm_f2u(w.t); }
+VRT_DEV uint32_t walk_word_xy(const RayWalk& w) { return ((uint32_t)w.ix & 0xffffu) | ((uint32_t)w.iy << 16); }
+VRT_DEV uint32_t walk_word_z(const RayWalk& w) { return ((uint32_t)w.iz & 0xffffu) | ((uint32_t)w.lod << 16) | (normal_code(w.hn) << 20); }
+VRT_DEV void walk_pack(const RayWalk& w, uint32_t& t, uint32_t& cell_xy, uint32_t& cell_z) {
+    t = walk_word_t(w); cell_xy = walk_word_xy(w); cell_z = walk_word_z(w);
+}
 VRT_DEV void walk_store(const SlotRef& s, const RayWalk& w) {
-    s.sf(PF_T, w.t);
-    s.su(PF_CELL_XY, ((uint32_t)w.ix & 0xffffu) | ((uint32_t)w.iy << 16));
-    s.su(PF_CELL_Z, ((uint32_t)w.iz & 0xffffu) | ((uint32_t)w.lod << 16) | (normal_code(w.hn) << 20));
+    s.su(PF_T, walk_word_t(w));
+    s.su(PF_CELL_XY, walk_word_xy(w));
+    s.su(PF_CELL_Z, walk_word_z(w));
     s.su(PF_ITERS, (uint32_t)w.iters);
 }
 VRT_DEV void walk_store_constants(const SlotRef& s, const RayWalk& w) {
@@ -299,6 +309,32 @@ VRT_DEV int pool_begin_known(const FrameParams& fp, const SlotRef& s, int u, int
     s.su(PF_FLOOR_T, rec.ft);
     s.su(PF_T, rec.x); s.su(PF_CELL_XY, rec.y); s.su(PF_CELL_Z, rec.z); s.su(PF_ITERS, 0u);
     return slot_state_after_walk<G>(dm_u2f(rec.x), dm_u2f(rec.ft));
+}
+
+// The record the pooled schedule leaves for sample 0 of pixel (u, v), made without a pool: what BEGIN sets up (pool_begin: the
+// camera ray from fp.camera_pos, its floor distance, the prepared walk) and, where there is something to walk, what the WALK stage
+// ends on -- the same walk_trip / descend_flat on the pyramid in global memory, carried the way that stage and probe_ray's
+// PROBE_WALK_RECORD carry it.  A walk suspended into a slot comes back as the bits it was (walk_load), so walking it in one go gives
+// the same three words.  A ray with nothing to walk (culled, or the grid box missed) gets the record BEGIN gives it.  k_primary_records
+// fills a launch's table with these ahead of the launch, so that its BEGIN starts sample 0 from the record as it starts the others.
+template <int G, bool CULL>
+VRT_DEV PrimaryRecord primary_record_walk(const FrameParams& fp, const GlobalPyramid<G>& P, const float* cull, int u, int v, uint32_t tag) {
+    const f3 pos = fp.camera_pos, d = camera_ray_dir(fp, u, v);
+    PrimaryRecord r;
+    r.dx = dm_f2u(d.x); r.dy = dm_f2u(d.y); r.dz = dm_f2u(d.z);
+    r.ft = dm_f2u(floor_probe(fp, pos, d));
+    RayWalk w;
+    if (walk_prepare<G, CULL>(world_to_voxel<G>(pos), d, w, cull)) {
+        BrickCache bc;
+        bc.key = -1; bc.word = 0ULL;
+        CoarseWords cw;
+        coarse_fetch(P, w.ix, w.iy, w.iz, cw);
+        int nq;
+        while (!walk_trip(P, w, bc, cw, nq)) {}
+    }
+    walk_pack(w, r.x, r.y, r.z);
+    r.w = primary_check(r, tag);
+    return r;
 }
 
 // BEGIN: work item (u, v, sample) -> camera ray pending.
