@@ -451,6 +451,36 @@ enum { VRT_DIST_TO_EMPTY = 1 };
 #define VRT_DIST_MAX_D2 195075            /* 3 * 255^2: every distance a 256^3 grid holds */
 int vrt_distance_field(vrt_ctx* ctx, const int32_t lo[3], const int32_t hi[3], int32_t max_d2, uint32_t flags,
                        void* d2 /* int32[hx][hy][hz] */, void* nearest /* int32[hx][hy][hz], may be NULL */, int on_device);
+/* Ask a PREPARED grid which voxels of the box [lo, hi) hang together: connected-component labels, on the device.
+ * CELLS AND MEMBERS.  Only the cells of the box take part; they live in the index space of vrt_upload_voxels.  A cell is SOLID iff its
+ * stored material byte is > 0 (signed) -- the same rule as vrt_distance_field and vrt_sweep_boxes.  The MEMBERS are the solid cells of
+ * the box; with VRT_LABEL_EMPTY in `flags` they are the non-solid cells of the box instead.  The floor plane is not a cell.
+ * vrt_set_reference_indexing does not change the answer.
+ * ADJACENCY.  Two members are adjacent iff their coordinates differ by at most 1 on every axis and by 1 in total (the 6 face
+ * neighbours; the default); with VRT_LABEL_CONN_18 by at most 2 in total (faces and edges), with VRT_LABEL_CONN_26 by at most 3 (faces,
+ * edges and corners).  Both connectivity flags at once are VRT_E_INVALID.  Cells outside the box DO NOT EXIST: a component that
+ * continues outside the box is cut at the box's faces, and two parts of the box that are joined only through cells outside it are two
+ * components -- on purpose, and unlike vrt_distance_field, whose targets outside the box count.  Cells outside the grid never exist.
+ * LABEL.  A COMPONENT is a class of the transitive closure of adjacency.  labels[c] is the smallest linear GRID index
+ * (x * grid_res + y) * grid_res + z among the cells of c's component, and -1 where c is not a member.  A cell is the ROOT of its
+ * component iff labels[c] is its own index.  The labels are a function of the grid, the box and the flags alone.  At 256^3 they reach
+ * 16 777 215 and stay positive in int32.  labels is int32[hx][hy][hz] over the cells of the box, C order, z fastest.
+ * RESULT (may be NULL).  cells: the number of members; components: the number of roots; reserved: 0.  `result` lives where `labels`
+ * lives: host memory with on_device = 0, device memory with on_device = 1.
+ * ORDERING AND PURITY are vrt_distance_field's: the call is queued on the context's stream, behind every edit queued so far and ahead of
+ * later ones; the pending accumulation is not forced; no history, g-buffer, counter or statistic is touched, and frames rendered
+ * around it are bit for bit the frames rendered without it.  on_device = 0: host arrays, the call returns when they are filled; = 1:
+ * device memory, the work is only queued: the call does not synchronise with the host.
+ * Scratch: the union-find works in the output array itself.  Besides it the context holds a few counter words, and on the host path it
+ * stages 4 bytes per box cell plus 16 -- in a buffer of the context's own (not the distance field's, the voxeliser's or the query
+ * staging buffer), grown on demand, kept by the context, freed by vrt_destroy.
+ * VRT_E_INVALID: NULL ctx, lo, hi or labels; lo > hi or a box outside the grid (vrt_update_voxels' rules); unknown flag bits or both
+ * connectivity bits; on_device not 0 or 1.  VRT_E_STATE: before vrt_prepare, or after a vrt_upload_voxels that no vrt_prepare has
+ * followed.  An empty box returns VRT_OK, writes no label and zeroes `result`.  No counterpart in the reference. */
+enum { VRT_LABEL_EMPTY = 1, VRT_LABEL_CONN_18 = 2, VRT_LABEL_CONN_26 = 4 };
+typedef struct vrt_label_result { int64_t cells; int32_t components; int32_t reserved; } vrt_label_result;            /* 16 bytes */
+int vrt_label_components(vrt_ctx* ctx, const int32_t lo[3], const int32_t hi[3], uint32_t flags,
+                         void* labels /* int32[hx][hy][hz] */, vrt_label_result* result /* may be NULL */, int on_device);
 /* Renderer.accumulate_clouds / compute_atmosphere (pathtracer.py:325-329) */
 int vrt_sky_accumulate_clouds(vrt_ctx* ctx, int max_samples);
 int vrt_sky_compute_slice(vrt_ctx* ctx, int slice_idx, int max_slices);

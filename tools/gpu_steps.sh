@@ -17,6 +17,8 @@
 #   voxelizerate    tools/voxelize_rate.py: ms a call of vrt_voxelize_triangles next to vrt_update_voxels of the same box -> voxelize_rate.jsonl under this run's output folder
 #   fillrate        tools/fill_rate.py: ms a call of vrt_fill_triangles next to vrt_voxelize_triangles of the same mesh and vrt_update_voxels of the same box -> fill_rate.jsonl under this run's output folder
 #   distancerate    tools/distance_rate.py: ms a call of vrt_distance_field (d2; d2 + nearest) next to vrt_fetch_voxels of the same box -> distance_rate.jsonl under this run's output folder
+#   labelrate       tools/label_rate.py: ms a call of vrt_label_components next to vrt_fetch_voxels and vrt_distance_field of the same box -> label_rate.jsonl under this run's output folder
+#   labelkernels    tools/label_kernels.py: the three k_label_* kernels' durations per configuration, from a kernel trace -> label_kernels.jsonl under this run's output folder
 #   trace:CASE      rocprofv3 --kernel-trace --stats of bench_scenes.py CASE (CASE = bench: the bench command, config 2)
 #   pmc:CASE        tools/pmc.sh CASE + summary
 #   timeline:CASE[:MODE[:LAG]]  launches and copies in time (tools/timeline.py)
@@ -77,6 +79,13 @@ for l in open('$O/scenes${arg:+_}${arg//,/_}.jsonl'):
     distancerate)
       timeout -k 10 300 python tools/distance_rate.py --out $O/distance_rate.jsonl > $O/distance_rate.out 2> $O/distance_rate.err || { rc=$?; tail -5 $O/distance_rate.err; fail distancerate $rc; }
       tail -1 $O/distance_rate.out ;;
+    labelrate)
+      timeout -k 10 300 python tools/label_rate.py --out $O/label_rate.jsonl > $O/label_rate.out 2> $O/label_rate.err || { rc=$?; tail -5 $O/label_rate.err; fail labelrate $rc; }
+      tail -2 $O/label_rate.out ;;
+    labelkernels)
+      here=$PWD   # (the repository's root: the script has changed into it)
+      ( cd /tmp; export TMPDIR=/tmp; timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d $O/trace_label -o t -- python $here/tools/label_kernels.py run > $O/label_kernels.out 2> $O/label_kernels.err ) || fail labelkernels $?
+      python tools/label_kernels.py digest $O/trace_label $O/label_kernels.jsonl; rm -rf $O/trace_label ;;
     trace)
       ( cd /tmp; export TMPDIR=/tmp
         if [ "$arg" == "bench" ]; then timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -o t -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.json 2> $O/trace_bench.err

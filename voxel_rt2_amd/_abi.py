@@ -33,6 +33,10 @@ assert TRIANGLE.itemsize == 48 and VOXELIZE_RESULT.itemsize == 40
 DIST_TO_EMPTY = 1
 DIST_FAR = 0x7FFFFFFF
 DIST_MAX_D2 = 195075
+# vrt_label_result (vrt_label_components)
+LABEL_EMPTY, LABEL_CONN_18, LABEL_CONN_26 = 1, 2, 4
+LABEL_RESULT = np.dtype([("cells", np.int64), ("components", np.int32), ("reserved", np.int32)])
+assert LABEL_RESULT.itemsize == 16
 # vrt_path_ray / vrt_radiance (vrt_trace_radiance)
 PATH_RAY = np.dtype([("origin", np.float32, 3), ("stream", np.uint32), ("dir", np.float32, 3), ("reserved", np.uint32)])
 RADIANCE = np.dtype([("rgb", np.float32, 3), ("t", np.float32)])
@@ -124,6 +128,7 @@ def declare(lib, prefix):
     sig("gather_probes", C.c_int, P, C.c_int64, P, C.c_int, C.c_uint32, P, C.c_int)
     sig("fetch_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
     sig("distance_field", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, P, P, C.c_int)
+    sig("label_components", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, P, P, C.c_int)
     sig("sky_accumulate_clouds", C.c_int, P, C.c_int)
     sig("sky_compute_slice", C.c_int, P, C.c_int, C.c_int)
     sig("sky_accumulate_clouds_slice", C.c_int, P, C.c_int, C.c_int, C.c_int)

@@ -250,6 +250,47 @@ class NativeSession:
         self._call("distance_field", (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), max_d2, flags, ptrs[0], ptrs[1], 0)
         return parts if nearest else parts[0]
 
+    def label_components(self, lo, hi, connectivity=6, empty=False, out=None):
+        """The connected components of the solid cells of the box [lo, hi) (empty: of its non-solid cells) under 6-, 18- or
+        26-connectivity: every member labelled with the smallest linear grid index of its component, every other cell -1
+        (include/vrt_api.h, vrt_label_components).  Cells outside the box do not exist.  Host path: returns (labels, result) -- an
+        int32 array of shape hi - lo (`out` if given, filled in place) and the dict of cells, components, reserved.  Device path:
+        `out` is a torch int32 tensor on the device of that shape, or the pair (labels, result) with `result` a device tensor of 16
+        bytes (_abi.LABEL_RESULT), taken without a copy; the work is queued on the session's stream and `out` is returned, not yet
+        filled."""
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError("lo and hi are three coordinates each")
+        if connectivity not in (6, 18, 26):
+            raise ValueError("connectivity is 6, 18 or 26")
+        shape = tuple(max(h - l, 0) for l, h in zip(lo, hi))
+        flags = C.c_uint32({6: 0, 18: _abi.LABEL_CONN_18, 26: _abi.LABEL_CONN_26}[connectivity] | (_abi.LABEL_EMPTY if empty else 0))
+        box = ((C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi))
+        labels, result = out if isinstance(out, (tuple, list)) else (out, None)
+        if hasattr(labels, "data_ptr"):
+            import torch
+            if labels.dtype != torch.int32 or tuple(labels.shape) != shape or not labels.is_contiguous():
+                raise ValueError(f"device path: the labels are a contiguous int32 device tensor of shape {list(shape)}")
+            if result is not None and (not hasattr(result, "data_ptr") or result.numel() * result.element_size() != 16 or not result.is_contiguous()):
+                raise ValueError("device path: `result` is a contiguous device tensor of 16 bytes")
+            res = C.c_void_p(result.data_ptr()) if result is not None else None
+            if labels.numel():   # (an empty tensor's pointer may be NULL, which the library refuses; it checks box and state all the same)
+                self._call("label_components", *box, flags, C.c_void_p(labels.data_ptr()), res, 1)
+            else:
+                self._call("label_components", *box, flags, C.c_void_p(result.data_ptr()) if result is not None else np.zeros(1, np.int32).ctypes.data_as(C.c_void_p), res,
+                           1 if result is not None else 0)
+            return out
+        if result is not None:
+            raise ValueError("host path: `out` is the labels array; the result record is returned")
+        if labels is None:
+            labels = np.empty(shape, np.int32)
+        if not isinstance(labels, np.ndarray) or labels.dtype != np.int32 or labels.shape != shape or not labels.flags.c_contiguous:
+            raise ValueError(f"`out` is a contiguous int32 array of shape {list(shape)}")
+        rec = np.zeros(1, _abi.LABEL_RESULT)
+        ptr = labels.ctypes.data_as(C.c_void_p) if labels.size else np.zeros(1, np.int32).ctypes.data_as(C.c_void_p)   # (as above)
+        self._call("label_components", *box, flags, ptr, rec.ctypes.data_as(C.c_void_p), 0)
+        return labels, {k: int(rec[0][k]) for k in ("cells", "components", "reserved")}
+
     def upload_materials(self, table):
         table = np.ascontiguousarray(table, dtype=np.float32)
         if table.shape != (128, 14):

@@ -122,6 +122,8 @@ struct vrt_ctx {
     size_t vox_bytes = 0;
     uint8_t* d_dist = nullptr;        // vrt_distance_field: the passes' values and chosen coordinates, and on the host path the staged results (plan_distance_layout; grown on demand)
     size_t dist_bytes = 0;
+    uint8_t* d_label = nullptr;       // vrt_label_components: the counter words and on the host path the staged labels (plan_label_layout; grown on demand)
+    size_t label_bytes = 0;
     uint8_t* d_radiance_plane = nullptr;   // vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes: a work counter (256 bytes) and the scratch plane of VRT_RADIANCE_ITEMS item values (allocated on first use)
     float* d_mats = nullptr;
     Counters* d_counters = nullptr;

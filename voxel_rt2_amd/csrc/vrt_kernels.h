@@ -18,6 +18,7 @@
 #include "vrt_voxelize.h"
 #include "vrt_fill.h"
 #include "vrt_distance.h"
+#include "vrt_label.h"
 #include "vrt_query.h"
 #include "vrt_denoise.h"
 
@@ -91,6 +92,10 @@ hipError_t launch_fill_resolve(hipStream_t st, int grid_res, const EditBox& clip
 struct DistScratch { int* a; int* b; uint8_t* cz; uint8_t* cy; };
 // k_dist_z, k_dist_y, k_dist_x, one after the other on `st`: d2 (and nearest, unless NULL) of the cells of p.box (not empty), device memory
 hipError_t launch_distance_field(hipStream_t st, int grid_res, const DistBox& p, const int8_t* mat, const DistScratch& s, int* d2, int* nearest);
+// vrt_label_components (vrt_label.h): k_label_tile, k_label_seams (where the box has more than one tile) and k_label_finish, one after the
+// other on `st`, behind a memset of `counters` (the 16-byte record k_label_finish adds members and roots to).  labels: int32 per cell of
+// p.box (not empty), device memory, every word written; the union-find works in it.
+hipError_t launch_label_components(hipStream_t st, const LabelBox& p, const int8_t* mat, int* labels, vrt_label_result* counters);
 // A sampled query Q (vrt_query.h:RadianceQuery, SensorQuery, ProbeQuery): samples [s0, s0 + count) of n records (device memory) worked into
 // plane[n * count] by the query's item kernel (k_trace_radiance, k_gather_irradiance, k_gather_probes) and folded into out[n] (k_fold_query).
 // n * count <= Q::max_items; staged / oob as for launch_cast_rays; head: one word of device memory, the launch's work counter.

@@ -2065,6 +2065,91 @@ hipError_t launch_distance_field(hipStream_t st, int grid_res, const DistBox& p,
     return nearest ? launch_distance_passes<true>(st, grid_res, p, mat, s, d2, nearest) : launch_distance_passes<false>(st, grid_res, p, mat, s, d2, nullptr);
 }
 
+// ---- vrt_label_components: a union-find in the output array (vrt_label.h holds the arithmetic and the proof, vrt_plan.h the tile shape) --------
+// Three launches; the kernel boundary is the only barrier between workgroups, and no thread ever waits for another: every loop is
+// label_find's or label_union's, bounded by vrt_label.h's first sentence.
+//   k_label_tile    a workgroup a tile: material bytes straight from d_mat (a wave's lanes on 64 consecutive z: one segment), members
+//                   seeded with their tile-local name in LDS, united with their forward neighbours inside the tile by LDS atomics, and
+//                   every cell's word stored -- the grid index of its tile root, or VRT_LABEL_NONE.
+//   k_label_seams   a workgroup a tile again: a thread a slot on a tile face, united with the forward neighbours that lie in another tile.
+//                   The label array is touched through agent-scope relaxed atomic loads and atomic min only (LabelWords): a plain load
+//                   could be served by an L1 or by another XCD's L2 that nobody refreshes.  Even so nothing here NEEDS a fresh
+//                   value -- a stale one is an earlier parent, and vrt_label.h's second sentence covers it.
+//   k_label_finish  a thread a cell: walks to its root and stores it in place (one more parent to whoever still reads the word);
+//                   members and roots counted by ballot per wave, summed over the workgroup's four waves in LDS, one atomic per
+//                   counter word and workgroup.
+struct LabelLds {   // names: tile-local slots
+    int* s;
+    VRT_DEV int load(int i) const { return __hip_atomic_load(s + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    VRT_DEV int atomic_min(int i, int v) const { return __hip_atomic_fetch_min(s + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+};
+struct LabelWords {   // names: grid indices; the words sit box-locally
+    int* L;
+    const LabelBox& p;
+    VRT_DEV int load(int g) const { return __hip_atomic_load(L + label_box_of_grid(p, g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    VRT_DEV int atomic_min(int g, int v) const { return __hip_atomic_fetch_min(L + label_box_of_grid(p, g), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    VRT_DEV void store(int g, int v) const { __hip_atomic_store(L + label_box_of_grid(p, g), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+__global__ __launch_bounds__(256) void k_label_tile(LabelBox p, const int8_t* __restrict__ mat, int* __restrict__ L) {
+    __shared__ int s[VRT_LABEL_TILE];
+    const LabelTile r = label_tile(p, blockIdx.x);
+    LabelLds m{s};
+    for (int t = threadIdx.x; t < VRT_LABEL_TILE; t += 256) s[t] = label_tile_seed(p, r, mat, t);
+    __syncthreads();
+    for (int t = threadIdx.x; t < VRT_LABEL_TILE; t += 256) {
+        if (m.load(t) < 0) continue;
+        for (int k = 0; k < p.forward; k++) label_tile_link(m, r, t, k);
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < VRT_LABEL_TILE; t += 256) {
+        int lx, ly, lz;
+        label_tile_cell(t, lx, ly, lz);
+        if (label_in_tile(r, lx, ly, lz)) L[label_box_index(p, r.o[0] + lx, r.o[1] + ly, r.o[2] + lz)] = label_tile_result(m, p, r, t);
+    }
+}
+__global__ __launch_bounds__(256) void k_label_seams(LabelBox p, int* L) {
+    const LabelTile r = label_tile(p, blockIdx.x);
+    LabelWords m{L, p};
+    for (int t = threadIdx.x; t < VRT_LABEL_TILE; t += 256) {
+        int lx, ly, lz;
+        label_tile_cell(t, lx, ly, lz);
+        if (!label_in_tile(r, lx, ly, lz) || !label_on_seam(p, r, lx, ly, lz)) continue;
+        if (m.load(label_grid_index(p, r.o[0] + lx, r.o[1] + ly, r.o[2] + lz)) < 0) continue;
+        for (int k = 0; k < p.forward; k++) label_seam_link(m, p, r, t, k);
+    }
+}
+__global__ __launch_bounds__(256) void k_label_finish(LabelBox p, int* L, vrt_label_result* counters) {
+    __shared__ int part[4][2];
+    const int nv = p.n[0] * p.n[1] * p.n[2], i = blockIdx.x * 256 + threadIdx.x;
+    LabelWords m{L, p};
+    bool member = false, root = false;
+    if (i < nv) label_finish_cell(m, p, i / (p.n[2] * p.n[1]), i / p.n[2] % p.n[1], i % p.n[2], member, root);
+    const int members = __popcll(__ballot(member)), roots = __popcll(__ballot(root));
+    if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6][0] = members; part[threadIdx.x >> 6][1] = roots; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int cells = part[0][0] + part[1][0] + part[2][0] + part[3][0], comps = part[0][1] + part[1][1] + part[2][1] + part[3][1];
+        if (cells) atomicAdd((unsigned long long*)&counters->cells, (unsigned long long)cells);
+        if (comps) atomicAdd(&counters->components, comps);
+    }
+}
+hipError_t launch_label_components(hipStream_t st, const LabelBox& p, const int8_t* mat, int* labels, vrt_label_result* counters) {
+    const int nv = edit_box_voxels(p.box);
+    if (nv == 0) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(counters, 0, sizeof(vrt_label_result), st);
+    if (e != hipSuccess) return e;
+    const int tiles = label_tile_count(p);
+    hipLaunchKernelGGL(k_label_tile, dim3(tiles), dim3(256), 0, st, p, mat, labels);
+    VRT_LAUNCH_CHECK();
+    if (tiles > 1) {   // (a lone tile has no seam)
+        hipLaunchKernelGGL(k_label_seams, dim3(tiles), dim3(256), 0, st, p, labels);
+        VRT_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_label_finish, dim3((nv + 255) / 256), dim3(256), 0, st, p, labels, counters);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
 // A sampled query's chunk -- samples [s0, s0 + count) of n records -- worked into `plane` by the query's item kernel and folded into `out`.
 // n * count is at most Q::max_items (plan_query_chunk); `head`: the launch's work counter, zeroed here on the stream.
 template <class Q>

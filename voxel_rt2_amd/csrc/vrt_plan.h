@@ -332,6 +332,26 @@ static inline DistLayout plan_distance_layout(size_t gx, size_t gy, size_t bx, s
     return l;
 }
 
+// ---- vrt_label_components (vrt_label.h) -------------------------------------------------------------------------------------------------
+// The tile a workgroup of k_label_tile solves in LDS, cut from the box's own corner: memory is z-fastest, so the long edge is z and a
+// wave's 64 lanes sit on 64 consecutive z -- one coalesced 64-byte segment of material bytes, 64 consecutive LDS words.  8 x 8 x 64
+// cells are 16 KB of int32: three workgroups a CU's LDS, and a quarter of a tile's cells lie on a face the seam pass must visit.
+#define VRT_LABEL_TX 8
+#define VRT_LABEL_TY 8
+#define VRT_LABEL_TZ 64
+#define VRT_LABEL_TILE (VRT_LABEL_TX * VRT_LABEL_TY * VRT_LABEL_TZ)
+// The scratch of one call: the union-find works in the output array itself, so the context holds the counter words only -- laid out
+// as the 16-byte result record (members, roots, 0), which k_label_finish adds to -- and on the host path the staged labels
+// int32[bx][by][bz] behind them: 4 bytes per box cell plus the record.
+struct LabelLayout { size_t result_at, labels_at, bytes; };
+static inline LabelLayout plan_label_layout(size_t nv, bool staged) {
+    LabelLayout l;
+    l.result_at = 0;
+    l.labels_at = 256;
+    l.bytes = l.labels_at + (staged ? (4 * nv + 255) & ~(size_t)255 : 0);
+    return l;
+}
+
 // ---- the sampled queries: vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes (vrt_query.h) ----------------------------------------------------
 // The work item is (record, sample) -- (ray, sample) or (sensor, sample); a finished item leaves its value in a scratch plane -- 12 bytes
 // an item for a radiance, a 32-byte vrt_irradiance record of four terms for a sensor -- which k_fold_query sums per record in sample

@@ -1,5 +1,5 @@
 // vrt_scene_ops.hip -- the calls on a prepared scene: the box edit (vrt_update_voxels), the queries (vrt_cast_rays, vrt_sweep_boxes,
-// vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes), vrt_fetch_voxels, vrt_distance_field and the two triangle edits
+// vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes), vrt_fetch_voxels, vrt_distance_field, vrt_label_components and the two triangle edits
 // (vrt_voxelize_triangles, vrt_fill_triangles).
 // A part of vrt_api.hip's translation unit (#included there behind vrt_pipeline.hip, not compiled by itself), so that everything here
 // stays static.  What the calls share is written once: the scratch buffers' growth (grow_scratch), the box argument's checks
@@ -248,6 +248,46 @@ int vrt_distance_field(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], int
     HIP_TRY(hipMemcpyAsync(d2, d_d2, 4 * nv, hipMemcpyDeviceToHost, c->stream));
     if (nearest) HIP_TRY(hipMemcpyAsync(nearest, d_nearest, 4 * nv, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(sync_stream_only(c, c->stream));
+    return VRT_OK;
+}
+// The connected components of the box's members (vrt_label.h): three launches on the context's stream, reading d_mat as
+// vrt_distance_field does -- so the same ordering, no enter(), no flush.  The union-find works in the labels themselves; the context's
+// own buffer holds the counter words the last launch adds to and, on the host path, the staged labels (plan_label_layout).  Stream order
+// lets the next call reuse it; the host path's copies out of it are waited for here, the device path's copy of the record is queued.
+static_assert(sizeof(vrt_label_result) == 16, "record size of include/vrt_api.h");
+int vrt_label_components(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], uint32_t flags, void* labels, vrt_label_result* result, int on_device) {
+    if (!c || !lo || !hi || !labels) return fail(VRT_E_INVALID, "null argument");
+    if (on_device != 0 && on_device != 1) return fail(VRT_E_INVALID, "on_device must be 0 or 1");
+    const uint32_t both = VRT_LABEL_CONN_18 | VRT_LABEL_CONN_26;
+    const char* const bad = (flags & ~(uint32_t)(VRT_LABEL_EMPTY | both)) != 0u ? "unknown flag bits" : (flags & both) == both ? "VRT_LABEL_CONN_18 and VRT_LABEL_CONN_26 exclude one another" : nullptr;
+    EditBox box;
+    if (const int rc = scene_box(c, lo, hi, "vrt_label_components reads", box, bad)) return rc;
+    const size_t nv = (size_t)edit_box_voxels(box);
+    if (nv == 0) {   // no label to write; the record is zeroed where it lives
+        if (result && !on_device) memset(result, 0, sizeof(*result));
+        if (result && on_device) {
+            HIP_TRY(hipSetDevice(c->device));
+            HIP_TRY(hipMemsetAsync(result, 0, sizeof(*result), c->stream));
+        }
+        return VRT_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const LabelBox p = label_plan_box(box, c->cfg.grid_res, flags);
+    const LabelLayout l = plan_label_layout(nv, !on_device);
+    if (grow_scratch(c, &c->d_label, &c->label_bytes, l.bytes) != VRT_OK) return VRT_E_DEVICE;
+    vrt_label_result* const counters = (vrt_label_result*)(c->d_label + l.result_at);
+    if (on_device) {
+        HIP_TRY(launch_label_components(c->stream, p, c->d_mat, (int*)labels, counters));
+        if (result) HIP_TRY(hipMemcpyAsync(result, counters, sizeof(*result), hipMemcpyDeviceToDevice, c->stream));
+        return VRT_OK;
+    }
+    int* const d_labels = (int*)(c->d_label + l.labels_at);
+    HIP_TRY(launch_label_components(c->stream, p, c->d_mat, d_labels, counters));
+    HIP_TRY(hipMemcpyAsync(labels, d_labels, 4 * nv, hipMemcpyDeviceToHost, c->stream));
+    vrt_label_result r;   // (on this stack frame: the wait below covers it)
+    if (result) HIP_TRY(hipMemcpyAsync(&r, counters, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(sync_stream_only(c, c->stream));
+    if (result) *result = r;
     return VRT_OK;
 }
 // ---- editing the scene with triangles: vrt_voxelize_triangles, vrt_fill_triangles ---------------------------------------------------------

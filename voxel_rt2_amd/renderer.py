@@ -597,6 +597,90 @@ class Renderer(VoxelStore):
         self._edit_from_device(lo, hi, torch.where(gone, torch.zeros_like(bm), bm), torch.where(gone[..., None], torch.zeros_like(bc), bc), reset)
         return count
 
+    # -- what hangs together (include/vrt_api.h, vrt_label_components; no counterpart in the reference) ----------------------------------
+    def _label_box(self, what, lo, hi):
+        if not getattr(self, "_prepared", False):
+            raise NativeError(f"{what} asks a prepared scene: call prepare_data() first")
+        if self._voxels_dirty:
+            self.update_voxels(reset=False)
+        self._push()
+        g = self.voxel_grid_res
+        return [int(v) for v in ((0, 0, 0) if lo is None else lo)], [int(v) for v in ((g, g, g) if hi is None else hi)]
+
+    def label_components(self, lo=None, hi=None, connectivity=6, empty=False):
+        """The connected components of the solid voxels of the box [lo, hi) of array indices -- by default the whole grid -- on the
+        scene as prepare_data() / update_voxels() left it (voxels written with set_voxel and not yet sent go first): (labels, result).
+        labels: an int32 array of shape hi - lo, every solid cell holding the smallest linear array index (x * G + y) * G + z of its
+        component, every other cell -1; result: the dict of `cells` (solid cells) and `components`.  connectivity: 6 (faces), 18 (and
+        edges) or 26 (and corners).  empty=True labels the non-solid cells instead.  Cells outside the box do not exist: a piece that
+        continues outside it is cut at its faces."""
+        lo, hi = self._label_box("label_components", lo, hi)
+        return self._s.label_components(lo, hi, connectivity, empty)
+
+    def _labels_on_device(self, lo, hi, connectivity, empty):
+        """the labels of the box as a torch tensor on the device, computed and waited for"""
+        import torch
+        labels = torch.empty(tuple(max(h - l, 0) for l, h in zip(lo, hi)), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()                               # (allocations are torch's; the library writes on the session's stream)
+        self._s.label_components(lo, hi, connectivity, empty, out=labels)
+        self._s.sync()
+        return labels
+
+    def components(self, lo=None, hi=None, connectivity=6, empty=False):
+        """The table of the components label_components finds, computed on the device (torch.unique and scatter_reduce over the labels)
+        and sorted by root: a dict of device tensors -- root int32[n], the component's smallest linear array index; size int64[n], its
+        cells; lo, hi int32[n, 3], its tight box [lo, hi) of array indices."""
+        import torch
+        lo, hi = self._label_box("components", lo, hi)
+        labels = self._labels_on_device(lo, hi, connectivity, empty)
+        at = torch.nonzero(labels >= 0)                                                         # box-local coordinates, int64[m, 3]
+        root, inverse, size = torch.unique(labels[labels >= 0], return_inverse=True, return_counts=True)
+        cells = (at + torch.tensor(lo, device="cuda")).to(torch.int32)
+        where = inverse[:, None].expand(-1, 3)
+        big = torch.iinfo(torch.int32).max
+        c_lo = torch.full((len(root), 3), big, dtype=torch.int32, device="cuda").scatter_reduce(0, where, cells, "amin")
+        c_hi = torch.full((len(root), 3), -1, dtype=torch.int32, device="cuda").scatter_reduce(0, where, cells, "amax") + 1
+        return dict(root=root, size=size, lo=c_lo, hi=c_hi)
+
+    def floating_voxels(self, lo, hi, connectivity=6):
+        """What would fall: a boolean device tensor of shape hi - lo marking the solid cells of the box [lo, hi) whose component -- cut
+        at the box's faces -- has no cell in the box's lowest layer y == lo[1] (the world's up is y).  Put the box's lowest layer on
+        what carries the scene (the ground, a slab): what is joined to it stands, the rest floats."""
+        import torch
+        lo, hi = self._label_box("floating_voxels", lo, hi)
+        labels = self._labels_on_device(lo, hi, connectivity, False)
+        if labels.numel() == 0:
+            return labels >= 0
+        ground = labels[:, 0, :]
+        return (labels >= 0) & ~torch.isin(labels, torch.unique(ground[ground >= 0]))
+
+    def remove_floating(self, lo, hi, connectivity=6, reset=True):
+        """Carve floating_voxels(lo, hi, connectivity) out of the grid (material 0, colour 0), on the device.  Returns the number of
+        cells that became empty and brings voxel_material / voxel_color in step over the box.  reset: start a fresh accumulation."""
+        import torch
+        gone = self.floating_voxels(lo, hi, connectivity)
+        count = int(gone.sum().item())
+        if count == 0:
+            return 0
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        bm, bc = torch.empty(gone.shape, dtype=torch.int8, device="cuda"), torch.empty(tuple(gone.shape) + (3,), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        self._s.fetch_voxels(lo, hi, bm.data_ptr(), bc.data_ptr(), on_device=True)
+        self._s.sync()
+        self._edit_from_device(lo, hi, torch.where(gone, torch.zeros_like(bm), bm), torch.where(gone[..., None], torch.zeros_like(bc), bc), reset)
+        return count
+
+    def sealed_cavities(self, lo, hi):
+        """The cells a flood from outside cannot reach: a boolean device tensor of shape hi - lo marking the non-solid cells of the box
+        [lo, hi) whose 6-connected component of non-solid cells touches no face of the box."""
+        import torch
+        lo, hi = self._label_box("sealed_cavities", lo, hi)
+        labels = self._labels_on_device(lo, hi, 6, True)
+        if labels.numel() == 0:
+            return labels >= 0
+        faces = torch.cat([f.reshape(-1) for f in (labels[0], labels[-1], labels[:, 0], labels[:, -1], labels[:, :, 0], labels[:, :, -1])])
+        return (labels >= 0) & ~torch.isin(labels, torch.unique(faces[faces >= 0]))
+
     def mesh_box(self, vertices):
         """The box [lo, hi) of array indices that encloses every voxel a mesh with these vertices (world units, any shape (..., 3)) can
         cover, clamped to the grid: what voxelize_triangles takes as lo, hi.  A vertex on a grid plane counts the cells on both sides.
