@@ -211,6 +211,11 @@ void vrt_destroy(vrt_ctx* c) {
     drain_all(c);
     resolve_events(c);
 #if defined(VRT_DEV_KNOBS)   // development build: what the A/B runs and tests/test_gpu_prepass.py read (the shipped library reports nothing)
+    if (getenv("VRT_PRIMARY_REPORT")) {
+        unsigned long long r[2] = {0ULL, 0ULL};
+        if (c->d_pv_report && hipMemcpy(r, c->d_pv_report, sizeof(r), hipMemcpyDeviceToHost) != hipSuccess) (void)hipGetLastError();
+        fprintf(stderr, "vrt: primary vertices served %u of %u render launches, paths finished %llu sent on %llu\n", c->primary_queued, c->passes_n[0], r[0], r[1]);
+    }
     if (getenv("VRT_PREPASS_REPORT")) fprintf(stderr, "vrt: pre-passes queued %u told %u of %u render launches\n", c->prepass_queued, c->prepass_told, c->passes_n[0]);
 #endif
     for (PlaneSet& p : c->sets) {

@@ -80,6 +80,10 @@ struct Lane {
     hipStream_t stream = nullptr;
     uint32_t* pool_scratch = nullptr;
     PrimaryRecord* prim_cache = nullptr;   // camera-ray records of fused launches (allocated on first use)
+    uint32_t* pv_counts = nullptr;         // the queue k_primary_vertex leaves this lane's launch (vrt_primary.h; allocated on first use,
+    uint32_t* pv_entries = nullptr;        // grown when a launch needs more): counter lines, continuation records, leftover items
+    uint32_t* pv_leftovers = nullptr;
+    size_t pv_entry_words = 0, pv_left_words = 0;   // words allocated
     unsigned last_seq = 0;                 // launch_seq + 1 of the last launch queued on this stream (0: none)
     int last_set = -1;                     // the copy that launch wrote: its ev_r is the lane's latest (-1: none since the streams were drained)
 };
@@ -156,6 +160,8 @@ struct vrt_ctx {
     const float* last_gb_depth = nullptr;
     mat4 prev_view{}, prev_proj{};
     uint32_t frame = 0;
+    unsigned primary_queued = 0;      // launches whose primary vertices were shaded ahead of them (plan_primary)
+    unsigned long long* d_pv_report = nullptr;   // development builds with VRT_PRIMARY_REPORT: paths finished ahead of the pool, paths sent on
     unsigned prepass_queued = 0, prepass_told = 0;   // pre-passes queued so far, and those the launch was told of (plan_prepass)
     LaunchSeq launch_seq;     // .next: render launches so far (selects which work counters a launch uses, and its records' tag); .reserved: a pre-pass holds that number (vrt_plan.h)
 

@@ -9,6 +9,7 @@
 #include "vrt_sky.h"
 #include "vrt_path.h"
 #include "vrt_pool.h"
+#include "vrt_primary.h"
 #include "vrt_restir.h"
 #include "vrt_temporal.h"
 #include "vrt_plan.h"
@@ -40,6 +41,8 @@
 #ifndef VRT_POOL_MIN_WAVES
 #define VRT_POOL_MIN_WAVES 2
 #endif
+
+static_assert(VRT_PV_HEADS == VRT_WORK_HEADS, "the queue of vrt_primary.h has a part per work head");
 
 namespace vrt {
 
@@ -118,6 +121,14 @@ hipError_t launch_render_pool(hipStream_t st, int grid_res, const RenderVariant&
 // launch's camera rays under the launch's tag.  fp, sc, v: the launch's own.
 hipError_t launch_primary_records(hipStream_t st, int grid_res, const RenderVariant& v, const FrameParams& fp, const SceneData& sc, PrimaryRecord* prim_cache,
                                   unsigned launch_seq);
+// The primary vertices of pooled launch number launch_seq (plan_primary, vrt_plan.h), behind its pre-pass on the same stream: k_primary_vertex
+// finishes the paths that end at or right behind the primary vertex and leaves the others in pq, whose counts the caller has zeroed in
+// stream order.  launch_render_pool_queued is that launch: the same geometry, residency and scratch as launch_render_pool's.
+hipError_t launch_primary_vertex(hipStream_t st, int grid_res, const RenderVariant& v, const FrameParams& fp, const SceneData& sc, const PixelBuffers& out,
+                                 const PrimaryRecord* prim_cache, unsigned launch_seq, int n_samples, const PrimaryQueue& pq);
+hipError_t launch_render_pool_queued(hipStream_t st, int grid_res, const RenderVariant& v, int n_blocks, const FrameParams& fp, const SceneData& sc,
+                                     const PixelBuffers& out, unsigned* work_counters, unsigned launch_seq, int n_samples, uint32_t* cold,
+                                     uint32_t* drain_signal, PrimaryRecord* prim_cache, const PrimaryQueue& pq);
 hipError_t launch_mat_derived(hipStream_t st, const float* mats, float* mats_x /*[128][8]*/);  // after every material upload
 // spatial reuse over rows [r0, r1); first a per-pixel prepare pass over all rows the launch holds (fp.row0..fp.row1) into gb.geo / gb.src
 hipError_t launch_gris(hipStream_t st, int grid_res, bool instr, const FrameParams& fp, const SceneData& sc, const GrisBuffers& gb, int r0, int r1);

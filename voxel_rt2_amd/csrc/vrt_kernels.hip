@@ -388,14 +388,14 @@ __device__ __forceinline__ int lane_rank(unsigned long long m) {  // set bits of
 // WAVES path pools of SLOTS slots per workgroup: 4 x 128 with two workgroups per CU (two waves per SIMD) by default; the whole l1
 // level of a 256^3 grid leaves room for one workgroup of 8 x 128 per CU; a DENSE 128^3 grid runs one workgroup of 12 x 96 per CU
 // -- three waves per SIMD at 168 registers (k_render_pool_dense12 below).
-template <int G, bool RESTIR, bool INSTR, bool BLACK_SUN, bool CULL, bool D12 = false, bool SERVED = false>   // D12: twelve waves, and SHADE's shadow rays with the branchy descent; SERVED: below
+template <int G, bool RESTIR, bool INSTR, bool BLACK_SUN, bool CULL, bool D12 = false, bool SERVED = false, bool QUEUED = false>   // D12: twelve waves, and SHADE's shadow rays with the branchy descent; SERVED, QUEUED: below
 // 208 registers per wave (the attribute counts half of the unified file): two waves per SIMD then leave the 96 that
 // k_temporal runs in beside them (see there).  The allocator would take 238; the cap costs 28 bytes of scratch.
 // The ReSTIR instantiation (no overlapped launches, so nothing runs beside it) takes the two-wave maximum of 256.
 #ifndef VRT_POOL_HALF_VGPRS
 #define VRT_POOL_HALF_VGPRS 104
 #endif
-__device__ __forceinline__ void render_pool_body(const FrameParams& fp, const SceneData& sc, const PixelBuffers& out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache) {
+__device__ __forceinline__ void render_pool_body(const FrameParams& fp, const SceneData& sc, const PixelBuffers& out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache, const PrimaryQueue& pq = PrimaryQueue{}) {
     constexpr int WAVES = pool_shape<G>(D12).waves, SLOTS = pool_shape<G>(D12).slots;
     constexpr int WORDS = (SLOTS + 63) / 64;
     constexpr bool BIG = (G == 256);   // which coarse levels are staged how: see LdsPyramid2
@@ -475,6 +475,12 @@ __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const Sc
     const uint32_t prim_tag = drain_value;  // launch_seq + 1: unique per launch, never 0
     unsigned head = blockIdx.x & (VRT_WORK_HEADS - 1u);  // workgroups go round-robin over the 8 XCDs
     int heads_left = VRT_WORK_HEADS;
+    // QUEUED: the items of a head are what k_primary_vertex left in its part of the queue -- continuation records first, then leftovers
+    unsigned q_cont = 0u, q_left = 0u;   // wave-uniform: of the current head
+    if constexpr (QUEUED) {
+        q_cont = pq.counts[head * VRT_PV_COUNT_STRIDE]; q_left = pq.counts[head * VRT_PV_COUNT_STRIDE + 1];
+        q_cont = q_cont < pq.cap ? q_cont : pq.cap; q_left = q_left < pq.left_cap ? q_left : pq.left_cap;
+    }
 
 #if defined(VRT_DIAG_REGIONS)
     unsigned long long t_prev = __builtin_readcyclecounter();
@@ -599,6 +605,32 @@ __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const Sc
             const int take = n < 64 ? n : 64;
             unsigned base = 0u, limit = 0u;  // items [base, limit) go to lanes 0.. of this BEGIN
             unsigned range0 = 0u, per_sample = 1u;  // first item of the range they belong to, items per sample in it
+            unsigned q_head = 0u, q_n_cont = 0u;    // QUEUED: the head [base, limit) belongs to, and its continuation records
+            if constexpr (QUEUED) {
+              if (stage == SLOT_EMPTY) {
+                VRT_SUB_START();
+                unsigned got = 0u;
+                if (lane == 0) got = atomicAdd(work_counter + head * VRT_WORK_HEAD_STRIDE, (unsigned)take);
+                got = (unsigned)__builtin_amdgcn_readfirstlane((int)got);
+                const unsigned cnt = q_cont + q_left;
+                q_head = head; q_n_cont = q_cont;
+                base = got;
+                limit = (got + (unsigned)take < cnt) ? got + (unsigned)take : cnt;
+                if (got + (unsigned)take >= cnt) {
+                    heads_left -= 1;
+                    head = (head + 1u) & (VRT_WORK_HEADS - 1u);
+                    q_cont = pq.counts[head * VRT_PV_COUNT_STRIDE]; q_left = pq.counts[head * VRT_PV_COUNT_STRIDE + 1];
+                    q_cont = q_cont < pq.cap ? q_cont : pq.cap; q_left = q_left < pq.left_cap ? q_left : pq.left_cap;
+                    if (heads_left == 0) {
+                        exhausted = true;
+                        if (drain_signal && lane == 0 && atomicExch(work_counter + 1, 1u) == 0u)
+                            __hip_atomic_fetch_max(drain_signal, drain_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    }
+                }
+                if (base > limit) base = limit;
+                VRT_SUB_CLOCK(0);   // (the sub-clocks of the plain BEGIN below, at the same points: reservation, read, set-up)
+              }
+            } else
             if (stage == SLOT_EMPTY) {
                 VRT_SUB_START();
                 // pull from the current head; a used-up range sends the wave on to the next head (and this BEGIN
@@ -641,6 +673,37 @@ __device__ __forceinline__ void render_pool_body(const FrameParams& fp, const Sc
                 } else {
                     VRT_REGION(13);
                     const unsigned my = base + (unsigned)lane;
+                    if constexpr (QUEUED) {
+                        if (my < limit) {
+                            const int slot = (int)list[lane];
+                            s.base = pool + slot;
+                            if (my < q_n_cont) {
+                                constexpr int PW = PrimaryContWords<BLACK_SUN>::count;
+                                const uint32_t* const at = pq.entries + ((size_t)q_head * pq.cap + my) * PW;
+                                uint32_t e[PW];
+#pragma unroll
+                                for (int k = 0; k < PW; k++) e[k] = at[k];
+                                VRT_SUB_CLOCK(1);
+                                state[slot] = (uint32_t)pool_begin_queued<G, CULL, BLACK_SUN>(fp, scl.cull, s, cold_wave + slot * COLD, e, ts);
+                                VRT_SUB_CLOCK(3);   // a set-up with a ray: the bounce ray's
+                            } else {
+                                // a depth-0 item k_primary_vertex left to the pool: as a launch without the queue begins it
+                                const uint32_t item = pq.leftovers[(size_t)q_head * pq.left_cap + (my - q_n_cont)];
+                                const int u = (int)(item & 0xfffu), v = (int)((item >> 12) & 0xfffu), sample = (int)(item >> 28);
+                                const PrimaryRecord rec = primary_record_load(&prim_cache[(v - fp.row0) * fp.W + u]);
+                                const bool known = primary_record_valid(rec, prim_tag);
+                                VRT_SUB_CLOCK(1);
+                                int st;
+                                if (known) st = pool_begin_known<G>(fp, s, u, v, sample, rec);
+                                else {
+                                    st = pool_begin<G, CULL>(fp, scl.cull, s, u, v, sample, ts);
+                                    if (sample == 0 && st != SLOT_RAY) primary_record_store(&prim_cache[(v - fp.row0) * fp.W + u], primary_record(s, prim_tag));
+                                }
+                                state[slot] = (uint32_t)st;
+                                VRT_SUB_CLOCK(known ? 2 : 3);
+                            }
+                        }
+                    } else
                     if (my < limit) {
                         const int slot = (int)list[lane];
                         s.base = pool + slot;
@@ -730,6 +793,84 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(VRT_PRIMARY_HALF
     GlobalPyramid<G> P;
     P.p = sc.pyr;
     primary_record_store(&prim_cache[(v - fp.row0) * fp.W + u], primary_record_walk<G, CULL>(fp, P, sc.cull, u, v, tag));
+}
+
+// The primary vertex of every path of a launch, AHEAD of it (vrt_primary.h): one wave a workgroup, one workgroup an 8x8 tile, a lane
+// a pixel, gated as k_primary_records is, whose records it reads; no LDS, the pyramid (walked by the emitting sun's shadow rays only)
+// and the material table through global memory.  NOT the pre-pass's register budget: at 96 registers it spills 52-97 of them and
+// measures slower than at 160, where it no longer fits beside two pooled waves of a SIMD, only beside one (below).  The g-buffer is
+// written once a pixel; paths that go on are compacted per sample with a ballot and one atomic a wave onto the queue of head (tile % 8).
+#ifndef VRT_PRIMARY_VERTEX_HALF_VGPRS
+#define VRT_PRIMARY_VERTEX_HALF_VGPRS 80   // 160 registers: no spills under a black sun, 5-11 under an emitting one; three waves a SIMD where no pooled wave is, one beside
+                                           // a single pooled wave -- the slots a draining launch frees.  Measured against 96 (beside two pooled waves, 52-97 spills), 128 and 256: DESIGN.md section 7
+#endif
+#if 2 * VRT_PRIMARY_VERTEX_HALF_VGPRS + 2 * VRT_POOL_HALF_VGPRS > 512
+#error "k_primary_vertex must fit beside one pooled wave of a SIMD at least"   // (or it only runs where the chip is empty)
+#endif
+template <int G, bool BLACK_SUN, bool CULL>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(VRT_PRIMARY_VERTEX_HALF_VGPRS))) void k_primary_vertex(FrameParams fp, SceneData sc, PixelBuffers out, const PrimaryRecord* prim_cache, uint32_t tag, int n_samples, PrimaryQueue pq) {
+    const int tiles_x = (fp.W + 7) >> 3;
+    const unsigned tile = blockIdx.x, in = threadIdx.x;
+    const int u = (int)(tile % (unsigned)tiles_x) * 8 + (int)(in & 7u);
+    const int v = launch_tile_row(fp, (int)(tile / (unsigned)tiles_x)) + (int)(in >> 3);
+    const bool live = u < fp.W && v < fp.row1 && launch_renders_row(fp, v) && !outside_render_area(fp, (float)u, (float)v);
+    const unsigned head = tile & (VRT_PV_HEADS - 1u);
+    constexpr int PW = PrimaryContWords<BLACK_SUN>::count;
+    GlobalPyramid<G> P;
+    P.p = sc.pyr;
+    TraceStats ts;
+    stats_zero(ts);
+    PrimaryRecord rec;
+    rec.x = rec.y = rec.z = rec.dx = rec.dy = rec.dz = rec.ft = rec.w = 0u;
+    bool known = false;
+    Hit h;
+    hit_init(h);
+    int state = SLOT_ESCAPE;
+    if (live) {
+        rec = primary_record_load(&prim_cache[(v - fp.row0) * fp.W + u]);
+        known = primary_record_valid(rec, tag);
+        if (known) {
+            state = primary_vertex_hit<G>(fp, sc, rec, h, ts);
+            primary_vertex_gbuffer(fp, out, u, v, rec, h);
+        }
+    }
+    unsigned n_done = 0u, n_on = 0u;
+    for (int sample = 0; sample < n_samples; sample++) {
+        Path<false> p;
+        bool on = false;
+        if (known) on = primary_vertex_sample<G, BLACK_SUN, CULL>(fp, sc, P, out, u, v, sample, rec, h, state, p, ts);
+        // continuations: one atomic a wave on the head's record count; a record that does not fit is a leftover
+        const unsigned long long m_on = __ballot(on);
+        bool left = live && !known;
+        if (m_on != 0ULL) {
+            unsigned at = 0u;
+            if (in == (unsigned)__builtin_ctzll(m_on)) at = atomicAdd(&pq.counts[head * VRT_PV_COUNT_STRIDE], (unsigned)__popcll(m_on));
+            at = (unsigned)__shfl((int)at, __builtin_ctzll(m_on), 64) + (unsigned)__popcll(m_on & ((1ULL << in) - 1ULL));
+            if (on) {
+                if (at < pq.cap) primary_cont_pack<BLACK_SUN>(pq.entries + ((size_t)head * pq.cap + at) * PW, p);
+                else left = true;
+            }
+        }
+        const unsigned long long m_left = __ballot(left);
+        if (m_left != 0ULL) {
+            unsigned at = 0u;
+            if (in == (unsigned)__builtin_ctzll(m_left)) at = atomicAdd(&pq.counts[head * VRT_PV_COUNT_STRIDE + 1], (unsigned)__popcll(m_left));
+            at = (unsigned)__shfl((int)at, __builtin_ctzll(m_left), 64) + (unsigned)__popcll(m_left & ((1ULL << in) - 1ULL));
+            if (left && at < pq.left_cap) pq.leftovers[(size_t)head * pq.left_cap + at] = primary_leftover_item(u, v, sample);
+        }
+        if (known && !left) { if (on) n_on++; else n_done++; }
+    }
+    if (pq.report) {   // development builds: the counts the tests read
+        unsigned long long a = n_done, b = n_on;
+        for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
+        if (in == 0u) { atomicAdd(&pq.report[0], a); atomicAdd(&pq.report[1], b); }
+    }
+}
+// QUEUED: the instantiation for launches behind k_primary_vertex (plan_primary, vrt_plan.h): BEGIN resumes the queue's paths at depth 1
+// and takes its leftovers as depth-0 items.  A kernel of its own, so that every other launch runs the machine code it ran before.
+template <int G, bool BLACK_SUN, bool CULL>
+__global__ __launch_bounds__(64 * pool_shape<G>(false).waves, VRT_POOL_MIN_WAVES) __attribute__((amdgpu_num_vgpr(VRT_POOL_HALF_VGPRS))) void k_render_pool_queued(FrameParams fp, SceneData sc, PixelBuffers out, unsigned* work_counter, unsigned* next_counter, int n_samples, uint32_t* cold, uint32_t* drain_signal, uint32_t drain_value, PrimaryRecord* prim_cache, PrimaryQueue pq) {
+    render_pool_body<G, false, false, BLACK_SUN, CULL, false, true, true>(fp, sc, out, work_counter, next_counter, n_samples, cold, drain_signal, drain_value, prim_cache, pq);
 }
 
 // ---- spatial reuse ---------------------------------------------------------------------------
@@ -1546,6 +1687,24 @@ hipError_t launch_primary_records(hipStream_t st, int grid_res, const RenderVari
     if (tiles <= 0) return hipSuccess;
     // the tag the launch itself will look for (launch_render_pool): launch_seq + 1
     VRT_BY_GRID(grid_res, VRT_BY_2(v.cull, false, hipLaunchKernelGGL((k_primary_records<G, A>), dim3(tiles), dim3(64), 0, st, fp, sc, prim_cache, launch_seq + 1u)));
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_primary_vertex(hipStream_t st, int grid_res, const RenderVariant& v, const FrameParams& fp, const SceneData& sc, const PixelBuffers& out,
+                                 const PrimaryRecord* prim_cache, unsigned launch_seq, int n_samples, const PrimaryQueue& pq) {
+    const int tiles = ((fp.W + 7) >> 3) * launch_tile_rows(fp);
+    if (tiles <= 0) return hipSuccess;
+    VRT_BY_GRID(grid_res, VRT_BY_2(v.black_sun, v.cull, hipLaunchKernelGGL((k_primary_vertex<G, A, B>), dim3(tiles), dim3(64), 0, st, fp, sc, out, prim_cache, launch_seq + 1u, n_samples, pq)));
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_render_pool_queued(hipStream_t st, int grid_res, const RenderVariant& v, int n_blocks, const FrameParams& fp, const SceneData& sc,
+                                     const PixelBuffers& out, unsigned* work_counters, unsigned launch_seq, int n_samples, uint32_t* cold,
+                                     uint32_t* drain_signal, PrimaryRecord* prim_cache, const PrimaryQueue& pq) {
+    unsigned* work_counter = work_counters + (launch_seq & 15u) * (VRT_WORK_HEADS * VRT_WORK_HEAD_STRIDE);
+    unsigned* next_counter = work_counters + ((launch_seq + 8u) & 15u) * (VRT_WORK_HEADS * VRT_WORK_HEAD_STRIDE);
+    VRT_BY_GRID(grid_res, VRT_BY_2(v.black_sun, v.cull, hipLaunchKernelGGL((k_render_pool_queued<G, A, B>), dim3(n_blocks), dim3(64 * pool_shape<G>(false).waves), 0, st, fp, sc, out,
+                                                                         work_counter, next_counter, n_samples, cold, drain_signal, launch_seq + 1u, prim_cache, pq)));
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -349,34 +349,95 @@ static PrimaryRecord* lane_prim_cache(vrt_ctx* c, int lane) {
     return l.prim_cache;
 }
 
+// The queue of `lane` for a launch of `tiles` tiles and g samples (plan_primary_caps), allocated on first use and grown behind the
+// lane's stream when a launch needs more than the last did.  False: no memory for it -- the launch is queued without.
+static bool lane_primary_queue(vrt_ctx* c, int lane, const RenderVariant& v, unsigned tiles, int g, PrimaryQueue* q) {
+    Lane& l = c->lanes[lane];
+    const PrimaryCaps caps = plan_primary_caps(tiles, g, c->knobs.primary_cap);
+    const size_t words = v.black_sun ? PrimaryContWords<true>::count : PrimaryContWords<false>::count;
+    const size_t need_e = (size_t)VRT_PV_HEADS * caps.cap * words, need_l = (size_t)VRT_PV_HEADS * caps.left_cap;
+    if (need_e == 0 || need_l == 0) return false;
+    if (need_e > l.pv_entry_words || need_l > l.pv_left_words || !l.pv_counts) {
+        if (l.pv_entries || l.pv_leftovers) { if (hipStreamSynchronize(lane_stream(c, lane)) != hipSuccess) { (void)hipGetLastError(); return false; } }
+        (void)dfree(c, &l.pv_entries); (void)dfree(c, &l.pv_leftovers);
+        l.pv_entry_words = l.pv_left_words = 0;
+        bool ok = l.pv_counts || dalloc(c, &l.pv_counts, (size_t)VRT_PV_HEADS * VRT_PV_COUNT_STRIDE) == hipSuccess;
+        ok = ok && dmalloc(c, &l.pv_entries, need_e * sizeof(uint32_t)) == hipSuccess && dmalloc(c, &l.pv_leftovers, need_l * sizeof(uint32_t)) == hipSuccess;
+        if (!ok) { (void)hipGetLastError(); (void)dfree(c, &l.pv_entries); (void)dfree(c, &l.pv_leftovers); return false; }
+        l.pv_entry_words = need_e; l.pv_left_words = need_l;
+    }
+#if defined(VRT_DEV_KNOBS)
+    if (!c->d_pv_report && getenv("VRT_PRIMARY_REPORT") && dalloc(c, &c->d_pv_report, 2) != hipSuccess) { (void)hipGetLastError(); (void)dfree(c, &c->d_pv_report); }
+#endif
+    q->counts = l.pv_counts; q->entries = l.pv_entries; q->leftovers = l.pv_leftovers;
+    q->cap = caps.cap; q->left_cap = caps.left_cap;
+    q->report = c->d_pv_report;
+    return true;
+}
+
 // An overlapped launch into copy `set` on render stream `lane` comes behind what it depends on.  pre: the launch's pre-pass
-// (plan_prepass) goes in here; *served: it was queued and the launch is to be told.
-static int order_overlapped_launch(vrt_ctx* c, int set, int lane, const Prepass& pre, const RenderVariant& v, const FrameParams& fp, const SceneData& sc, bool* served) {
+// (plan_prepass) goes in here; *served: it was queued and the launch is to be told.  out, g: what the launch writes and its samples;
+// *queue: with plan_primary, the launch's primary vertices are queued here too (k_primary_vertex) and the launch is to take its
+// paths from queue->.
+static int order_overlapped_launch(vrt_ctx* c, int set, int lane, const Prepass& pre, const RenderVariant& v, const FrameParams& fp, const SceneData& sc, bool* served,
+                                   const PixelBuffers& out, int g, PrimaryQueue* queue, bool* queued) {
     hipStream_t rs = lane_stream(c, lane);
     *served = false;
+    *queued = false;
+    PrimaryRecord* prim_queued = nullptr;
     if (c->main_dirty) {  // uploads / prepare / sky kernels queued on the main stream come first (where it is a lane itself: in stream order)
         HIP_TRY(hipEventRecord(c->ev_main, c->stream));
         for (int s = 0; s < c->n_streams; s++) HIP_TRY(hipStreamWaitEvent(c->lanes[s].stream, c->ev_main, 0));
         c->main_dirty = false;
     }
-    // The pre-pass reads the scene and writes the lane's record table, which the lane's previous launch has done with in stream
-    // order: it is queued HERE, behind the scene and in front of every wait that holds the launch itself back -- for the copy it
-    // writes, for the slots it takes -- so that it runs beside the launches of the other lanes.  It carries the number the launch
-    // takes below; from here on that number belongs to this launch whether or not it gets queued (plan_seq_abort).
-    if (pre.queue) {
-        if (PrimaryRecord* prim = lane_prim_cache(c, lane)) {
-            HIP_TRY(launch_primary_records(rs, c->cfg.grid_res, v, fp, sc, prim, plan_seq_reserve(c->launch_seq)));
-            *served = pre.tell;
-            c->prepass_queued++;
-            if (pre.tell) c->prepass_told++;
+    // What goes on the lane ahead of the launch, in plan_lane_ops' order (vrt_plan.h).  The pre-pass reads the scene and writes the
+    // lane's record table, which the lane's previous launch has done with in stream order: behind the scene and in front of every wait
+    // that holds the launch itself back -- for the copy it writes, for the slots it takes -- so that it runs beside the launches of the
+    // other lanes.  It carries the number the launch takes below; from here on that number belongs to this launch whether or not it
+    // gets queued (plan_seq_abort).  The primary vertices write the copy's colour planes and g-buffer: behind the pass that last read
+    // it, and in front of the gate -- the kernel takes no heavy slot; the queue's counts are zeroed in stream order, behind the lane's
+    // previous launch, which read them.
+    const PlaneSet& p = c->sets[set];
+    const unsigned target = plan_gate_target(c->launch_seq.next, c->prev_launch_full, c->grid_div, c->knobs.gate_extra, c->last_full_seq);
+    const bool gate = plan_gate_wait(target, c->lanes[lane].last_seq, c->drain_signal != nullptr, c->drain_signalled);
+    LaneOp ops[LANE_OP_COUNT];
+    const int n_ops = plan_lane_ops(pre, plan_primary(pre, c->knobs.primary), p.ev_t_valid, gate, ops);
+    for (int k = 0; k < n_ops; k++) {
+        switch (ops[k]) {
+        case LANE_OP_PREPASS:
+            if (PrimaryRecord* prim = lane_prim_cache(c, lane)) {
+                HIP_TRY(launch_primary_records(rs, c->cfg.grid_res, v, fp, sc, prim, plan_seq_reserve(c->launch_seq)));
+                *served = pre.tell;
+                prim_queued = prim;
+                c->prepass_queued++;
+                if (pre.tell) c->prepass_told++;
+            }
+            break;
+        case LANE_OP_WAIT_PASS:   // the pass that last read this copy
+            HIP_TRY(hipStreamWaitEvent(rs, c->sets[p.ev_t_of].ev_t, 0));
+            break;
+        case LANE_OP_ZERO_QUEUE: {   // (without a record table or memory for the queue the launch is queued as one without this stage)
+            const unsigned tiles = (unsigned)(((fp.W + 7) >> 3) * launch_tile_rows(fp));
+            if (prim_queued && tiles > 0u && lane_primary_queue(c, lane, v, tiles, g, queue)) {
+                HIP_TRY(hipMemsetAsync(queue->counts, 0, (size_t)VRT_PV_HEADS * VRT_PV_COUNT_STRIDE * sizeof(uint32_t), rs));
+                *queued = true;
+            }
+            break;
+        }
+        case LANE_OP_PRIMARY_VERTEX:
+            if (*queued) {
+                *queued = false;   // (until the kernel is queued: a failure here leaves a launch that is not told)
+                HIP_TRY(launch_primary_vertex(rs, c->cfg.grid_res, v, fp, sc, out, prim_queued, c->launch_seq.next, g, *queue));
+                *queued = true;
+                c->primary_queued++;
+            }
+            break;
+        case LANE_OP_WAIT_GATE:   // the dispatch gate (vrt_ctx::drain_signal): when the launch whose workgroup slots this one will take starts to drain
+            HIP_TRY(hipStreamWaitValue32(rs, c->drain_signal, target, hipStreamWaitValueGte, 0xFFFFFFFFu));
+            break;
+        default: break;
         }
     }
-    const PlaneSet& p = c->sets[set];
-    if (p.ev_t_valid) HIP_TRY(hipStreamWaitEvent(rs, c->sets[p.ev_t_of].ev_t, 0));  // the pass that last read this copy
-    // the dispatch gate (vrt_ctx::drain_signal): when the launch whose workgroup slots this one will take starts to drain
-    const unsigned target = plan_gate_target(c->launch_seq.next, c->prev_launch_full, c->grid_div, c->knobs.gate_extra, c->last_full_seq);
-    if (plan_gate_wait(target, c->lanes[lane].last_seq, c->drain_signal != nullptr, c->drain_signalled))
-        HIP_TRY(hipStreamWaitValue32(rs, c->drain_signal, target, hipStreamWaitValueGte, 0xFFFFFFFFu));
     return VRT_OK;
 }
 
@@ -525,10 +586,11 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
         bool lone = !overlapped;   // every workgroup slot
         if (overlapped && c->grid_div > 1) lone = pipeline_nearly_empty(c);
         const SceneData sc = make_scene_data(c);
-        bool prim_served = false;
+        bool prim_served = false, prim_queued = false;
+        PrimaryQueue pq{};
         if (overlapped) {
             const Prepass pre = plan_prepass(v, overlapped, lone, c->grid_div, c->knobs.prepass);
-            if (order_overlapped_launch(c, set, lane, pre, v, fp, sc, &prim_served) != VRT_OK) return VRT_E_DEVICE;
+            if (order_overlapped_launch(c, set, lane, pre, v, fp, sc, &prim_served, pixel_buffers_of(c, set, g, planes), g, &pq, &prim_queued) != VRT_OK) return VRT_E_DEVICE;
         } else if (c->last_set != 0) {
             if (restore_single_set(c) != VRT_OK) return VRT_E_DEVICE;
         }
@@ -553,7 +615,8 @@ static int accumulate_impl(vrt_ctx* c, int n_samples) {
         PrimaryRecord* const prim = v.share_primary ? lane_prim_cache(c, lane) : nullptr;
         const int all_blocks = v.dense12 ? c->render_blocks_d12 : c->render_blocks;
         const int blocks = lone ? all_blocks : plan_partial_blocks(all_blocks, c->grid_div);
-        if (pooled) HIP_TRY(launch_render_pool(rs, c->cfg.grid_res, v, blocks, fp, sc, out, c->d_work, seq, g, c->lanes[lane].pool_scratch, c->drain_signal, prim, prim_served));
+        if (pooled && prim_queued) HIP_TRY(launch_render_pool_queued(rs, c->cfg.grid_res, v, blocks, fp, sc, out, c->d_work, seq, g, c->lanes[lane].pool_scratch, c->drain_signal, prim, pq));
+        else if (pooled) HIP_TRY(launch_render_pool(rs, c->cfg.grid_res, v, blocks, fp, sc, out, c->d_work, seq, g, c->lanes[lane].pool_scratch, c->drain_signal, prim, prim_served));
         else HIP_TRY(launch_render(rs, c->cfg.grid_res, restir, v.instr, c->render_blocks, fp, sc, out, c->d_work, seq, g, c->knobs.chunk));
         c->drain_signalled = pooled && c->drain_signal != nullptr;
         c->prev_launch_full = blocks == all_blocks;

@@ -16,6 +16,9 @@
 #endif                    // and the eight-deep one (not measured with K > 1) accumulate every launch in a pass of its own
 #define VRT_MAX_DEFER 8   // largest K a switch may ask for: VRT_MAX_GROUP of vrt_temporal.h (vrt_ctx.h asserts that they agree)
 #define VRT_LEAN_STREAMS 2
+#ifndef VRT_PRIMARY_DEFAULT
+#define VRT_PRIMARY_DEFAULT 1   // Knobs::primary of the shipped library
+#endif
 
 // Environment switches, read ONCE when a context is created (never on the launch path).
 // The shipped library knows four: VRT_RENDER=pool|fused (which of the two schedules of the same per-path code renders),
@@ -26,7 +29,7 @@
 // loaded by tests/test_gpu_pipeline.py and the A/B runs of tools/) adds the development switches: the fault-injection hook
 // VRT_TEST_FAIL_LAUNCH and the A/B switches VRT_CULL, VRT_DENSE, VRT_DEEP_ITEMS, VRT_DEEPER_ITEMS, VRT_STREAMS, VRT_GRID_DIV,
 // VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER, VRT_PASS_STREAM, VRT_CTX_LANE, VRT_CAST_VIEW,
-// VRT_PREPASS.
+// VRT_PREPASS, VRT_PRIMARY, VRT_PRIMARY_CAP.
 struct Knobs {
     int render = -1;               // -1: the library's choice, 0: fused, 1: pool; -2: a value VRT_RENDER does not know
     bool overlap = true;
@@ -42,6 +45,8 @@ struct Knobs {
     int max_fused = VRT_MAX_FUSED, full_below = 2, chunk = 0, fail_launch = -1, gate_extra = 0, time_every = 0;
     int defer4 = VRT_DEFER_4DEEP, defer8 = 1;   // render launches whose accumulation runs as one pass, per pipeline depth (VRT_DEFER: both)
     int cast_view = -1;            // -1: by the batch size (plan_cast_staged), 0: k_cast_rays on the pyramid in global memory, 1: coarse levels staged in LDS
+    int primary = VRT_PRIMARY_DEFAULT;   // plan_primary: 0: no launch has its primary vertices shaded ahead of it, 1: those the rule names
+    long long primary_cap = 0;     // plan_primary_caps: continuation records of a launch's queue, all heads together (0: the rule's)
     int prepass = 1;               // plan_prepass: 0: no launch has a pre-pass, 1: those the rule names, 2: the same, queued, but the launch is not told (A/B: what co-residency costs)
 };
 static Knobs read_knobs() {
@@ -69,6 +74,8 @@ static Knobs read_knobs() {
     if (const char* e = getenv("VRT_FULL_BELOW")) { const int v = atoi(e); if (v >= 0 && v <= 3) k.full_below = v; }   // 0: no overlapped launch takes every slot, whatever the host's timing (tests)
     if (const char* e = getenv("VRT_DEFER")) { const int v = atoi(e); if (v >= 0 && v <= VRT_MAX_DEFER) k.defer4 = k.defer8 = v < 1 ? 1 : v; }   // 0, 1: a pass per launch
     if (const char* e = getenv("VRT_CHUNK")) { const int v = atoi(e); if (v >= 64 && v <= 4096) k.chunk = v / 64 * 64; }
+    if (const char* e = getenv("VRT_PRIMARY")) { const int v = atoi(e); if (v == 0 || v == 1) k.primary = v; }
+    if (const char* e = getenv("VRT_PRIMARY_CAP")) { const long long v = atoll(e); if (v >= 8) k.primary_cap = v; }
     if (const char* e = getenv("VRT_PREPASS")) { const int v = atoi(e); if (v >= 0 && v <= 2) k.prepass = v; }
     if (const char* e = getenv("VRT_CAST_VIEW")) k.cast_view = strcmp(e, "staged") == 0 ? 1 : strcmp(e, "global") == 0 ? 0 : -1;
 #endif
@@ -122,6 +129,42 @@ static inline Prepass plan_prepass(const RenderVariant& v, bool overlapped, bool
     p.queue = knob != 0 && overlapped && !lone && grid_div == 2 && v.pooled && v.share_primary && !v.instr && !v.dense12 && !v.restir;
     p.tell = p.queue && knob != 2;
     return p;
+}
+// Whether a launch's primary vertices are shaded ahead of it (k_primary_vertex, vrt_kernels.hip; vrt_primary.h) and the launch resumes
+// its paths from the queue that kernel leaves (the QUEUED instantiation): exactly the launches that have a pre-pass and are told of it
+// -- the kernel reads the pre-pass's records.  (It does not share the pre-pass's wave slot: at 160 registers it fits beside one pooled
+// wave of a SIMD, not two, and runs where a draining launch has freed slots.)  knob: Knobs::primary.
+static inline bool plan_primary(const Prepass& pre, int knob) { return knob != 0 && pre.queue && pre.tell; }
+// The queue of such a launch over `tiles` 8x8 tiles of n_samples samples, per work head (8 of them; tile t appends to head t % 8).
+// left_cap: every item of the head's tiles -- a leftover can always be written, so no path is dropped.  cap: continuation records; a
+// path that finds them used up becomes a leftover and is begun by the pool from depth 0, the same bits.  Three eighths of the
+// items: of the path-samples a tenth (sun-lit) to a quarter (S1) go on in the small frames of tests/test_gpu_primary_vertex.py and
+// 20.7 % on the 1080p headline (the development build's report over a bench run) -- a quarter would leave a head
+// with a few more continuing paths than the average nothing to spare; the overflow route is exact but costs the pool a depth-0 turn.
+// 64 bytes a record under a black sun, 96 under an emitting one: a 1080p launch of four samples holds 3.1 M records -- 199 MB
+// (299 MB) a lane -- and 33 MB of leftover words.  A queue that has to grow (a later launch with
+// more tiles or samples) is reallocated behind a host wait for the lane's stream: once, on the launch path.
+// knob_cap: Knobs::primary_cap, records of all heads together (tests force 64).
+struct PrimaryCaps { unsigned cap, left_cap; };
+static inline PrimaryCaps plan_primary_caps(unsigned tiles, int n_samples, long long knob_cap) {
+    PrimaryCaps c;
+    c.left_cap = ((tiles + 7u) / 8u) * 64u * (unsigned)n_samples;
+    c.cap = knob_cap > 0 ? (unsigned)(knob_cap / 8) : (unsigned)((3ull * c.left_cap + 7ull) / 8ull);
+    if (c.cap > c.left_cap) c.cap = c.left_cap;
+    return c;
+}
+// What is queued on an overlapped launch's lane ahead of the launch itself, in order.  The pre-pass first (it waits for nothing but the
+// lane's previous launch); the wait for the pass that last read the copy the launch writes; then, with plan_primary, the zeroing of
+// the queue's counts and k_primary_vertex, which writes that copy and is no pooled launch, so not the gate's business; the dispatch gate last, right in front of
+// the pooled launch.  wait_pass: such a pass is on record; wait_gate: plan_gate_wait.
+enum LaneOp { LANE_OP_PREPASS = 0, LANE_OP_WAIT_PASS, LANE_OP_ZERO_QUEUE, LANE_OP_PRIMARY_VERTEX, LANE_OP_WAIT_GATE, LANE_OP_COUNT };
+static inline int plan_lane_ops(const Prepass& pre, bool primary, bool wait_pass, bool wait_gate, LaneOp* ops) {
+    int n = 0;
+    if (pre.queue) ops[n++] = LANE_OP_PREPASS;
+    if (wait_pass) ops[n++] = LANE_OP_WAIT_PASS;
+    if (primary && pre.queue && pre.tell) { ops[n++] = LANE_OP_ZERO_QUEUE; ops[n++] = LANE_OP_PRIMARY_VERTEX; }
+    if (wait_gate) ops[n++] = LANE_OP_WAIT_GATE;
+    return n;
 }
 // The launch numbers.  A launch takes the next number when it is queued (plan_seq_take); its records carry the number as their tag
 // (+ 1), and a tag must never come to mean two launches -- a launch with another camera would take the first one's records for its
