@@ -97,4 +97,10 @@ for scene in sys.argv[1:] or ["s1", "sunlit", "dense"]:
     if sum(sub) and sum(cyc.values()):
         print("  BEGIN, of all pool wave-cycles: " + "  ".join(f"{nm} {100 * sub[k] / tot:.1f}%" for k, nm in
               enumerate(("work reservation (atomic round trip)", "record read + check", "set-up from a record", "set-up with a ray"))))
+    pv = [int(out[56 + k]) for k in range(8)]   # k_primary_vertex's region clocks (VRT_PV_CLOCK, csrc/vrt_trace.h); its launches render every path-sample counted in n
+    if sum(pv):
+        print(f"  k_primary_vertex wave-cycles per path-sample: {sum(pv) / n:.1f}" + (f"   (pool: {sum(cyc.values()) / n:.1f})" if sum(cyc.values()) else ""))
+        print("  k_primary_vertex wave-cycles by region, share (per path-sample): " + "  ".join(f"{nm} {100 * pv[k] / sum(pv):.1f}% ({pv[k] / n:.2f})" for k, nm in
+              ((0, "record load + check"), (1, "hit rebuild + g-buffer"), (2, "surface set-up"), (7, "path begin"), (3, "cone draws + sample_bsdf (+ light sample)"),
+               (4, "bounce ray floor_probe/walk_prepare"), (5, "escape shade + path_finish"), (6, "queue append"))))
     s.close()

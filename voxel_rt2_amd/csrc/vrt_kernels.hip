@@ -798,17 +798,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(VRT_PRIMARY_HALF
 // The primary vertex of every path of a launch, AHEAD of it (vrt_primary.h): one wave a workgroup, one workgroup an 8x8 tile, a lane
 // a pixel, gated as k_primary_records is, whose records it reads; no LDS, the pyramid (walked by the emitting sun's shadow rays only)
 // and the material table through global memory.  NOT the pre-pass's register budget: at 96 registers it spills 52-97 of them and
-// measures slower than at 160, where it no longer fits beside two pooled waves of a SIMD, only beside one (below).  The g-buffer is
-// written once a pixel; paths that go on are compacted per sample with a ballot and one atomic a wave onto the queue of head (tile % 8).
+// measures slower than at 160, where it no longer fits beside two pooled waves of a SIMD, only beside one (below).  The g-buffer and
+// the shading point of the primary vertex (primary_vertex_surf: material row, mat_derive, basis) are made once a pixel, ahead of the
+// sample loop; paths that go on are compacted per sample with a ballot and one atomic a wave onto the queue of head (tile % 8).
+// Two budgets, so two kernels around one body (the register attribute takes a literal).  What decides is how many of its waves fit
+// beside ONE pooled wave of a SIMD (208 registers: 304 are left), the slots a draining launch frees: two of up to 152 registers, one of
+// 160 or 168.  Under a black sun the kernel took 139 registers before the shading point was shared -- allocated as 144, two such waves --
+// and asks for 165 with it live across the sample loop; capped at 144 it spills ONE register and keeps the second wave.  Measured in one
+// session, headline: 144: +2.7 % over the parent, 152: +2.5 %, 160: +2.1 %, 168: -0.6 %.  Under an emitting sun it took
+// 157 already (one wave beside a pooled one); at 168 no instantiation spills, at 160 eleven registers do, at 144 fourteen, and the
+// sun-lit scene orders them 168 > 160 > 152 = 144, all above the parent.
 #ifndef VRT_PRIMARY_VERTEX_HALF_VGPRS
-#define VRT_PRIMARY_VERTEX_HALF_VGPRS 80   // 160 registers: no spills under a black sun, 5-11 under an emitting one; three waves a SIMD where no pooled wave is, one beside
-                                           // a single pooled wave -- the slots a draining launch frees.  Measured against 96 (beside two pooled waves, 52-97 spills), 128 and 256: DESIGN.md section 7
+#define VRT_PRIMARY_VERTEX_HALF_VGPRS 72       // black sun: 144 registers
 #endif
-#if 2 * VRT_PRIMARY_VERTEX_HALF_VGPRS + 2 * VRT_POOL_HALF_VGPRS > 512
+#ifndef VRT_PRIMARY_VERTEX_SUN_HALF_VGPRS
+#define VRT_PRIMARY_VERTEX_SUN_HALF_VGPRS 84   // emitting sun: 168 registers (allocated like 160: three waves a SIMD where no pooled wave is)
+#endif
+#if 2 * VRT_PRIMARY_VERTEX_HALF_VGPRS + 2 * VRT_POOL_HALF_VGPRS > 512 || 2 * VRT_PRIMARY_VERTEX_SUN_HALF_VGPRS + 2 * VRT_POOL_HALF_VGPRS > 512
 #error "k_primary_vertex must fit beside one pooled wave of a SIMD at least"   // (or it only runs where the chip is empty)
 #endif
+#ifndef VRT_PRIMARY_SHARED_SURF
+#define VRT_PRIMARY_SHARED_SURF 1   // 0 (A/B and region-clock variants only): the shading point per sample inside path_shade, as before it was shared
+#endif
 template <int G, bool BLACK_SUN, bool CULL>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(VRT_PRIMARY_VERTEX_HALF_VGPRS))) void k_primary_vertex(FrameParams fp, SceneData sc, PixelBuffers out, const PrimaryRecord* prim_cache, uint32_t tag, int n_samples, PrimaryQueue pq) {
+static __device__ __forceinline__ void primary_vertex_body(const FrameParams& fp, const SceneData& sc, const PixelBuffers& out, const PrimaryRecord* prim_cache, uint32_t tag, int n_samples, const PrimaryQueue& pq) {
     const int tiles_x = (fp.W + 7) >> 3;
     const unsigned tile = blockIdx.x, in = threadIdx.x;
     const int u = (int)(tile % (unsigned)tiles_x) * 8 + (int)(in & 7u);
@@ -826,19 +839,31 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(VRT_PRIMARY_VERT
     Hit h;
     hit_init(h);
     int state = SLOT_ESCAPE;
+    constexpr bool SHARED_SURF = VRT_PRIMARY_SHARED_SURF != 0;
+    Surf surf;   // the pixel's shading point, built once ahead of the sample loop (primary_vertex_surf)
+#if defined(VRT_DIAG_REGIONS)
+    __shared__ unsigned long long pv_clock[PVR_COUNT + 1];   // the wave's region clocks (VRT_PV_CLOCK, vrt_trace.h)
+    if (in <= (unsigned)PVR_COUNT) pv_clock[in] = 0ULL;
+    ts.pv = pv_clock;
+    ts.pv[PVR_COUNT] = __builtin_readcyclecounter();
+#endif
     if (live) {
         rec = primary_record_load(&prim_cache[(v - fp.row0) * fp.W + u]);
         known = primary_record_valid(rec, tag);
-        if (known) {
-            state = primary_vertex_hit<G>(fp, sc, rec, h, ts);
-            primary_vertex_gbuffer(fp, out, u, v, rec, h);
-        }
+    }
+    VRT_PV_CLOCK(ts, PVR_RECORD);
+    if (known) {
+        state = primary_vertex_hit<G>(fp, sc, rec, h, ts);
+        primary_vertex_gbuffer(fp, out, u, v, rec, h);
+        VRT_PV_CLOCK(ts, PVR_HIT);
+        if constexpr (SHARED_SURF) (void)primary_vertex_surf<GlobalPyramid<G>>(sc, rec, h, state, surf);
+        VRT_PV_CLOCK(ts, PVR_SURF);
     }
     unsigned n_done = 0u, n_on = 0u;
     for (int sample = 0; sample < n_samples; sample++) {
         Path<false> p;
         bool on = false;
-        if (known) on = primary_vertex_sample<G, BLACK_SUN, CULL>(fp, sc, P, out, u, v, sample, rec, h, state, p, ts);
+        if (known) on = primary_vertex_sample<G, BLACK_SUN, CULL, SHARED_SURF>(fp, sc, P, out, u, v, sample, rec, h, state, p, ts, &surf);
         // continuations: one atomic a wave on the head's record count; a record that does not fit is a leftover
         const unsigned long long m_on = __ballot(on);
         bool left = live && !known;
@@ -859,12 +884,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(VRT_PRIMARY_VERT
             if (left && at < pq.left_cap) pq.leftovers[(size_t)head * pq.left_cap + at] = primary_leftover_item(u, v, sample);
         }
         if (known && !left) { if (on) n_on++; else n_done++; }
+        VRT_PV_CLOCK(ts, PVR_APPEND);
     }
+#if defined(VRT_DIAG_REGIONS)
+    if (in < (unsigned)PVR_COUNT) atomicAdd(&g_vrt_region[56 + in], pv_clock[in]);   // [56..63]: tools/diag_regions.py
+    static_assert(56 + PVR_COUNT <= 64, "the region counters' last eight words");
+#endif
     if (pq.report) {   // development builds: the counts the tests read
         unsigned long long a = n_done, b = n_on;
         for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
         if (in == 0u) { atomicAdd(&pq.report[0], a); atomicAdd(&pq.report[1], b); }
     }
+}
+template <int G, bool CULL>   // black sun
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(VRT_PRIMARY_VERTEX_HALF_VGPRS))) void k_primary_vertex(FrameParams fp, SceneData sc, PixelBuffers out, const PrimaryRecord* prim_cache, uint32_t tag, int n_samples, PrimaryQueue pq) {
+    primary_vertex_body<G, true, CULL>(fp, sc, out, prim_cache, tag, n_samples, pq);
+}
+template <int G, bool CULL>   // emitting sun
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(VRT_PRIMARY_VERTEX_SUN_HALF_VGPRS))) void k_primary_vertex_sun(FrameParams fp, SceneData sc, PixelBuffers out, const PrimaryRecord* prim_cache, uint32_t tag, int n_samples, PrimaryQueue pq) {
+    primary_vertex_body<G, false, CULL>(fp, sc, out, prim_cache, tag, n_samples, pq);
 }
 // QUEUED: the instantiation for launches behind k_primary_vertex (plan_primary, vrt_plan.h): BEGIN resumes the queue's paths at depth 1
 // and takes its leftovers as depth-0 items.  A kernel of its own, so that every other launch runs the machine code it ran before.
@@ -1694,7 +1732,8 @@ hipError_t launch_primary_vertex(hipStream_t st, int grid_res, const RenderVaria
                                  const PrimaryRecord* prim_cache, unsigned launch_seq, int n_samples, const PrimaryQueue& pq) {
     const int tiles = ((fp.W + 7) >> 3) * launch_tile_rows(fp);
     if (tiles <= 0) return hipSuccess;
-    VRT_BY_GRID(grid_res, VRT_BY_2(v.black_sun, v.cull, hipLaunchKernelGGL((k_primary_vertex<G, A, B>), dim3(tiles), dim3(64), 0, st, fp, sc, out, prim_cache, launch_seq + 1u, n_samples, pq)));
+    if (v.black_sun) VRT_BY_GRID(grid_res, VRT_BY_2(v.cull, false, hipLaunchKernelGGL((k_primary_vertex<G, A>), dim3(tiles), dim3(64), 0, st, fp, sc, out, prim_cache, launch_seq + 1u, n_samples, pq)));
+    else VRT_BY_GRID(grid_res, VRT_BY_2(v.cull, false, hipLaunchKernelGGL((k_primary_vertex_sun<G, A>), dim3(tiles), dim3(64), 0, st, fp, sc, out, prim_cache, launch_seq + 1u, n_samples, pq)));
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -225,6 +225,34 @@ VRT_DEV void path_begin(const FrameParams& fp, Path<RESTIR>& p, int u, int v, in
 // (vrt_pool.h) drop the other kind's code.
 enum { HIT_ANY = 0, HIT_SOMETHING = 1, HIT_NOTHING = 2 };
 
+// The shading point `s` of a surface hit `h` of a ray along `d` (the view vector is -d), surf_init() as path_shade() evaluates it: the
+// material-only terms from the staged row where there is one (PyrT::mats_packed), the basis in its face-normal form.  A function of
+// (scene, hit, direction) alone, so a caller whose vertices share all three (the fused samples of a pixel at depth 0:
+// vrt_primary.h) builds it once through path_surf() and hands it to path_shade<..., SURF_GIVEN>.
+// A macro under the function, and path_shade() expands the macro itself: as a call of path_surf() the block is optimised on its own
+// before it is inlined (the divisions of mat_derive() sink below the basis' branch), and every kernel that derives the material terms
+// inline -- k_render, k_trace_radiance, the two gather kernels -- came out as other machine code than before there was a function
+// (tools/asm_diff.py; the pooled kernels, which load packed rows, did not care).
+#define VRT_PATH_SURF(PyrT, sc, h, d, s)                                  \
+    {                                                                     \
+        Material m;                                                       \
+        MatDerived mx;                                                    \
+        if constexpr (mats_packed_of<PyrT>::value) {                      \
+            m = load_material_packed((sc).mats, (h).mat_id, (h).albedo, mx); \
+        } else {                                                          \
+            m = load_material((sc).mats, (h).mat_id);                     \
+            m.base = (h).albedo;                                          \
+            mx = mat_derive(m);                                           \
+        }                                                                 \
+        f3 tx, ty;                                                        \
+        ortho_basis_axis_normal((h).normal, tx, ty);                      \
+        surf_set(s, m, mx, (h).normal, -(d), tx, ty);                     \
+    }
+template <class PyrT>
+VRT_DEV void path_surf(const SceneData& sc, const Hit& h, f3 d, Surf& s) {
+    VRT_PATH_SURF(PyrT, sc, h, d, s)
+}
+
 // One iteration of pathtracer.py:396-525 after its closest-hit query `h`.  Returns true when the path is over.
 // BLACK_SUN: the caller knows (and the launch parameters say) that the sun does not emit -- scene.py's default, which
 // example1.py never changes.  Then nothing can use the light sample except case (b) below, and the compiler drops
@@ -233,9 +261,11 @@ enum { HIT_ANY = 0, HIT_SOMETHING = 1, HIT_NOTHING = 2 };
 // STORE = false: the primary vertex's g-buffer values are not stored and `out` is not read (vrt_radiance.h: a query writes no pixel).
 // DISC0 = false: a path whose FIRST segment escapes does not see the sun's disc (hit_sun = 0 at depth 0; vrt_sensor.h: the caller has
 // counted the sun at the path's origin already).  Later segments see it as ever.
-template <bool RESTIR, int KIND, bool BLACK_SUN = false, bool STORE = true, bool DISC0 = true, class PyrT>
+// SURF_GIVEN: `given` is path_surf() of this vertex, built by the caller (who knows it is a surface: the test below); otherwise it is
+// built here and `given` is not read.  A compile-time switch: chosen at run time, the shading point goes through scratch.
+template <bool RESTIR, int KIND, bool BLACK_SUN = false, bool STORE = true, bool DISC0 = true, bool SURF_GIVEN = false, class PyrT>
 VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& P, const PixelBuffers& out, int local_idx,
-                        Path<RESTIR>& p, const Hit& h, TraceStats& ts) {
+                        Path<RESTIR>& p, const Hit& h, TraceStats& ts, const Surf* given = nullptr) {
     const int depth = p.depth;
     const f3 hit_pos = p.pos + h.closest * p.d;
     const bool surface = (KIND != HIT_NOTHING) && (!h.hit_light) && (h.closest < DM_INF);
@@ -269,22 +299,10 @@ VRT_DEV bool path_shade(const FrameParams& fp, const SceneData& sc, const PyrT& 
     if (surface) {
         VRT_REGION(2);
         p.pos = hit_pos + h.normal * VRT_EPS;
-        // surf_init(): the material-only terms from the staged row where there is one, the basis in its face-normal form
-        Surf s;
-        {
-            Material m;
-            MatDerived mx;
-            if constexpr (mats_packed_of<PyrT>::value) {
-                m = load_material_packed(sc.mats, h.mat_id, h.albedo, mx);
-            } else {
-                m = load_material(sc.mats, h.mat_id);
-                m.base = h.albedo;
-                mx = mat_derive(m);
-            }
-            f3 tx, ty;
-            ortho_basis_axis_normal(h.normal, tx, ty);
-            surf_set(s, m, mx, h.normal, -p.d, tx, ty);
-        }
+        Surf here;
+        if constexpr (!SURF_GIVEN) VRT_PATH_SURF(PyrT, sc, h, p.d, here)
+        const Surf& s = SURF_GIVEN ? *given : here;
+        VRT_PV_CLOCK(ts, PVR_SURF);
 
         // Sun sample (pathtracer.py:435-476) and next direction (478-497).  The random draws keep the reference's
         // order -- two for the cone, then the BSDF sampler's -- but the shadow ray, which draws nothing, is traced

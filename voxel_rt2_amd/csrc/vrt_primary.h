@@ -5,7 +5,8 @@
 // depth 0, floor_probe and walk_prepare of the bounce ray.  k_primary_vertex (vrt_kernels.hip) does that with one lane a pixel of an
 // 8x8 tile -- no pool, no scheduler, every lane at the same depth -- and finishes the paths that end there: sky pixels, emissive
 // surfaces, max_depth 1, and bounce rays that have nothing to walk and miss the floor (their escape is shaded with the state still in
-// registers).  A path that goes on is appended to a queue in device memory as a PrimaryCont record, from which the pooled launch's
+// registers).  What the fused samples of a pixel share is made once, ahead of the sample loop: the hit, the g-buffer and the shading
+// point of a surface hit (primary_vertex_surf).  A path that goes on is appended to a queue in device memory as a PrimaryCont record, from which the pooled launch's
 // BEGIN (the QUEUED instantiation of render_pool_body) resumes it at depth 1; BEGIN sets the bounce ray up again (pool_launch_ray:
 // the same functions on the same bits).  Every function called here is the one the pool calls; results do not depend on who
 // evaluates them.
@@ -73,28 +74,44 @@ VRT_DEV void primary_vertex_gbuffer(const FrameParams& fp, const PixelBuffers& o
     stream_store(&out.gb_depth[local_idx], view_to_screen(xform(fp.view, ppos, 1.0f), fp.proj).z);
 }
 
+// The shading point of the pixel's primary vertex, once for all its samples: camera, jitter and scene are the launch's, so the hit, the
+// view vector (minus the record's direction, which is every sample's p.d at depth 0) and with them path_surf() are the same for every
+// fused sample.  Built only where path_shade treats the hit as a surface (its own test); returns whether it was.
+template <class PyrT>
+VRT_DEV bool primary_vertex_surf(const SceneData& sc, const PrimaryRecord& rec, const Hit& h, int state, Surf& s) {
+    if (!(state == SLOT_SHADE && !h.hit_light && h.closest < DM_INF)) return false;
+    path_surf<PyrT>(sc, h, mk3(dm_u2f(rec.dx), dm_u2f(rec.dy), dm_u2f(rec.dz)), s);
+    return true;
+}
+
 // Sample `sample` of pixel (u, v) from its camera ray's record and hit (primary_vertex_hit) up to where the pool has to take over.
 // True: the path goes on -- `p` is what SHADE would have stored at depth 0 (path_store_hot, path_store_cold).  False: it is finished
-// and its pixel values are written.
-template <int G, bool BLACK_SUN, bool CULL, class PyrT>
+// and its pixel values are written.  SHARED_SURF: `surf` is the pixel's primary_vertex_surf (read only where that returned true);
+// otherwise path_shade builds the shading point for this sample alone.
+template <int G, bool BLACK_SUN, bool CULL, bool SHARED_SURF = false, class PyrT>
 VRT_DEV bool primary_vertex_sample(const FrameParams& fp, const SceneData& sc, const PyrT& P, const PixelBuffers& out, int u, int v, int sample,
-                                   const PrimaryRecord& rec, const Hit& h, int state, Path<false>& p, TraceStats& ts) {
+                                   const PrimaryRecord& rec, const Hit& h, int state, Path<false>& p, TraceStats& ts, const Surf* surf = nullptr) {
     path_begin_along(fp, p, u, v, sample, mk3(dm_u2f(rec.dx), dm_u2f(rec.dy), dm_u2f(rec.dz)));
     const int local_idx = (v - fp.row0) * fp.W + u;
+    VRT_PV_CLOCK(ts, PVR_BEGIN);
     bool done;   // (STORE = false: the g-buffer is the pixel's, primary_vertex_gbuffer)
-    if (state == SLOT_SHADE) done = path_shade<false, HIT_SOMETHING, BLACK_SUN, false>(fp, sc, P, out, local_idx, p, h, ts);
-    else done = path_shade<false, HIT_NOTHING, false, false>(fp, sc, P, out, local_idx, p, h, ts);
+    if (state == SLOT_SHADE) {
+        done = path_shade<false, HIT_SOMETHING, BLACK_SUN, false, true, SHARED_SURF>(fp, sc, P, out, local_idx, p, h, ts, surf);
+        VRT_PV_CLOCK(ts, PVR_SAMPLE);   // (from path_shade's own point behind the shading point: draws, sample_bsdf, the light sample; all of an emissive hit)
+    } else done = path_shade<false, HIT_NOTHING, false, false>(fp, sc, P, out, local_idx, p, h, ts);
     if (!done) {
         // pool_launch_ray's test of the bounce ray: one that has nothing to walk and misses the floor is ESCAPE's at once
         const float ft = floor_probe(fp, p.pos, p.d);
         RayWalk w;
         const bool alive = walk_prepare<G, CULL>(world_to_voxel<G>(p.pos), p.d, w, sc.cull);
+        VRT_PV_CLOCK(ts, PVR_BOUNCE_RAY);
         if (alive || slot_state_after_walk<G>(w.t, ft) != SLOT_ESCAPE) return true;
         Hit none;
         hit_init(none);
         (void)path_shade<false, HIT_NOTHING, false>(fp, sc, P, out, local_idx, p, none, ts);
     }
     path_finish<false>(fp, sc, out, local_idx, p, ts);
+    VRT_PV_CLOCK(ts, PVR_FINISH);   // (the escape's shade and path_finish)
     return false;
 }
 

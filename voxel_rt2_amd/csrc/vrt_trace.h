@@ -504,8 +504,35 @@ VRT_DEV void walk_result(f3 d, float t, int ix, int iy, int iz, f3 hn, int iters
 
 struct Hit { float closest; f3 normal; f3 albedo; int hit_light; int mat_id; };
 
+#if defined(VRT_DIAG_REGIONS) && defined(__HIPCC__)
+// Diagnostic build only: k_primary_vertex's region clocks ride in the statistics record, the one thing every function it calls is handed.
+// `pv` is the wave's clock block in LDS (one wave a workgroup): [q] the cycles of region q, [PVR_COUNT] the previous clock point.  The
+// wave's cycles since that point go to region q.  In LDS, not in registers, because most clock points stand in divergent code: whichever
+// lanes are active there read the same words and write the same values, so the block follows the WAVE through both sides of a branch,
+// where a register copy would follow each lane past the side it did not take.  Null in every other kernel (a uniform branch).  The wait
+// in front of the clock charges a region with the loads and stores it issued (it perturbs what it measures: the shipped kernel overlaps
+// them with the next region).  Flushed once a wave (vrt_kernels.hip).
+enum { PVR_RECORD = 0, PVR_HIT, PVR_SURF, PVR_SAMPLE, PVR_BOUNCE_RAY, PVR_FINISH, PVR_APPEND, PVR_BEGIN, PVR_COUNT };
+struct TraceStats { unsigned rays, iters, queries, closest_hits, sky_lookups; volatile unsigned long long* pv; };
+VRT_DEV void stats_zero(TraceStats& s) { s.rays = s.iters = s.queries = s.closest_hits = s.sky_lookups = 0u; s.pv = nullptr; }
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VRT_PV_CLOCK(ts, q)                                                        \
+    do {                                                                           \
+        if ((ts).pv) {                                                             \
+            __asm__ volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");        \
+            const unsigned long long t_ = __builtin_readcyclecounter();            \
+            (ts).pv[q] = (ts).pv[q] + (t_ - (ts).pv[PVR_COUNT]);                   \
+            (ts).pv[PVR_COUNT] = t_;                                               \
+        }                                                                          \
+    } while (0)
+#else
+#define VRT_PV_CLOCK(ts, q) ((void)0)
+#endif
+#else
 struct TraceStats { unsigned rays, iters, queries, closest_hits, sky_lookups; };
 VRT_DEV void stats_zero(TraceStats& s) { s.rays = s.iters = s.queries = s.closest_hits = s.sky_lookups = 0u; }
+#define VRT_PV_CLOCK(ts, q) ((void)0)
+#endif
 
 VRT_DEV void hit_init(Hit& h) {
     h.closest = DM_INF;
