@@ -1,7 +1,13 @@
 // primary_vertex_emul.cpp -- TEST TOOLING: emul.cpp plus the render stage as a launch behind k_primary_vertex runs it, on the host.
 // What this covers and what it does not: launches of ONE sample (sample index 0; a call of n samples is n launches, as in emul.cpp), one
 // pixel at a time -- so the per-pixel functions, the record's packing and the queue's layout and consumption, but neither samples 1-3
-// of a fused launch nor the wave's ballot compaction and atomics, which only tests/test_gpu_primary_vertex.py exercises.
+// of a fused launch nor the wave's ballot compaction and atomics, which only tests/test_gpu_primary_vertex.py and
+// tests/test_gpu_primary_routes.py exercise.  Of the three routes a record that fails its check takes, the `spoil` option here covers
+// two in their per-pixel form, for sample 0: the pixel left to the pool as a depth-0 item (`left = live && !known`) and that item begun
+// by pool_begin (the `!known` arm of the QUEUED BEGIN, without its record store).  The device test (the development build's hook
+// VRT_TEST_SPOIL_RECORDS) covers all three on the wave's own code: the first for samples 0-3 through the ballot compaction and the atomics,
+// the second with sample 0's record store and the later samples that find it or do not, and the third, which this file has nothing of:
+// the `!known` arm for sample 0 of the SERVED instantiation (VRT_PRIMARY=0 behind a pre-pass).
 // Per tile and pixel, tiles in the kernel's order: the camera ray's record (primary_record_walk), the hit rebuilt once a pixel
 // (primary_vertex_hit), the sample through primary_vertex_sample; a path that goes on is packed into the queue of head (tile % 8)
 // (primary_cont_pack) or, where the head's records are used up, left as a depth-0 item.  Then the queue is consumed head by head

@@ -4,7 +4,9 @@ for the device alone (hipcc -S, the library's flags) from this tree and from REV
 folder), cuts both listings into functions and compares every function both have, instruction for instruction: comments dropped, block
 labels renumbered in order of appearance (a function's labels carry its number in the file, which moves when functions are added).
 
-    python tools/asm_diff.py [REV] [--rename REGEX=REPL ...] [name-substring ...]         REV: default HEAD~1
+    python tools/asm_diff.py [REV] [--rename REGEX=REPL ...] [-DNAME[=VALUE] ...] [name-substring ...]         REV: default HEAD~1
+
+-D...: both sides are compiled with these definitions too (-DVRT_DEV_KNOBS: the development build's kernels, libvrt_dev.so).
 
 --rename: a kernel of this tree whose name changed (a template parameter added with a default, say) is paired with REV's by rewriting this
 tree's demangled names with re.sub(REGEX, REPL, name) first, e.g. --rename '(k_render_pool<[^>]*), false>=\1>'.
@@ -25,8 +27,11 @@ from voxel_rt2_amd import build as B  # noqa: E402
 SRC = os.path.join("voxel_rt2_amd", "csrc", "vrt_kernels.hip")
 
 
+DEFINES = []
+
+
 def listing(root, out):
-    flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC")]
+    flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC")] + DEFINES
     subprocess.run([B._hipcc()] + flags + ["--offload-device-only", "-S", os.path.join(root, SRC), "-o", out], check=True, capture_output=True)
     return open(out).read()
 
@@ -64,6 +69,8 @@ def normal(body):
 
 def main():
     args = sys.argv[1:]
+    DEFINES[:] = [a for a in args if a.startswith("-D")]
+    args = [a for a in args if not a.startswith("-D")]
     renames = []
     while "--rename" in args:
         i = args.index("--rename")

@@ -214,7 +214,10 @@ void vrt_destroy(vrt_ctx* c) {
     if (getenv("VRT_PRIMARY_REPORT")) {
         unsigned long long r[2] = {0ULL, 0ULL};
         if (c->d_pv_report && hipMemcpy(r, c->d_pv_report, sizeof(r), hipMemcpyDeviceToHost) != hipSuccess) (void)hipGetLastError();
-        fprintf(stderr, "vrt: primary vertices served %u of %u render launches, paths finished %llu sent on %llu\n", c->primary_queued, c->passes_n[0], r[0], r[1]);
+        std::string grown;   // per lane that has a queue: how often it was reallocated for a larger launch (lane_primary_queue)
+        for (const Lane& l : c->lanes) if (l.pv_counts) grown += (grown.empty() ? "" : ",") + std::to_string(l.pv_regrown);
+        fprintf(stderr, "vrt: primary vertices served %u of %u render launches, paths finished %llu sent on %llu, queues regrown [%s]\n", c->primary_queued, c->passes_n[0], r[0], r[1],
+                grown.c_str());
     }
     if (getenv("VRT_PREPASS_REPORT")) fprintf(stderr, "vrt: pre-passes queued %u told %u of %u render launches\n", c->prepass_queued, c->prepass_told, c->passes_n[0]);
 #endif

@@ -84,6 +84,9 @@ struct Lane {
     uint32_t* pv_entries = nullptr;        // grown when a launch needs more): counter lines, continuation records, leftover items
     uint32_t* pv_leftovers = nullptr;
     size_t pv_entry_words = 0, pv_left_words = 0;   // words allocated
+#if defined(VRT_DEV_KNOBS)
+    unsigned pv_regrown = 0;               // times a queue this lane already had was reallocated for a larger launch (VRT_PRIMARY_REPORT)
+#endif
     unsigned last_seq = 0;                 // launch_seq + 1 of the last launch queued on this stream (0: none)
     int last_set = -1;                     // the copy that launch wrote: its ev_r is the lane's latest (-1: none since the streams were drained)
 };

@@ -129,6 +129,11 @@ hipError_t launch_primary_vertex(hipStream_t st, int grid_res, const RenderVaria
 hipError_t launch_render_pool_queued(hipStream_t st, int grid_res, const RenderVariant& v, int n_blocks, const FrameParams& fp, const SceneData& sc,
                                      const PixelBuffers& out, unsigned* work_counters, unsigned launch_seq, int n_samples, uint32_t* cold,
                                      uint32_t* drain_signal, PrimaryRecord* prim_cache, const PrimaryQueue& pq);
+#if defined(VRT_DEV_KNOBS)
+// Test hook (VRT_TEST_SPOIL_RECORDS, vrt_plan.h): behind launch_primary_records on the same stream, the records of the launch's live pixels
+// whose table index is launch_number mod n (mod n) fail their check from here on.  fp: the launch's own.
+hipError_t launch_spoil_primary_records(hipStream_t st, const FrameParams& fp, PrimaryRecord* prim_cache, unsigned n, unsigned launch_number);
+#endif
 hipError_t launch_mat_derived(hipStream_t st, const float* mats, float* mats_x /*[128][8]*/);  // after every material upload
 // spatial reuse over rows [r0, r1); first a per-pixel prepare pass over all rows the launch holds (fp.row0..fp.row1) into gb.geo / gb.src
 hipError_t launch_gris(hipStream_t st, int grid_res, bool instr, const FrameParams& fp, const SceneData& sc, const GrisBuffers& gb, int r0, int r1);

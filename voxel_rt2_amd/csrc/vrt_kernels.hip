@@ -1747,6 +1747,30 @@ hipError_t launch_render_pool_queued(hipStream_t st, int grid_res, const RenderV
     VRT_LAUNCH_CHECK();
     return hipSuccess;
 }
+#if defined(VRT_DEV_KNOBS)
+// Test hook of the development build (VRT_TEST_SPOIL_RECORDS=N, vrt_plan.h; tests/test_gpu_primary_routes.py): behind a launch's pre-pass,
+// ahead of everything that reads its records, the records of the live pixels -- k_primary_records' own gating -- whose index in the
+// table is launch_number mod N (mod N) have bit 0 of their check word inverted, so that they fail primary_record_valid under every tag
+// that the payload passed with.  What the design says of a missing, stale or torn record (vrt_pool.h) then has to hold: k_primary_vertex
+// makes every sample of such a pixel a leftover, and the pool begins it from depth 0, g-buffer and record included.  N = 1: every record.
+__global__ __launch_bounds__(64) void k_spoil_primary_records(FrameParams fp, PrimaryRecord* prim_cache, uint32_t n, uint32_t launch_number) {
+    const int tiles_x = (fp.W + 7) >> 3;
+    const unsigned tile = blockIdx.x, in = threadIdx.x;
+    const int u = (int)(tile % (unsigned)tiles_x) * 8 + (int)(in & 7u);
+    const int v = launch_tile_row(fp, (int)(tile / (unsigned)tiles_x)) + (int)(in >> 3);
+    if (!(u < fp.W && v < fp.row1 && launch_renders_row(fp, v) && !outside_render_area(fp, (float)u, (float)v))) return;
+    const uint32_t i = (uint32_t)((v - fp.row0) * fp.W + u);
+    if (i % n != launch_number % n) return;
+    prim_cache[i].w ^= 1u;
+}
+hipError_t launch_spoil_primary_records(hipStream_t st, const FrameParams& fp, PrimaryRecord* prim_cache, unsigned n, unsigned launch_number) {
+    const int tiles = ((fp.W + 7) >> 3) * launch_tile_rows(fp);
+    if (tiles <= 0 || n == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_spoil_primary_records, dim3(tiles), dim3(64), 0, st, fp, prim_cache, (uint32_t)n, (uint32_t)launch_number);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+#endif
 hipError_t launch_mat_derived(hipStream_t st, const float* mats, float* mats_x) {
     hipLaunchKernelGGL(k_mat_derived, dim3(1), dim3(128), 0, st, mats, mats_x);
     VRT_LAUNCH_CHECK();

@@ -359,6 +359,9 @@ static bool lane_primary_queue(vrt_ctx* c, int lane, const RenderVariant& v, uns
     if (need_e == 0 || need_l == 0) return false;
     if (need_e > l.pv_entry_words || need_l > l.pv_left_words || !l.pv_counts) {
         if (l.pv_entries || l.pv_leftovers) { if (hipStreamSynchronize(lane_stream(c, lane)) != hipSuccess) { (void)hipGetLastError(); return false; } }
+#if defined(VRT_DEV_KNOBS)
+        if (l.pv_entries || l.pv_leftovers) l.pv_regrown++;   // (the first allocation is not counted: tests/test_gpu_primary_routes.py)
+#endif
         (void)dfree(c, &l.pv_entries); (void)dfree(c, &l.pv_leftovers);
         l.pv_entry_words = l.pv_left_words = 0;
         bool ok = l.pv_counts || dalloc(c, &l.pv_counts, (size_t)VRT_PV_HEADS * VRT_PV_COUNT_STRIDE) == hipSuccess;
@@ -407,6 +410,11 @@ static int order_overlapped_launch(vrt_ctx* c, int set, int lane, const Prepass&
         case LANE_OP_PREPASS:
             if (PrimaryRecord* prim = lane_prim_cache(c, lane)) {
                 HIP_TRY(launch_primary_records(rs, c->cfg.grid_res, v, fp, sc, prim, plan_seq_reserve(c->launch_seq)));
+#if defined(VRT_DEV_KNOBS)
+                // test hook (tests/test_gpu_primary_routes.py): with VRT_TEST_SPOIL_RECORDS=N (read at vrt_create) every N-th record of the
+                // pre-pass fails its check, the pattern moving with the launch's number: behind the pre-pass, ahead of every reader
+                if (c->knobs.spoil_records > 0) HIP_TRY(launch_spoil_primary_records(rs, fp, prim, (unsigned)c->knobs.spoil_records, c->launch_seq.next));
+#endif
                 *served = pre.tell;
                 prim_queued = prim;
                 c->prepass_queued++;

@@ -29,7 +29,8 @@
 // loaded by tests/test_gpu_pipeline.py and the A/B runs of tools/) adds the development switches: the fault-injection hook
 // VRT_TEST_FAIL_LAUNCH and the A/B switches VRT_CULL, VRT_DENSE, VRT_DEEP_ITEMS, VRT_DEEPER_ITEMS, VRT_STREAMS, VRT_GRID_DIV,
 // VRT_DRAIN_GATE, VRT_FUSE, VRT_FUSE_RESTIR, VRT_OVERLAP_SINGLE, VRT_FULL_BELOW, VRT_CHUNK, VRT_DEFER, VRT_PASS_STREAM, VRT_CTX_LANE, VRT_CAST_VIEW,
-// VRT_PREPASS, VRT_PRIMARY, VRT_PRIMARY_CAP.
+// VRT_PREPASS, VRT_PRIMARY, VRT_PRIMARY_CAP; and a second test hook, VRT_TEST_SPOIL_RECORDS=N: every N-th camera-ray record of a pre-pass is made to
+// fail its check before anything reads it (k_spoil_primary_records, vrt_kernels.hip), so that the routes for missing and stale records run.
 struct Knobs {
     int render = -1;               // -1: the library's choice, 0: fused, 1: pool; -2: a value VRT_RENDER does not know
     bool overlap = true;
@@ -48,6 +49,9 @@ struct Knobs {
     int primary = VRT_PRIMARY_DEFAULT;   // plan_primary: 0: no launch has its primary vertices shaded ahead of it, 1: those the rule names
     long long primary_cap = 0;     // plan_primary_caps: continuation records of a launch's queue, all heads together (0: the rule's)
     int prepass = 1;               // plan_prepass: 0: no launch has a pre-pass, 1: those the rule names, 2: the same, queued, but the launch is not told (A/B: what co-residency costs)
+#if defined(VRT_DEV_KNOBS)
+    int spoil_records = 0;         // VRT_TEST_SPOIL_RECORDS: 0: off, N >= 1: the records whose index is launch number mod N (mod N) are spoiled behind every pre-pass
+#endif
 };
 static Knobs read_knobs() {
     Knobs k;
@@ -57,6 +61,7 @@ static Knobs read_knobs() {
     if (const char* e = getenv("GPU_MAX_HW_QUEUES")) k.hw_queues = atoi(e);
 #if defined(VRT_DEV_KNOBS)
     if (const char* e = getenv("VRT_TEST_FAIL_LAUNCH")) k.fail_launch = atoi(e);
+    if (const char* e = getenv("VRT_TEST_SPOIL_RECORDS")) { const int v = atoi(e); if (v >= 1) k.spoil_records = v; }
     if (const char* e = getenv("VRT_CULL")) k.cull = atoi(e) != 0;
     if (const char* e = getenv("VRT_DENSE")) k.dense = atoi(e) != 0;
     if (const char* e = getenv("VRT_DEEP_ITEMS")) k.deep_items = atoll(e);
