@@ -481,6 +481,60 @@ enum { VRT_LABEL_EMPTY = 1, VRT_LABEL_CONN_18 = 2, VRT_LABEL_CONN_26 = 4 };
 typedef struct vrt_label_result { int64_t cells; int32_t components; int32_t reserved; } vrt_label_result;            /* 16 bytes */
 int vrt_label_components(vrt_ctx* ctx, const int32_t lo[3], const int32_t hi[3], uint32_t flags,
                          void* labels /* int32[hx][hy][hz] */, vrt_label_result* result /* may be NULL */, int on_device);
+/* MOVE or COPY voxels of a PREPARED grid under an affine map, on the device: the piece found by vrt_label_components, carried as far as
+ * vrt_sweep_boxes allows, turned, mirrored or scaled -- without the voxels visiting the host.  Integers only: the result is a function of
+ * the stored voxels and the arguments alone, and no float exists anywhere in the library's part.
+ * THE MAP takes a DESTINATION cell to its SOURCE cell (nearest-neighbour resampling: every destination cell asks where it comes from).
+ * For a destination cell d, in int64: S_a = sum_b m[3a+b] * (2 d_b + 1) + t[a], a = 0..2, and the source cell is s_a = S_a >> 17, an
+ * ARITHMETIC shift: a floor, so cells are half-open.  (2 d + 1) is the cell's centre in half voxels; m is Q16 (65536 = 1.0); Q16 times half
+ * voxels is 2^-17 voxels, the unit of t.  VALID: |m[i]| <= 2^20 and |t[a]| <= 2^40.  THE BOUND: d < 256, so 2 d + 1 < 2^9, every product is
+ * below 2^29 in magnitude, a row's three below 2^31 and S below 2^31 + 2^40 < 2^41: no int64 operation can overflow, and |s| < 2^24 fits
+ * int32.  Singular, mirrored, scaling and shearing maps are all valid: the rule defines their result (the zero matrix draws every
+ * destination cell from the one cell t names).  A turn that is no multiple of 90 degrees does not keep the number of voxels -- a source
+ * cell may be drawn by no destination cell, or by two: that is what nearest-neighbour resampling does, and `written` and `erased` show it.
+ * BEFORE.  Everything is read from the stored voxels as they are when the call's work starts (a snapshot): source and destination boxes
+ * may overlap.
+ * SELECTED.  Source cell c is selected iff select == NULL or select[c] == select_value; `select` is int32 over the cells of the source
+ * box, C order, z fastest -- the labels of vrt_label_components over the same box plug in directly, select_value the component's root.
+ * A PIECE CELL is a selected cell of the source box whose material byte BEFORE is > 0 (signed): the solid rule of vrt_label_components.
+ * RECEIVES.  Cell d of the destination box receives iff s(d) lies in the source box and is a piece cell.  Only cells of the destination
+ * box can receive.
+ * VACATED.  With VRT_MOVE_ERASE_SOURCE every piece cell is vacated, whether or not any destination cell drew from it; without, none is.
+ * OCCUPIED.  Cell d is occupied iff its material byte BEFORE is > 0 and it is not vacated.
+ * FINAL GRID.  A receiving cell that is not both occupied and under VRT_MOVE_KEEP_SOLID takes the material and colour bytes of s(d) BEFORE
+ * and is WRITTEN.  Otherwise a vacated cell becomes material 0, colour 0, 0, 0.  Every other voxel of the grid keeps its bytes.
+ * RESULT (host memory, may be NULL).  written: the number of written cells; lo, hi: their tight box [lo, hi), all zero when there is
+ * none; blocked: the number of receiving cells that are occupied (whatever VRT_MOVE_KEEP_SOLID then does with them); erased: the number
+ * of vacated cells.
+ * VRT_MOVE_IF_FREE.  If blocked > 0 nothing changes at all: written = erased = 0 and the box is zero; blocked is still reported.  The
+ * device decides: there is no host round trip between the count and the edit.
+ * VRT_MOVE_DRY_RUN.  The grid and all derived state keep every byte; the record is what the call would have reported.
+ * STATE, ORDERING AND SYNCHRONISATION are vrt_update_voxels': everything vrt_prepare derives from the voxels is what a fresh upload of
+ * the final grid and a vrt_prepare would leave; histories and g-buffers are not touched (vrt_reset is the caller's); the call is queued
+ * on the context's stream, ordered against launches, queries and other edits, and forces the pending accumulation first.  It waits for
+ * the device exactly once, for the result and the culling record.  A dry run is ordered like vrt_fetch_voxels instead: it forces nothing.
+ * `select` with select_on_device = 0 is host memory, staged by the call; with 1 it is device memory, read in place.
+ * EMPTY BOXES.  An empty source box does nothing and zeroes the result.  An empty destination box with a non-empty source box receives
+ * nothing and still vacates under VRT_MOVE_ERASE_SOURCE: the rule is applied, not special-cased.
+ * Scratch: a buffer of the context's own (no other call's), grown on demand, kept by the context, freed by vrt_destroy: 4 bytes per cell
+ * of the source box for the snapshot, 4 bytes per cell of the LARGER of the two boxes for the box arrays the edits take, 4 bytes per
+ * cell of the source box for a staged selection, and under 1 KB of record and padding.  A whole 256^3 grid onto itself: 134 MB, 201 MB
+ * with a host selection.
+ * VRT_E_INVALID: NULL ctx or move; a source or destination box with lo > hi or outside the grid (vrt_update_voxels' rule); m or t out of
+ * bounds; unknown flag bits; reserved != 0; select_on_device not 0 or 1.  VRT_E_STATE: before vrt_prepare, or after a vrt_upload_voxels
+ * that no vrt_prepare has followed.  Every argument is checked on the host before anything is launched.  No counterpart in the reference. */
+enum { VRT_MOVE_ERASE_SOURCE = 1, VRT_MOVE_KEEP_SOLID = 2, VRT_MOVE_DRY_RUN = 4, VRT_MOVE_IF_FREE = 8 };
+typedef struct vrt_voxel_move {            /* 120 bytes */
+    int32_t src_lo[3], src_hi[3];          /* the source box [lo, hi), index space of vrt_upload_voxels */
+    int32_t dst_lo[3], dst_hi[3];          /* the destination box: the only cells that can receive */
+    int32_t m[9];                          /* row-major 3x3, Q16: maps DESTINATION to SOURCE */
+    int32_t select_value;
+    int64_t t[3];                          /* in 2^-17 voxels */
+    uint32_t flags, reserved;              /* reserved == 0 */
+} vrt_voxel_move;
+typedef struct vrt_move_result { int32_t lo[3], hi[3]; int64_t written, blocked, erased; } vrt_move_result;   /* 48 bytes */
+int vrt_move_voxels(vrt_ctx* ctx, const vrt_voxel_move* move, const void* select /* int32[src box], C order, or NULL */,
+                    int select_on_device, vrt_move_result* result /* host, may be NULL */);
 /* Renderer.accumulate_clouds / compute_atmosphere (pathtracer.py:325-329) */
 int vrt_sky_accumulate_clouds(vrt_ctx* ctx, int max_samples);
 int vrt_sky_compute_slice(vrt_ctx* ctx, int slice_idx, int max_slices);

@@ -18,6 +18,7 @@
 #   fillrate        tools/fill_rate.py: ms a call of vrt_fill_triangles next to vrt_voxelize_triangles of the same mesh and vrt_update_voxels of the same box -> fill_rate.jsonl under this run's output folder
 #   distancerate    tools/distance_rate.py: ms a call of vrt_distance_field (d2; d2 + nearest) next to vrt_fetch_voxels of the same box -> distance_rate.jsonl under this run's output folder
 #   labelrate       tools/label_rate.py: ms a call of vrt_label_components next to vrt_fetch_voxels and vrt_distance_field of the same box -> label_rate.jsonl under this run's output folder
+#   moverate        tools/move_rate.py: ms a call of vrt_move_voxels next to vrt_update_voxels of the same box and to fetch + torch.where + update -> move_rate.jsonl under this run's output folder
 #   labelkernels    tools/label_kernels.py: the three k_label_* kernels' durations per configuration, from a kernel trace -> label_kernels.jsonl under this run's output folder
 #   trace:CASE      rocprofv3 --kernel-trace --stats of bench_scenes.py CASE (CASE = bench: the bench command, config 2)
 #   pmc:CASE        tools/pmc.sh CASE + summary
@@ -82,6 +83,9 @@ for l in open('$O/scenes${arg:+_}${arg//,/_}.jsonl'):
     labelrate)
       timeout -k 10 300 python tools/label_rate.py --out $O/label_rate.jsonl > $O/label_rate.out 2> $O/label_rate.err || { rc=$?; tail -5 $O/label_rate.err; fail labelrate $rc; }
       tail -2 $O/label_rate.out ;;
+    moverate)
+      timeout -k 10 420 python tools/move_rate.py --out $O/move_rate.jsonl > $O/move_rate.out 2> $O/move_rate.err || { rc=$?; tail -5 $O/move_rate.err; fail moverate $rc; }
+      tail -2 $O/move_rate.out ;;
     labelkernels)
       here=$PWD   # (the repository's root: the script has changed into it)
       ( cd /tmp; export TMPDIR=/tmp; timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d $O/trace_label -o t -- python $here/tools/label_kernels.py run > $O/label_kernels.out 2> $O/label_kernels.err ) || fail labelkernels $?

@@ -37,6 +37,13 @@ DIST_MAX_D2 = 195075
 LABEL_EMPTY, LABEL_CONN_18, LABEL_CONN_26 = 1, 2, 4
 LABEL_RESULT = np.dtype([("cells", np.int64), ("components", np.int32), ("reserved", np.int32)])
 assert LABEL_RESULT.itemsize == 16
+# vrt_voxel_move / vrt_move_result (vrt_move_voxels)
+MOVE_ERASE_SOURCE, MOVE_KEEP_SOLID, MOVE_DRY_RUN, MOVE_IF_FREE = 1, 2, 4, 8
+MOVE_M_MAX, MOVE_T_MAX = 1 << 20, 1 << 40
+VOXEL_MOVE = np.dtype([("src_lo", np.int32, 3), ("src_hi", np.int32, 3), ("dst_lo", np.int32, 3), ("dst_hi", np.int32, 3), ("m", np.int32, 9),
+                       ("select_value", np.int32), ("t", np.int64, 3), ("flags", np.uint32), ("reserved", np.uint32)])
+MOVE_RESULT = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("written", np.int64), ("blocked", np.int64), ("erased", np.int64)])
+assert VOXEL_MOVE.itemsize == 120 and VOXEL_MOVE.fields["t"][1] == 88 and MOVE_RESULT.itemsize == 48
 # vrt_path_ray / vrt_radiance (vrt_trace_radiance)
 PATH_RAY = np.dtype([("origin", np.float32, 3), ("stream", np.uint32), ("dir", np.float32, 3), ("reserved", np.uint32)])
 RADIANCE = np.dtype([("rgb", np.float32, 3), ("t", np.float32)])
@@ -129,6 +136,7 @@ def declare(lib, prefix):
     sig("fetch_voxels", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), P, P, C.c_int)
     sig("distance_field", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, P, P, C.c_int)
     sig("label_components", C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, P, P, C.c_int)
+    sig("move_voxels", C.c_int, P, P, P, C.c_int, P)
     sig("sky_accumulate_clouds", C.c_int, P, C.c_int)
     sig("sky_compute_slice", C.c_int, P, C.c_int, C.c_int)
     sig("sky_accumulate_clouds_slice", C.c_int, P, C.c_int, C.c_int, C.c_int)

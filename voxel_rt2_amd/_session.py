@@ -291,6 +291,41 @@ class NativeSession:
         self._call("label_components", *box, flags, ptr, rec.ctypes.data_as(C.c_void_p), 0)
         return labels, {k: int(rec[0][k]) for k in ("cells", "components", "reserved")}
 
+    def move_voxels(self, src_lo, src_hi, dst_lo, dst_hi, m, t, flags=0, select=None, select_value=0):
+        """Move or copy the piece cells of the source box [src_lo, src_hi) into the destination box [dst_lo, dst_hi) under the integer
+        map (m: nine Q16 coefficients, row-major; t: three offsets in 2^-17 voxels) from destination cell to source cell
+        (include/vrt_api.h, vrt_move_voxels).  flags: _abi.MOVE_*.  select: None, a contiguous int32 array of the source box's shape
+        (host path: staged by the call) or a contiguous int32 torch tensor on the device of that shape, read in place without a
+        copy; a source cell takes part iff its entry equals select_value.  Returns the dict of lo, hi, written, blocked, erased; the
+        call has waited for the device."""
+        rec = np.zeros(1, _abi.VOXEL_MOVE)
+        for name, v in (("src_lo", src_lo), ("src_hi", src_hi), ("dst_lo", dst_lo), ("dst_hi", dst_hi), ("t", t)):
+            v = [int(x) for x in v]
+            if len(v) != 3:
+                raise ValueError(f"{name} has three entries")
+            if name == "t" and any(abs(x) >= 1 << 63 for x in v):
+                raise ValueError("t does not fit 64 bits")
+            rec[0][name] = v
+        m = [int(x) for x in np.asarray(m, dtype=object).reshape(-1)]
+        if len(m) != 9 or any(abs(x) >= 1 << 31 for x in m):
+            raise ValueError("m has nine entries that fit 32 bits")
+        rec[0]["m"], rec[0]["select_value"], rec[0]["flags"] = m, int(select_value), int(flags)
+        shape = tuple(max(int(h) - int(l), 0) for l, h in zip(src_lo, src_hi))
+        ptr, on_device = None, 0
+        if select is not None and hasattr(select, "data_ptr"):
+            import torch
+            if select.dtype != torch.int32 or tuple(select.shape) != shape or not select.is_contiguous():
+                raise ValueError(f"device path: `select` is a contiguous int32 device tensor of shape {list(shape)}")
+            ptr, on_device = (C.c_void_p(select.data_ptr()) if select.numel() else None), 1
+        elif select is not None:
+            if not isinstance(select, np.ndarray) or select.dtype != np.int32 or select.shape != shape or not select.flags.c_contiguous:
+                raise ValueError(f"`select` is a contiguous int32 array of shape {list(shape)}")
+            ptr = select.ctypes.data_as(C.c_void_p) if select.size else None
+        res = np.zeros(1, _abi.MOVE_RESULT)
+        self._call("move_voxels", rec.ctypes.data_as(C.c_void_p), ptr, on_device, res.ctypes.data_as(C.c_void_p))
+        return dict(lo=tuple(int(v) for v in res[0]["lo"]), hi=tuple(int(v) for v in res[0]["hi"]), written=int(res[0]["written"]),
+                    blocked=int(res[0]["blocked"]), erased=int(res[0]["erased"]))
+
     def upload_materials(self, table):
         table = np.ascontiguousarray(table, dtype=np.float32)
         if table.shape != (128, 14):

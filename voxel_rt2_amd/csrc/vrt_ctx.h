@@ -131,6 +131,8 @@ struct vrt_ctx {
     size_t dist_bytes = 0;
     uint8_t* d_label = nullptr;       // vrt_label_components: the counter words and on the host path the staged labels (plan_label_layout; grown on demand)
     size_t label_bytes = 0;
+    uint8_t* d_move = nullptr;        // vrt_move_voxels: the snapshot words, the box arrays of the larger box, the record and on the host path the staged selection (move_layout; grown on demand)
+    size_t move_bytes = 0;
     uint8_t* d_radiance_plane = nullptr;   // vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes: a work counter (256 bytes) and the scratch plane of VRT_RADIANCE_ITEMS item values (allocated on first use)
     float* d_mats = nullptr;
     Counters* d_counters = nullptr;

@@ -20,6 +20,7 @@
 #include "vrt_fill.h"
 #include "vrt_distance.h"
 #include "vrt_label.h"
+#include "vrt_move.h"
 #include "vrt_query.h"
 #include "vrt_denoise.h"
 
@@ -99,6 +100,15 @@ hipError_t launch_distance_field(hipStream_t st, int grid_res, const DistBox& p,
 // other on `st`, behind a memset of `counters` (the 16-byte record k_label_finish adds members and roots to).  labels: int32 per cell of
 // p.box (not empty), device memory, every word written; the union-find works in it.
 hipError_t launch_label_components(hipStream_t st, const LabelBox& p, const int8_t* mat, int* labels, vrt_label_result* counters);
+// vrt_move_voxels (vrt_move.h), p.src not empty; mat, rgb: the grid's arrays; snap: one word per cell of p.src; rec: the device's record.
+// launch_move_count: k_move_begin, k_move_snapshot (select: int32 per cell of p.src in device memory, or null) and, where p.dst is not
+// empty, the count pass k_move_dst<false>; the record is gathered per workgroup, one atomic a word.  The two array launches write box arrays for launch_edit -- the source box's (k_move_src), and
+// behind the source box's edit the destination box's (k_move_dst<true>, p.dst not empty); both read rec->blocked.
+hipError_t launch_move_count(hipStream_t st, const MovePlan& p, const int8_t* mat, const uint8_t* rgb, const int* select, uint32_t* snap, MoveRecord* rec);
+hipError_t launch_move_src_arrays(hipStream_t st, const MovePlan& p, const int8_t* mat, const uint8_t* rgb, const uint32_t* snap, int8_t* box_mat, uint8_t* box_rgb,
+                                  const MoveRecord* rec);
+hipError_t launch_move_dst_arrays(hipStream_t st, const MovePlan& p, const int8_t* mat, const uint8_t* rgb, const uint32_t* snap, int8_t* box_mat, uint8_t* box_rgb,
+                                  MoveRecord* rec);
 // A sampled query Q (vrt_query.h:RadianceQuery, SensorQuery, ProbeQuery): samples [s0, s0 + count) of n records (device memory) worked into
 // plane[n * count] by the query's item kernel (k_trace_radiance, k_gather_irradiance, k_gather_probes) and folded into out[n] (k_fold_query).
 // n * count <= Q::max_items; staged / oob as for launch_cast_rays; head: one word of device memory, the launch's work counter.

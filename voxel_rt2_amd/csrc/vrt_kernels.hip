@@ -2372,6 +2372,107 @@ hipError_t launch_label_components(hipStream_t st, const LabelBox& p, const int8
     return hipSuccess;
 }
 
+// ---- vrt_move_voxels: voxels of a box moved or copied under an integer affine map (vrt_move.h holds the arithmetic and the passes' order) ----
+//   k_move_snapshot  a thread a cell of the source box, z fastest: the cell's word (move_snap_cell) stored; the piece cells the call
+//                    vacates counted into `erased`.
+//   k_move_dst       a workgroup a tile of VRT_MOVE_TX x TY x TZ cells of the destination box, a thread a run of VRT_MOVE_RUN cells along z: the
+//                    map once, then the z step.  A tile's source cells are a slab a few cells thick whatever the map turns it to, one
+//                    4-byte word a cell.  <false> is the count pass, <true> writes the destination box's arrays, a wave's lanes on 64
+//                    consecutive z of one line; it reads the count pass's `blocked` for VRT_MOVE_IF_FREE.
+//   k_move_src       a thread a cell of the source box: the source box's arrays.
+// The record: the two counting kernels run at most VRT_MOVE_COUNT_BLOCKS workgroups, each striding over cells or tiles with its tallies in
+// registers; at the end a wave folds them by shuffles, the workgroup's four waves meet in LDS and ONE thread adds to the record's words.
+// (One atomic a wave and tile was measured first: on a half-full 128^3 grid the 260 000 atomics on the record's one cache line were
+// 0.7 of the count pass's 0.8 ms.)  Plain C++ and vector memory operations throughout.
+#define VRT_MOVE_COUNT_BLOCKS 2048
+__global__ __launch_bounds__(64) void k_move_begin(MoveRecord* rec) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) move_record_begin(*rec);
+}
+static __device__ __forceinline__ void move_tally_fold(MoveTally& t) {   // over the wave; every lane ends with the wave's
+    for (int d = 32; d > 0; d >>= 1) {
+        t.written += __shfl_xor(t.written, d, 64);
+        t.blocked += __shfl_xor(t.blocked, d, 64);
+        for (int a = 0; a < 3; a++) { t.lo[a] = min(t.lo[a], __shfl_xor(t.lo[a], d, 64)); t.hi[a] = max(t.hi[a], __shfl_xor(t.hi[a], d, 64)); }
+    }
+}
+__global__ __launch_bounds__(256) void k_move_snapshot(MovePlan p, int n, const int8_t* __restrict__ mat, const uint8_t* __restrict__ rgb, const int* __restrict__ select,
+                                                       uint32_t* __restrict__ snap, MoveRecord* rec) {
+    __shared__ unsigned part[4];
+    unsigned pieces = 0u;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {   // (n <= 2^24, the stride <= 2^19: no overflow)
+        const uint32_t w = move_snap_cell(p, i, mat, rgb, select);
+        snap[i] = w;
+        pieces += move_vacated(p.flags, w) ? 1u : 0u;
+    }
+    for (int d = 32; d > 0; d >>= 1) pieces += __shfl_xor(pieces, d, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = pieces;
+    __syncthreads();
+    if (threadIdx.x == 0 && part[0] + part[1] + part[2] + part[3]) atomicAdd(&rec->erased, (unsigned long long)(part[0] + part[1] + part[2] + part[3]));
+}
+template <bool BUILD>
+__global__ __launch_bounds__(256) void k_move_dst(MovePlan p, int tiles, const int8_t* __restrict__ mat, const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ snap,
+                                                  int8_t* __restrict__ box_mat, uint8_t* __restrict__ box_rgb, MoveRecord* rec) {
+    __shared__ MoveTally part[4];
+    MoveTally t = move_tally_none();
+    const bool go = BUILD ? move_go(p.flags, rec->blocked) : true;
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        int x, y, z;
+        const int n = move_tile_run(p, tile, threadIdx.x, x, y, z);
+        if (n > 0) move_dst_run<BUILD>(p, go, x, y, z, n, mat, rgb, snap, box_mat, box_rgb, t);
+    }
+    if (!BUILD) {
+        move_tally_fold(t);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = t;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < 4; w++) {
+                t.written += part[w].written; t.blocked += part[w].blocked;
+                for (int a = 0; a < 3; a++) { t.lo[a] = min(t.lo[a], part[w].lo[a]); t.hi[a] = max(t.hi[a], part[w].hi[a]); }
+            }
+            if (t.blocked) atomicAdd(&rec->blocked, (unsigned long long)t.blocked);
+            if (t.written) {
+                atomicAdd(&rec->written, (unsigned long long)t.written);
+                for (int a = 0; a < 3; a++) { atomicMin(&rec->lo[a], t.lo[a]); atomicMax(&rec->hi[a], t.hi[a]); }
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_move_src(MovePlan p, int n, const int8_t* __restrict__ mat, const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ snap,
+                                                  int8_t* __restrict__ box_mat, uint8_t* __restrict__ box_rgb, const MoveRecord* rec) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) move_src_build(p, move_go(p.flags, rec->blocked), i, mat, rgb, snap, box_mat, box_rgb);
+}
+hipError_t launch_move_count(hipStream_t st, const MovePlan& p, const int8_t* mat, const uint8_t* rgb, const int* select, uint32_t* snap, MoveRecord* rec) {
+    const int n_src = edit_box_voxels(p.src);
+    if (n_src == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_move_begin, dim3(1), dim3(64), 0, st, rec);
+    VRT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_move_snapshot, dim3(std::min((n_src + 255) / 256, VRT_MOVE_COUNT_BLOCKS)), dim3(256), 0, st, p, n_src, mat, rgb, select, snap, rec);
+    VRT_LAUNCH_CHECK();
+    if (edit_box_voxels(p.dst) != 0) {
+        const int tiles = move_tile_count(p);
+        hipLaunchKernelGGL(k_move_dst<false>, dim3(std::min(tiles, VRT_MOVE_COUNT_BLOCKS)), dim3(256), 0, st, p, tiles, mat, rgb, (const uint32_t*)snap, (int8_t*)nullptr,
+                           (uint8_t*)nullptr, rec);
+        VRT_LAUNCH_CHECK();
+    }
+    return hipSuccess;
+}
+hipError_t launch_move_src_arrays(hipStream_t st, const MovePlan& p, const int8_t* mat, const uint8_t* rgb, const uint32_t* snap, int8_t* box_mat, uint8_t* box_rgb,
+                                  const MoveRecord* rec) {
+    const int n_src = edit_box_voxels(p.src);
+    if (n_src == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_move_src, dim3((n_src + 255) / 256), dim3(256), 0, st, p, n_src, mat, rgb, snap, box_mat, box_rgb, rec);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+hipError_t launch_move_dst_arrays(hipStream_t st, const MovePlan& p, const int8_t* mat, const uint8_t* rgb, const uint32_t* snap, int8_t* box_mat, uint8_t* box_rgb,
+                                  MoveRecord* rec) {
+    if (edit_box_voxels(p.dst) == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_move_dst<true>, dim3(move_tile_count(p)), dim3(256), 0, st, p, move_tile_count(p), mat, rgb, snap, box_mat, box_rgb, rec);
+    VRT_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
 // A sampled query's chunk -- samples [s0, s0 + count) of n records -- worked into `plane` by the query's item kernel and folded into `out`.
 // n * count is at most Q::max_items (plan_query_chunk); `head`: the launch's work counter, zeroed here on the stream.
 template <class Q>

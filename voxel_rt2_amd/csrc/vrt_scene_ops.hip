@@ -76,6 +76,67 @@ int vrt_update_voxels(vrt_ctx* c, const int32_t lo[3], const int32_t hi[3], cons
     }
     return finish_edit(c, box, box_mat, box_rgb);
 }
+// Move or copy the piece cells of the source box under the map of `mv` (vrt_move.h): snapshot and count on the context's stream, then
+// the source box's arrays and the destination box's, each through launch_edit like any other box -- ordered and synchronised as
+// vrt_update_voxels, with ONE wait, for the record and the culling record together.  VRT_MOVE_DRY_RUN reads and nothing else: it is
+// ordered like vrt_fetch_voxels (no enter(), no flush) and waits for its record alone.  The source box's edit is left out where the
+// call vacates nothing (no VRT_MOVE_ERASE_SOURCE): its arrays would be the grid's own bytes.
+static_assert(sizeof(vrt_voxel_move) == 120 && sizeof(vrt_move_result) == 48 && sizeof(MoveRecord) == 48, "record sizes of include/vrt_api.h");
+static_assert(VRT_MOVE_ERASE_SOURCE == 1 && VRT_MOVE_KEEP_SOLID == 2 && VRT_MOVE_DRY_RUN == 4 && VRT_MOVE_IF_FREE == 8 && VRT_MOVE_FLAGS == 15u, "the flag bits vrt_move.h tests");
+static_assert(VRT_MOVE_TILE == 256 * VRT_MOVE_RUN, "k_move_dst: a thread a run");
+int vrt_move_voxels(vrt_ctx* c, const vrt_voxel_move* mv, const void* select, int select_on_device, vrt_move_result* result) {
+    if (!c || !mv) return fail(VRT_E_INVALID, "null argument");
+    if (select_on_device != 0 && select_on_device != 1) return fail(VRT_E_INVALID, "select_on_device must be 0 or 1");
+    long long t[3];
+    for (int a = 0; a < 3; a++) t[a] = (long long)mv->t[a];
+    EditBox src, dst;
+    for (int a = 0; a < 3; a++) { dst.lo[a] = mv->dst_lo[a]; dst.hi[a] = mv->dst_hi[a]; }
+    const char* const bad = !move_valid(mv->m, t, mv->flags, mv->reserved) ? "m within +-2^20, t within +-2^40, known flag bits and reserved == 0 are required"
+                            : !edit_box_valid(dst, c->cfg.grid_res)         ? "the destination box must satisfy 0 <= lo <= hi <= grid_res on every axis"
+                                                                            : nullptr;
+    if (const int rc = scene_box(c, mv->src_lo, mv->src_hi, "vrt_move_voxels edits", src, bad)) return rc;
+    if (result) memset(result, 0, sizeof(*result));
+    const size_t n_src = (size_t)edit_box_voxels(src), n_dst = (size_t)edit_box_voxels(dst);
+    if (n_src == 0) return VRT_OK;
+    const bool dry = (mv->flags & VRT_MOVE_DRY_RUN) != 0u;
+    if (dry) HIP_TRY(hipSetDevice(c->device));
+    else if (enter(c) != VRT_OK) return VRT_E_DEVICE;
+    const MovePlan p = move_plan(src, dst, mv->m, t, mv->select_value, mv->flags, c->cfg.grid_res);
+    const bool staged = select != nullptr && !select_on_device;
+    const MoveLayout l = move_layout(n_src, n_dst, staged);
+    if (grow_scratch(c, &c->d_move, &c->move_bytes, l.bytes) != VRT_OK) return VRT_E_DEVICE;
+    uint32_t* const snap = (uint32_t*)c->d_move;
+    int8_t* const box_mat = (int8_t*)(c->d_move + l.mat_at);
+    uint8_t* const box_rgb = c->d_move + l.rgb_at;
+    MoveRecord* const rec = (MoveRecord*)(c->d_move + l.record_at);
+    const int* d_select = (const int*)select;
+    if (!dry) c->main_dirty = true;
+    if (staged) {
+        HIP_TRY(hipMemcpyAsync(c->d_move + l.select_at, select, 4 * n_src, hipMemcpyHostToDevice, c->stream));
+        d_select = (const int*)(c->d_move + l.select_at);
+    }
+    HIP_TRY(launch_move_count(c->stream, p, c->d_mat, c->d_rgb, d_select, snap, rec));
+    MoveRecord r;   // (on this stack frame: the one wait below covers the copy)
+    HIP_TRY(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    if (dry) HIP_TRY(sync_stream_only(c, c->stream));   // (also ends the loan of the host selection)
+    else {
+        const EditBox* const boxes[2] = {(mv->flags & VRT_MOVE_ERASE_SOURCE) ? &src : nullptr, n_dst ? &dst : nullptr};
+        for (int k = 0; k < 2; k++) {   // source box first; the arrays are shared: stream order lets the second box reuse them
+            if (!boxes[k]) continue;
+            if (k == 0) HIP_TRY(launch_move_src_arrays(c->stream, p, c->d_mat, c->d_rgb, snap, box_mat, box_rgb, rec));
+            else HIP_TRY(launch_move_dst_arrays(c->stream, p, c->d_mat, c->d_rgb, snap, box_mat, box_rgb, rec));
+            HIP_TRY(launch_edit(c->stream, c->cfg.grid_res, *boxes[k], box_mat, box_rgb, c->d_mat, c->d_rgb, c->d_grid, c->d_l0, c->d_l1, c->d_l2, c->d_l3, c->d_l0c,
+                                c->d_l0c_base, c->d_cull));
+        }
+        if (const int rc = read_cull_record(c)) return rc;
+    }
+    if (result) {
+        long long written, blocked, erased;
+        move_result(mv->flags, r, result->lo, result->hi, written, blocked, erased);
+        result->written = written; result->blocked = blocked; result->erased = erased;
+    }
+    return VRT_OK;
+}
 // ---- asking the scene: vrt_cast_rays, vrt_trace_radiance, vrt_gather_irradiance, vrt_gather_probes, vrt_fetch_voxels ------------------------------
 // All READ scene data (pyramid, texels, stored voxels), on the context's stream: behind every edit queued so far, ahead of every
 // later one.  Render launches read the same data on their own streams and nothing here writes what they or their passes touch, so

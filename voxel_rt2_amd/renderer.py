@@ -670,6 +670,81 @@ class Renderer(VoxelStore):
         self._edit_from_device(lo, hi, torch.where(gone, torch.zeros_like(bm), bm), torch.where(gone[..., None], torch.zeros_like(bc), bc), reset)
         return count
 
+    # -- moving what is there (include/vrt_api.h, vrt_move_voxels; no counterpart in the reference) ---------------------------------------
+    @staticmethod
+    def rotation_matrix(axis, degrees):
+        """The 3x3 rotation by `degrees` about `axis` ("x", "y", "z" or a 3-vector), float64; a multiple of 90 degrees about a
+        coordinate axis comes out in exact integers."""
+        axis = {"x": (1.0, 0.0, 0.0), "y": (0.0, 1.0, 0.0), "z": (0.0, 0.0, 1.0)}.get(axis, axis) if isinstance(axis, str) else axis
+        k = np.asarray(axis, np.float64)
+        k = k / np.linalg.norm(k)
+        q = float(degrees) / 90.0
+        c, s = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(q) % 4] if q == int(q) else (np.cos(np.radians(degrees)), np.sin(np.radians(degrees)))
+        K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+        return np.eye(3) * c + s * K + (1.0 - c) * np.outer(k, k)
+
+    @staticmethod
+    def move_transform(rotation=None, pivot=None, shift=(0, 0, 0)):
+        """(m, t) of vrt_move_voxels for the FORWARD map p' = R (p - pivot) + pivot + shift in array-index space (a cell's centre is
+        its index + 0.5; pivot and shift may be fractional; R any invertible 3x3, by default the identity): the map is inverted in
+        float64 and rounded here -- m = rint(R^-1 * 2^16), t = rint((pivot - R^-1 (pivot + shift)) * 2^17) -- and the library sees the
+        integers only."""
+        R = np.eye(3) if rotation is None else np.asarray(rotation, np.float64).reshape(3, 3)
+        pivot = np.zeros(3) if pivot is None else np.asarray(pivot, np.float64).reshape(3)
+        shift = np.asarray(shift, np.float64).reshape(3)
+        inv = np.linalg.inv(R)
+        m = np.rint(inv * 65536.0).astype(np.int64)
+        t = np.rint((pivot - inv @ (pivot + shift)) * 131072.0).astype(np.int64)
+        return m, t
+
+    def moved_box(self, src_lo, src_hi, rotation=None, pivot=None, shift=(0, 0, 0)):
+        """Where the source box [src_lo, src_hi) goes under the forward map of move_transform: the bounds of its eight mapped corners,
+        grown by one cell and clipped to the grid -- (lo, hi) of array indices, the default destination box of move_voxels."""
+        R = np.eye(3) if rotation is None else np.asarray(rotation, np.float64).reshape(3, 3)
+        pivot = np.zeros(3) if pivot is None else np.asarray(pivot, np.float64).reshape(3)
+        shift = np.asarray(shift, np.float64).reshape(3)
+        corners = np.array([[(src_lo, src_hi)[(k >> a) & 1][a] for a in range(3)] for k in range(8)], np.float64)
+        image = (corners - pivot) @ R.T + pivot + shift
+        g = self.voxel_grid_res
+        lo = np.clip(np.floor(image.min(0)).astype(np.int64) - 1, 0, g)
+        hi = np.clip(np.ceil(image.max(0)).astype(np.int64) + 1, 0, g)
+        return tuple(int(v) for v in lo), tuple(int(v) for v in np.maximum(hi, lo))
+
+    def move_voxels(self, src_lo, src_hi, rotation=None, pivot=None, shift=(0, 0, 0), select=None, select_value=0, copy=False, keep_solid=False,
+                    if_free=False, dry_run=False, dst_lo=None, dst_hi=None, reset=True):
+        """Move the solid voxels of the box [src_lo, src_hi) of array indices by p' = rotation (p - pivot) + pivot + shift, on the device
+        (include/vrt_api.h, vrt_move_voxels): every cell of the destination box [dst_lo, dst_hi) -- by default moved_box(...) -- whose
+        centre maps back into a solid, selected cell of the source box takes that cell's material and colour, and the source's cells
+        are emptied (copy=True: they stay).  select: an int32 array or device tensor of the source box's shape, e.g. the labels of
+        label_components over the same box; only cells equal to select_value take part.  keep_solid: solid cells in the way keep
+        their voxel; if_free: nothing at all happens if a solid cell is in the way; dry_run: only the counts.  Nearest-neighbour
+        resampling: turns by multiples of 90 degrees about a pivot that maps cell centres to cell centres are exact, any other map
+        may lose or double voxels (compare written and erased).  Returns the dict of lo, hi (the tight box written), written, blocked
+        (solid cells that were in the way) and erased, and brings voxel_material / voxel_color in step over both boxes.  reset: start a
+        fresh accumulation if the grid changed."""
+        lo, hi = self._label_box("move_voxels", src_lo, src_hi)
+        m, t = self.move_transform(rotation, pivot, shift)
+        box = self.moved_box(lo, hi, rotation, pivot, shift)
+        dst_lo = [int(v) for v in (box[0] if dst_lo is None else dst_lo)]
+        dst_hi = [int(v) for v in (box[1] if dst_hi is None else dst_hi)]
+        flags = ((0 if copy else _abi.MOVE_ERASE_SOURCE) | (_abi.MOVE_KEEP_SOLID if keep_solid else 0) | (_abi.MOVE_IF_FREE if if_free else 0)
+                 | (_abi.MOVE_DRY_RUN if dry_run else 0))
+        if select is not None and not hasattr(select, "data_ptr"):
+            select = np.ascontiguousarray(select, np.int32)
+        res = self._s.move_voxels(lo, hi, dst_lo, dst_hi, m, t, flags, select, select_value)
+        if not dry_run and (res["written"] or res["erased"]):
+            if res["erased"]:
+                self.sync_voxels_from_device(lo, hi)
+            if res["written"]:
+                self.sync_voxels_from_device(res["lo"], res["hi"])
+            if reset:
+                self.reset_framebuffer()
+        return res
+
+    def copy_voxels(self, src_lo, src_hi, **kwargs):
+        """move_voxels(copy=True): the source keeps its voxels."""
+        return self.move_voxels(src_lo, src_hi, copy=True, **kwargs)
+
     def sealed_cavities(self, lo, hi):
         """The cells a flood from outside cannot reach: a boolean device tensor of shape hi - lo marking the non-solid cells of the box
         [lo, hi) whose 6-connected component of non-solid cells touches no face of the box."""
