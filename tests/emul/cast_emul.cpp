@@ -1,4 +1,4 @@
-// cast_emul.cpp -- TEST TOOLING: the loop of k_cast_rays (voxel_rt2_amd/csrc/vrt_kernels.hip) run on the host over cast_row of
+// cast_emul.cpp -- TEST TOOLING: the loop of k_cast_rays (voxel_rt2_amd/csrc/vrt_query_kernels.hip) run on the host over cast_row of
 // voxel_rt2_amd/csrc/vrt_cast.h, ray by ray, on a pyramid and texel grid the test hands over (tests/edit.py builds them in numpy);
 // the loop of k_fetch_voxels; and the plain decisions of vrt_cast_rays (vrt_plan.h).  The views of the pyramid and the scene record's
 // conversion are tests/emul/query_emul.h's.  tests/cast.py compiles this with g++ and calls it through ctypes.

@@ -1,4 +1,4 @@
-// distance_emul.cpp -- TEST TOOLING: the loops of the k_dist_* kernels (voxel_rt2_amd/csrc/vrt_kernels.hip) and of vrt_distance_field
+// distance_emul.cpp -- TEST TOOLING: the loops of the k_dist_* kernels (voxel_rt2_amd/csrc/vrt_scene_kernels.hip) and of vrt_distance_field
 // (vrt_scene_ops.hip) run on the host over the functions of voxel_rt2_amd/csrc/vrt_distance.h: the same checks, the same grown box, the same
 // scratch layout (plan_distance_layout), pass z line by line, passes y and x tile by tile with the lanes and groups of a workgroup one
 // after the other, each staging its lines in a local array the way the kernels stage them in LDS.  tests/distance.py compiles this with

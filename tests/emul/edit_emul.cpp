@@ -1,4 +1,4 @@
-// edit_emul.cpp -- TEST TOOLING: the loops of the k_edit_* kernels (voxel_rt2_amd/csrc/vrt_kernels.hip, launch_edit) run on the host over
+// edit_emul.cpp -- TEST TOOLING: the loops of the k_edit_* kernels (voxel_rt2_amd/csrc/vrt_scene_kernels.hip, launch_edit) run on the host over
 // the functions of voxel_rt2_amd/csrc/vrt_edit.h, index by index, in the order launch_edit queues them (the loops: edit_emul.h).
 // tests/test_voxel_edit_host.py compiles this with g++ and calls it through ctypes.
 #include "edit_emul.h"

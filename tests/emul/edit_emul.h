@@ -1,6 +1,6 @@
 // edit_emul.h -- TEST TOOLING shared by edit_emul.cpp, voxelize_emul.cpp and fill_emul.cpp: launch_edit's loops, and what the emulations
 // of the two triangle edits (vox_emul_call, fill_emul_call) have in common -- the checks of tri_edit (voxel_rt2_amd/csrc/vrt_scene_ops.hip),
-// the count-and-bounds tally both resolve kernels end on (tri_tally, vrt_kernels.hip) and the result record's conversion.
+// the count-and-bounds tally both resolve kernels end on (tri_tally, vrt_scene_kernels.hip) and the result record's conversion.
 #pragma once
 #include <cstring>
 #include "../../voxel_rt2_amd/csrc/vrt_voxelize.h"

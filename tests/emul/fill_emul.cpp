@@ -1,4 +1,4 @@
-// fill_emul.cpp -- TEST TOOLING: the loops of the k_fill_* kernels (voxel_rt2_amd/csrc/vrt_kernels.hip) and of vrt_fill_triangles
+// fill_emul.cpp -- TEST TOOLING: the loops of the k_fill_* kernels (voxel_rt2_amd/csrc/vrt_scene_kernels.hip) and of vrt_fill_triangles
 // (vrt_scene_ops.hip) run on the host over the functions of voxel_rt2_amd/csrc/vrt_fill.h: the set-up pass triangle by triangle, the
 // rasterise pass grab by grab with the 64 lanes of a wave one after the other, ONE resolve voxel by voxel after every batch, then
 // launch_edit's loops (vrt_edit.h) -- in batches whose size the caller chooses.  tests/fill.py compiles this with g++ and calls it

@@ -1,4 +1,4 @@
-// label_emul.cpp -- TEST TOOLING: the loops of the k_label_* kernels (voxel_rt2_amd/csrc/vrt_kernels.hip) and of vrt_label_components
+// label_emul.cpp -- TEST TOOLING: the loops of the k_label_* kernels (voxel_rt2_amd/csrc/vrt_scene_kernels.hip) and of vrt_label_components
 // (vrt_scene_ops.hip) run on the host over the functions of voxel_rt2_amd/csrc/vrt_label.h: the same checks, the same tiles, the same
 // scratch layout (plan_label_layout), phase by phase -- every tile solved in a local array the way the kernel solves it in LDS, then the
 // seams, then the finish in place.  What the device leaves to its scheduler is a parameter here: `seed` != 0 shuffles the order in which

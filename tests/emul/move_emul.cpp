@@ -1,4 +1,4 @@
-// move_emul.cpp -- TEST TOOLING: the loops of the k_move_* kernels (voxel_rt2_amd/csrc/vrt_kernels.hip) and of vrt_move_voxels
+// move_emul.cpp -- TEST TOOLING: the loops of the k_move_* kernels (voxel_rt2_amd/csrc/vrt_scene_kernels.hip) and of vrt_move_voxels
 // (vrt_scene_ops.hip) run on the host over the functions of voxel_rt2_amd/csrc/vrt_move.h: the same checks, the same tiles and runs, the
 // same scratch layout (move_layout), pass by pass in the order the call queues them -- snapshot, count, the source box's arrays and their
 // store, the destination box's arrays (built from the grid as the first store left it) and theirs.  Of launch_edit only the store of the

@@ -1,6 +1,6 @@
 // query_emul.h -- TEST TOOLING: what the host builds of the three scene queries share (cast_emul.cpp, radiance_emul.cpp, sensor_emul.cpp).
 // The staged view of the pyramid, the scene record the tests fill and its conversion to what the device functions read, the choice of
-// view, the block loop of a sampled query -- driven the way vrt_scene_ops.hip (sampled_query) and the kernels of vrt_kernels.hip drive it,
+// view, the block loop of a sampled query -- driven the way vrt_scene_ops.hip (sampled_query) and the kernels of vrt_query_kernels.hip drive it,
 // through the same traits (voxel_rt2_amd/csrc/vrt_query.h) -- and the small scene of the stand-alone programs.
 #pragma once
 #include <cstring>
@@ -9,7 +9,7 @@
 
 using namespace vrt;
 
-// The staged view of the kernels (LdsPyramid, vrt_kernels.hip: device only) restated for the host: the same members and reads, the coarse
+// The staged view of the kernels (LdsPyramid, vrt_views.h: device only) restated for the host: the same members and reads, the coarse
 // levels in copies of their own where the kernel has them in LDS.  OOB as there: whether the type carries the reference's reading
 // of cells outside the grid.
 template <int G_, bool OOB_>

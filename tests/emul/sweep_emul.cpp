@@ -1,4 +1,4 @@
-// sweep_emul.cpp -- TEST TOOLING: the loop of k_sweep_boxes (voxel_rt2_amd/csrc/vrt_kernels.hip) run on the host over the functions of
+// sweep_emul.cpp -- TEST TOOLING: the loop of k_sweep_boxes (voxel_rt2_amd/csrc/vrt_query_kernels.hip) run on the host over the functions of
 // voxel_rt2_amd/csrc/vrt_sweep.h, box by box: the lanes of a box one after the other, merged with the same order function the kernel's
 // butterfly uses, on pyramid levels the test hands over (tests/edit.py builds them in numpy); the candidate region, the validity gate
 // and the plain decisions of vrt_sweep_boxes (vrt_plan.h).  tests/sweep.py compiles this with g++ and calls it through ctypes.

@@ -1,4 +1,4 @@
-// voxelize_emul.cpp -- TEST TOOLING: the loops of the k_vox_* kernels (voxel_rt2_amd/csrc/vrt_kernels.hip) and of vrt_voxelize_triangles
+// voxelize_emul.cpp -- TEST TOOLING: the loops of the k_vox_* kernels (voxel_rt2_amd/csrc/vrt_scene_kernels.hip) and of vrt_voxelize_triangles
 // (vrt_scene_ops.hip) run on the host over the functions of voxel_rt2_amd/csrc/vrt_voxelize.h: the set-up pass triangle by triangle, the
 // rasterise pass grab by grab with the 64 lanes of a wave one after the other, the resolve voxel by voxel, then launch_edit's loops
 // (vrt_edit.h) -- in chunks whose size the caller chooses, so that ownership has to carry across them.  tests/voxelize.py compiles this

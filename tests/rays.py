@@ -54,7 +54,7 @@ def config(name):
 
 
 def grown_box(mat):
-    """k_cull_box (vrt_kernels.hip) from the voxel array: bounds of the solids at 4x4x4 brick granularity, +- 8 voxels.
+    """k_cull_box (vrt_scene_kernels.hip) from the voxel array: bounds of the solids at 4x4x4 brick granularity, +- 8 voxels.
     Returns lo[3], hi[3] (lo > hi without solids) and whether the box leaves part of the grid out (cull[6])."""
     G = mat.shape[0]
     bricks = (mat > 0).reshape(G // 4, 4, G // 4, 4, G // 4, 4).any(axis=(1, 3, 5))

@@ -95,7 +95,7 @@ def one_voxel_rays():
 
 @pytest.mark.parametrize("n_rays", [1, 63, 64, 65, 257])
 def test_batch_sizes_around_a_waves_reservation(one_voxel_rays, n_rays):
-    """A wave's take of 64 items, its short last take and a second workgroup (WaveItems, vrt_kernels.hip): 3 samples of n_rays rays on
+    """A wave's take of 64 items, its short last take and a second workgroup (WaveItems, vrt_query_kernels.hip): 3 samples of n_rays rays on
     the device path against the host build of the same functions, byte for byte."""
     rays, host_scene = one_voxel_rays
     rays = rays[(np.arange(n_rays) * 5) % len(rays)]

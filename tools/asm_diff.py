@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Are the device functions of this tree's kernels the machine code another revision generates?  Compiles voxel_rt2_amd/csrc/vrt_kernels.hip
-for the device alone (hipcc -S, the library's flags) from this tree and from REV's csrc/ and include/ (git archive into a temporary
-folder), cuts both listings into functions and compares every function both have, instruction for instruction: comments dropped, block
-labels renumbered in order of appearance (a function's labels carry its number in the file, which moves when functions are added).
+"""Are the device functions of this tree's kernels the machine code another revision generates?  Compiles each side's kernel units
+(KERNEL_SOURCES of its own voxel_rt2_amd/build.py; a revision from before there was such a list: its SOURCES without vrt_api.hip) for the
+device alone (hipcc -S, this tree's flags, a process per unit) from this tree and from REV's csrc/, include/ and build.py (git archive
+into a temporary folder), cuts the listings into functions and compares every function both sides have, whichever unit holds it,
+instruction for instruction: comments dropped, block labels renumbered in order of appearance (a function's labels carry its number in
+the file, which moves when functions are added).  A function that two units of one side define is an error (exit status 2).
 
     python tools/asm_diff.py [REV] [--rename REGEX=REPL ...] [-DNAME[=VALUE] ...] [name-substring ...]         REV: default HEAD~1
 
@@ -14,26 +16,52 @@ tree's demangled names with re.sub(REGEX, REPL, name) first, e.g. --rename '(k_r
 Prints one line per function that differs or that only one side has, then the counts; exit status 1 if a function both have differs.
 A function that holds the same multiset of instruction lines in another order (the scheduler swapping independent instructions) is
 reported apart from one whose instructions differ; both count for the exit status."""
+import importlib.util
 import os
 import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from voxel_rt2_amd import build as B  # noqa: E402
 
-SRC = os.path.join("voxel_rt2_amd", "csrc", "vrt_kernels.hip")
+CSRC = os.path.join("voxel_rt2_amd", "csrc")
+MAX_PROCS = 8   # compiler processes at a time
 
 
 DEFINES = []
 
 
-def listing(root, out):
+def kernel_sources(root):
+    """The units of `root` that hold device code, by root's own build.py."""
+    spec = importlib.util.spec_from_file_location("_asm_diff_build", os.path.join(root, "voxel_rt2_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return list(getattr(mod, "KERNEL_SOURCES", None) or [s for s in mod.SOURCES if s != "vrt_api.hip"])
+
+
+def listing(root, src, out):
     flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC")] + DEFINES
-    subprocess.run([B._hipcc()] + flags + ["--offload-device-only", "-S", os.path.join(root, SRC), "-o", out], check=True, capture_output=True)
+    subprocess.run([B._hipcc()] + flags + ["--offload-device-only", "-S", os.path.join(root, CSRC, src), "-o", out], check=True, capture_output=True)
     return open(out).read()
+
+
+def side(root, tmp, tag, what):
+    """{demangled name: [instruction lines]} over all kernel units of `root`, compiled side by side."""
+    srcs = kernel_sources(root)
+    with ThreadPoolExecutor(max_workers=min(len(srcs), MAX_PROCS)) as pool:
+        texts = list(pool.map(lambda s: listing(root, s, os.path.join(tmp, f"{tag}_{s}.s")), srcs))
+    out, home = {}, {}
+    for src, text in zip(srcs, texts):
+        for n, body in functions(text).items():
+            if n in out:
+                print(f"error: {what} defines {n[:150]} in two units, {home[n]} and {src}", file=sys.stderr)
+                sys.exit(2)
+            out[n], home[n] = body, src
+    return out
 
 
 def functions(text):
@@ -80,9 +108,9 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         old = os.path.join(tmp, "rev")
         os.makedirs(old)
-        tar = subprocess.run(["git", "-C", ROOT, "archive", rev, "voxel_rt2_amd/csrc", "include"], check=True, capture_output=True).stdout
+        tar = subprocess.run(["git", "-C", ROOT, "archive", rev, "voxel_rt2_amd/csrc", "voxel_rt2_amd/build.py", "include"], check=True, capture_output=True).stdout
         subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)
-        a, b = functions(listing(old, os.path.join(tmp, "a.s"))), functions(listing(ROOT, os.path.join(tmp, "b.s")))
+        a, b = side(old, tmp, "a", rev), side(ROOT, tmp, "b", "this tree")
     for pat, repl in renames:
         b = {re.sub(pat, repl, n): body for n, body in b.items()}
     pick = lambda n: not args or any(s in n for s in args)

@@ -2,7 +2,9 @@
 """List the loops of one kernel in a hipcc -S listing with their static instruction counts.
 
 usage: isa_loops.py k.s '_ZN3vrt8k_renderILb0ELb0EE' [min_instr]
-(k.s from: hipcc <build flags> --cuda-device-only -S voxel_rt2_amd/csrc/vrt_kernels.hip -o k.s)
+(k.s from: hipcc <build flags> --cuda-device-only -S voxel_rt2_amd/csrc/UNIT -o k.s, UNIT the file that holds the kernel:
+vrt_kernels.hip for the render kernels and frame passes, else vrt_scene_kernels.hip, vrt_query_kernels.hip, vrt_probe_kernels.hip
+or vrt_sky_kernels.hip)
 """
 import re, sys
 lines = open(sys.argv[1]).read().split('\n')

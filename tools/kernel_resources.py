@@ -8,7 +8,7 @@ from voxel_rt2_amd import build as B
 rows = []
 EXTRA = [a for a in sys.argv[1:] if a.startswith("-")]
 ONLY = [a for a in sys.argv[1:] if not a.startswith("-")]
-for src in B.SOURCES[:2]:
+for src in B.KERNEL_SOURCES:
     cmd = [B._hipcc()] + [f for f in B.FLAGS if f not in ("-shared",)] + EXTRA + ["-Rpass-analysis=kernel-resource-usage", "-c",
            os.path.join(B.CSRC, src), "-o", "/dev/null"]
     out = subprocess.run(cmd, capture_output=True, text=True).stderr

@@ -219,7 +219,7 @@ int main(int argc, char** argv) {
     FILE* f = fopen(argv[1], "rb");
     if (!f || fread(mat.data(), 1, mat.size(), f) != mat.size()) { printf("cannot read %s\n", argv[1]); return 1; }
     fclose(f);
-    // the bit-brick pyramid (vrt_kernels.hip: k_build_l0 / k_build_coarse / k_build_l0c)
+    // the bit-brick pyramid (vrt_scene_kernels.hip: k_build_l0 / k_build_coarse / k_build_l0c)
     std::vector<unsigned long long> l0(32 * 32 * 32, 0ULL), l1(512, 0ULL), l2(8, 0ULL), l0c;
     std::vector<uint32_t> base(513, 0u);
     size_t solid = 0;

@@ -10,11 +10,15 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libvrt_hip.so")
-SOURCES = ["vrt_kernels.hip", "vrt_sky_kernels.hip", "vrt_api.hip"]
+# the units that hold device code (tools/asm_diff.py, tools/kernel_resources.py), then the host side
+KERNEL_SOURCES = ["vrt_kernels.hip", "vrt_scene_kernels.hip", "vrt_query_kernels.hip", "vrt_probe_kernels.hip", "vrt_sky_kernels.hip"]
+SOURCES = KERNEL_SOURCES + ["vrt_api.hip"]
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
     "-ffp-contract=off", "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt",
@@ -26,6 +30,7 @@ FLAGS = [
     "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
     "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value", "-Wno-unused-result",
 ]
+LINK_FLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared"]   # of FLAGS, what the link of the units' objects takes
 
 
 def _hipcc():
@@ -33,6 +38,12 @@ def _hipcc():
         if cand and os.path.exists(cand):
             return cand
     raise RuntimeError("hipcc not found: libvrt_hip.so cannot be built (there is no CPU fallback)")
+
+
+def _run(cmd, verbose):
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    return subprocess.run(cmd, capture_output=True, text=True)
 
 
 def _deps():
@@ -71,15 +82,21 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
     out = out or OUT
     os.makedirs(os.path.dirname(out), exist_ok=True)
     tag = source_id() + ("+" + "".join(extra_flags) if extra_flags else "")
-    cmd = [_hipcc()] + FLAGS + list(extra_flags) + [f'-DVRT_BUILD_ID="{tag}"'] + [os.path.join(CSRC, s) for s in SOURCES] + ["-o", out]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        sys.stderr.write(r.stdout + r.stderr)
+    # The units are compiled side by side, one hipcc process each (one command over all of them compiles them one after the other),
+    # into objects in a folder that goes away, and linked once.
+    compile_flags = [f for f in FLAGS if f != "-shared"] + list(extra_flags) + [f'-DVRT_BUILD_ID="{tag}"']
+    with tempfile.TemporaryDirectory() as tmp:
+        objs = [os.path.join(tmp, os.path.splitext(s)[0] + ".o") for s in SOURCES]
+        cmds = [[_hipcc()] + compile_flags + ["-c", os.path.join(CSRC, s), "-o", o] for s, o in zip(SOURCES, objs)]
+        with ThreadPoolExecutor(max_workers=len(cmds)) as pool:
+            steps = list(pool.map(lambda c: _run(c, verbose), cmds))
+        if all(r.returncode == 0 for r in steps):
+            steps.append(_run([_hipcc()] + LINK_FLAGS + objs + ["-o", out], verbose))
+    if any(r.returncode != 0 for r in steps):
+        sys.stderr.write("".join(r.stdout + r.stderr for r in steps))
         raise RuntimeError("hipcc failed building libvrt_hip.so")
-    if verbose and r.stderr:
-        sys.stderr.write(r.stderr)
+    if verbose:
+        sys.stderr.write("".join(r.stderr for r in steps))
     return out
 
 

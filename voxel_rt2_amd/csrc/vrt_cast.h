@@ -1,6 +1,6 @@
 // vrt_cast.h -- vrt_cast_rays: caller-supplied rays against the prepared scene.  Which rays are walked at all, the record a ray
 // gets, and one ray's whole body (cast_row).  Plain functions over plain values, in the style of vrt_edit.h / vrt_plan.h: k_cast_rays
-// (vrt_kernels.hip) is a grid-stride loop over cast_row, one ray per lane, and tests/emul/cast_emul.cpp runs the same function on a
+// (vrt_query_kernels.hip) is a grid-stride loop over cast_row, one ray per lane, and tests/emul/cast_emul.cpp runs the same function on a
 // machine without a GPU (tests/test_cast_rays_host.py).
 //
 // A query is the reference's next_hit (pathtracer.py:218-244; next_hit in vrt_trace.h): floor plane, then the hierarchical DDA, then

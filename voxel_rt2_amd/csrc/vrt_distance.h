@@ -1,6 +1,6 @@
 // vrt_distance.h -- the arithmetic of vrt_distance_field: the exact squared Euclidean distance from every cell of a box to the nearest
 // TARGET cell of the grid (solid, or with VRT_DIST_TO_EMPTY non-solid), bounded by max_d2, and which target that is.  Plain functions
-// over plain values: the k_dist_* kernels (vrt_kernels.hip) are loops over them, one output element per call, and
+// over plain values: the k_dist_* kernels (vrt_scene_kernels.hip) are loops over them, one output element per call, and
 // tests/emul/distance_emul.cpp runs the same loops on a machine without a GPU (tests/test_distance_host.py).
 //
 // THE TRANSFORM is separable: (x-t_x)^2 + (y-t_y)^2 + (z-t_z)^2 is minimised axis by axis, z first, then y, then x.

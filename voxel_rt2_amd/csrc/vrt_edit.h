@@ -1,7 +1,7 @@
 // vrt_edit.h -- the index arithmetic of vrt_update_voxels: replacing the voxels of a box [lo, hi) of a prepared grid at a cost that
 // follows the box, not the grid.  Which voxel a box-local index is and where it sits in the grid's arrays, which cells of a pyramid
 // level a box touches, and the rebuild of one word of a level.  Plain functions over plain values: the k_edit_* kernels
-// (vrt_kernels.hip) are loops over them, one index per thread, and tests/emul/edit_emul.cpp runs the same loops on a machine without
+// (vrt_scene_kernels.hip) are loops over them, one index per thread, and tests/emul/edit_emul.cpp runs the same loops on a machine without
 // a GPU (tests/test_voxel_edit_host.py).
 //
 // A word is always RECOMPUTED from the level below (the fine level from the materials), never patched: a removed voxel clears its

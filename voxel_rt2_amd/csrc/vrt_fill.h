@@ -2,7 +2,7 @@
 // set-up for the parity test (edge functions, plane function, tie signs), the column test, the first cell of a column above the triangle,
 // the columns a triangle can own at all, its work items and one lane's share of an item, the toggle bit of (column, cell), the prefix-XOR
 // of a column's toggle words, and one voxel of the resolve.  Plain functions over plain values, in the style of vrt_voxelize.h, whose
-// snap and validity gate are used as they are: the k_fill_* kernels (vrt_kernels.hip) are loops over them, and
+// snap and validity gate are used as they are: the k_fill_* kernels (vrt_scene_kernels.hip) are loops over them, and
 // tests/emul/fill_emul.cpp runs the same loops on a machine without a GPU (tests/test_fill_host.py).
 //
 // WHAT IS COMPUTED (include/vrt_api.h, INSIDE).  Cell c is inside iff an odd number of valid triangles cross below its centre

@@ -1,6 +1,6 @@
 // vrt_label.h -- the arithmetic of vrt_label_components: which MEMBER cells of a box (solid, or with VRT_LABEL_EMPTY non-solid) hang
 // together under 6-, 18- or 26-adjacency, every cell labelled with the smallest linear grid index of its component.  Plain functions
-// over plain values: the k_label_* kernels (vrt_kernels.hip) are loops over them, and tests/emul/label_emul.cpp runs the same loops on a
+// over plain values: the k_label_* kernels (vrt_scene_kernels.hip) are loops over them, and tests/emul/label_emul.cpp runs the same loops on a
 // machine without a GPU (tests/test_label_host.py), in any order it likes.
 //
 // THE FOREST.  Every member owns one word that names a member of its own set: its PARENT, and the invariant is L[x] <= x.  A cell with

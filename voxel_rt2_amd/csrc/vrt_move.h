@@ -1,6 +1,6 @@
 // vrt_move.h -- the arithmetic of vrt_move_voxels: the voxels of a source box moved or copied under a fixed-point affine map that takes
 // a DESTINATION cell to its SOURCE cell (include/vrt_api.h states the rules).  Plain functions over plain values: the k_move_* kernels
-// (vrt_kernels.hip) are loops over them, and tests/emul/move_emul.cpp runs the same loops on a machine without a GPU
+// (vrt_scene_kernels.hip) are loops over them, and tests/emul/move_emul.cpp runs the same loops on a machine without a GPU
 // (tests/test_move_host.py).  Integers only: nothing here rounds.
 //
 // THE MAP.  S_a = sum_b m[3a+b] (2 d_b + 1) + t[a] in int64, the source cell s_a = S_a >> 17 (arithmetic: a floor).  |m| <= 2^20,

@@ -1,7 +1,7 @@
 // vrt_probe_sh.h -- vrt_gather_probes: the light at caller-supplied points in empty space as spherical-harmonic coefficients, the sun
 // kept apart.  Which probes are walked at all, one (probe, sample) item -- its sun sample, its sphere direction, its path -- the basis,
 // and the ordered sums over a probe's samples.  Plain functions over plain values, in the style of vrt_sensor.h: k_gather_probes
-// (vrt_kernels.hip) keeps one item per lane and steps it with probe_begin / probe_sun / probe_segment / probe_value between refills,
+// (vrt_query_kernels.hip) keeps one item per lane and steps it with probe_begin / probe_sun / probe_segment / probe_value between refills,
 // k_fold_query<ProbeQuery> (vrt_query.h) is a loop over probe_fold, and tests/emul/probe_emul.cpp runs the same functions on a machine
 // without a GPU (tests/test_probe_host.py).  (vrt_probe.h is the ray probe of the walk tests: another thing.)
 //

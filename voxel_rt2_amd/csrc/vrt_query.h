@@ -2,7 +2,7 @@
 // takes n input records and n_samples, works on (record, sample) items -- item i of a launch is record i % n, sample s0 + i / n -- leaves
 // each item's value in a scratch plane and folds the plane into one output record per input in sample order.  A traits struct names the
 // record types and the plane's bound and gives the query's arithmetic (vrt_radiance.h, vrt_sensor.h, vrt_probe_sh.h: it stays there) one spelling;
-// against it are written ONE fold kernel and ONE launcher (k_fold_query, launch_sampled_query: vrt_kernels.hip), ONE entry-point body
+// against it are written ONE fold kernel and ONE launcher (k_fold_query, launch_sampled_query: vrt_query_kernels.hip), ONE entry-point body
 // (sampled_query: vrt_scene_ops.hip) and ONE host loop (query_block: tests/emul/query_emul.h).  What a query keeps for itself is its per-item
 // header and the kernel that steps its items.  Plain structs of static functions, in the style of vrt_cast.h / vrt_radiance.h.
 #pragma once

@@ -1,6 +1,6 @@
 // vrt_radiance.h -- vrt_trace_radiance: path-traced radiance along caller-supplied rays.  Which rays are traced at all, one
 // (ray, sample) item from its first segment to its value, and the ordered sum over a ray's samples.  Plain functions over plain values,
-// in the style of vrt_cast.h: k_trace_radiance (vrt_kernels.hip) keeps one item per lane and steps it with radiance_begin /
+// in the style of vrt_cast.h: k_trace_radiance (vrt_query_kernels.hip) keeps one item per lane and steps it with radiance_begin /
 // radiance_segment / radiance_value between refills, k_fold_query<RadianceQuery> (vrt_query.h) is a loop over radiance_fold, and tests/emul/radiance_emul.cpp
 // runs the same functions on a machine without a GPU (tests/test_radiance_host.py).
 //

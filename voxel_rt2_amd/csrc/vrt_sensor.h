@@ -1,6 +1,6 @@
 // vrt_sensor.h -- vrt_gather_irradiance: how much light falls on caller-supplied surface points.  Which sensors are traced at all, one
 // (sensor, sample) item -- its directions, its sun term, its hemisphere path -- and the ordered sums over a sensor's samples.  Plain
-// functions over plain values, in the style of vrt_cast.h / vrt_radiance.h: k_gather_irradiance (vrt_kernels.hip) keeps one item per lane
+// functions over plain values, in the style of vrt_cast.h / vrt_radiance.h: k_gather_irradiance (vrt_query_kernels.hip) keeps one item per lane
 // and steps it with sensor_begin / sensor_sun / sensor_segment / sensor_value between refills, k_fold_query<SensorQuery> (vrt_query.h) is a loop over
 // sensor_fold, and tests/emul/sensor_emul.cpp runs the same functions on a machine without a GPU (tests/test_sensor_host.py).
 //

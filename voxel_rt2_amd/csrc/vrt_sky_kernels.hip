@@ -367,8 +367,6 @@ __global__ void k_sky_probe(SkyPrecompute sp, int op, int n, const float* in, in
     }
 }
 
-#define VRT_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
-
 hipError_t launch_sky_probe(hipStream_t st, const SkyPrecompute& sp, int op, int n, const float* in, int in_stride, float* out, int out_stride, f3 ambient) {
     hipLaunchKernelGGL(k_sky_probe, dim3((n + 63) / 64), dim3(64), 0, st, sp, op, n, in, in_stride, out, out_stride, ambient);
     VRT_LAUNCH_CHECK();

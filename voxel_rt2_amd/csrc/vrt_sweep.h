@@ -1,6 +1,6 @@
 // vrt_sweep.h -- vrt_sweep_boxes: caller-supplied axis-aligned boxes moved through the prepared scene.  Which boxes are tested at all,
 // one cell's test, the floor's, the order candidates are ranked by, the cells a box can meet at all, and one lane's share of a box
-// (sweep_lane).  Plain functions over plain values, in the style of vrt_cast.h / vrt_edit.h: k_sweep_boxes (vrt_kernels.hip) gives a box
+// (sweep_lane).  Plain functions over plain values, in the style of vrt_cast.h / vrt_edit.h: k_sweep_boxes (vrt_query_kernels.hip) gives a box
 // to a wave of 64 lanes and merges their candidates with a cross-lane minimum, and tests/emul/sweep_emul.cpp runs the same lanes one
 // after the other on a machine without a GPU (tests/test_sweep_boxes_host.py).
 //

@@ -95,6 +95,8 @@ VRT_DEV f4 mul4(const mat4& M, f4 v) {
 
 // Diagnostic build only (-DVRT_DIAG_REGIONS): per code region, how many times a WAVE entered it and with how many
 // active lanes -- where the issue slots of the divergent render kernel go.  Never defined in the shipped library.
+// `static`: every kernel unit has an array of its own, and k_diag_read reads the one of vrt_kernels.hip -- the render launches' counts,
+// which is all tools/diag_regions.py drives.  What the query kernels count through the same headers stays in their unit's copy, unread.
 #if defined(VRT_DIAG_REGIONS) && defined(__HIPCC__)
 static __device__ unsigned long long g_vrt_region[64];
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(VRT_DIAG_CLOCKS_ONLY)  // CLOCKS_ONLY: just the pooled kernel's stage clocks

@@ -2,7 +2,7 @@
 // coordinate to 64ths of a voxel, which triangles are tested at all, a triangle's set-up (edges, the thirteen axes, its projected
 // interval on each), the cube test at any power-of-two cell edge, the cells a triangle can cover at all, the work items of a triangle
 // and one lane's share of an item, and one voxel of the resolve.  Plain functions over plain values, in the style of vrt_edit.h /
-// vrt_cast.h / vrt_sweep.h: the k_vox_* kernels (vrt_kernels.hip) are loops over them, and tests/emul/voxelize_emul.cpp runs the same
+// vrt_cast.h / vrt_sweep.h: the k_vox_* kernels (vrt_scene_kernels.hip) are loops over them, and tests/emul/voxelize_emul.cpp runs the same
 // loops on a machine without a GPU (tests/test_voxelize_host.py).
 //
 // NO FLOAT SURVIVES THE SNAP.  include/vrt_api.h defines coverage on the snapped integer vertices, and everything here after vox_snap is
